@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- query-bases/s of SMEM discovery on the BASELINE.json workloads.
 
-  python bench.py [--gpus N --steps K --warmup W] [--config 1|2|3|4|5] [--mode lut|rmi|bwa]
+  python bench.py [--gpus N --steps K --warmup W] [--config 1|2|3|4|5] [--mode lut|rmi|bwa] [--dump-outputs DIR]
 
 N > 1 is launched by the driver as
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
@@ -70,6 +70,9 @@ CONFIGS = {
 K = 15
 EXPERTS = [1000]
 GEN_CHUNK = 10_000_000                           # reads are generated (on the device) in pieces
+DUMP_READS = 1 << 16                             # --dump-outputs: reads sampled from a larger batch
+DUMP_SEED = 20_261_015                           # ... and the seed of that sample
+DUMP_BYTES = 64 << 20                            # ... and the cap on all files written
 
 
 def shard_seed(cfg, world, rank):
@@ -366,9 +369,42 @@ def run_workload(args, cfg_id, mode, steps, warmup, world, rank, device, total_r
     kern_ms = [a.elapsed_time(b) for a, b in ev_k]
     path_ms = [a.elapsed_time(b) for a, b in ev]
     return dict(cfg=cfg, cfg_id=cfg_id, mode=mode, steps=steps, warmup=warmup, ix=ix, rl=rl, ref_codes=ref_codes, reads=reads,
+                offsets=offsets, rows=out[:total], status=status,
                 n_reads=n_reads, L=L, dt=dt, total=total, all_reads=int(tot[0].item()), all_rows=int(tot[1].item()),
                 kern_ms=kern_ms, path_ms=path_ms, t_build=t_build, broadcast_ms=broadcast_ms, read_kind=read_kind,
                 image_bytes=int(ix.blob.numel()))
+
+
+def dump_outputs(d, w):
+    """--dump-outputs: what the last timed step handed its caller (offsets, CSR rows, status), as .npy files in `d`
+    (float64 for the int64 offsets and the rows, float32 for status).  A batch of more than DUMP_READS reads is
+    represented by a fixed, seeded sample of DUMP_READS reads (in ascending order), and rows stop at the first sampled
+    read whose rows would take the files past DUMP_BYTES.  Files:
+      read_index [m]      which reads of the batch were sampled
+      row_offset [m]      offsets[r]: where read r's rows start in the CSR output
+      row_count  [m]      offsets[r + 1] - offsets[r]
+      status     [m]      the per-read status word
+      rows       [R, 4]   (start, end, lo, hi) of the first k sampled reads' rows, read by read
+      summary    [7]      n_reads, total rows, k, and the sums of the four columns over ALL rows of the batch"""
+    n, offsets, rows, status = w["n_reads"], w["offsets"], w["rows"], w["status"]
+    idx = np.arange(n) if n <= DUMP_READS else np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_READS, replace=False))
+    it = torch.as_tensor(idx, device=offsets.device)
+    lo = offsets[it]
+    cnt = offsets[it + 1] - lo
+    cum = torch.cumsum(cnt, 0)
+    cap_rows = (DUMP_BYTES - len(idx) * (8 + 8 + 8 + 4) - 64 * 1024) // (4 * 8)
+    k = int(torch.searchsorted(cum, torch.tensor([cap_rows], device=cum.device), right=True).item())
+    R = int(cum[k - 1].item()) if k else 0
+    src = torch.repeat_interleave(lo[:k] - (cum[:k] - cnt[:k]), cnt[:k], output_size=R) + torch.arange(R, device=lo.device)
+    colsum = rows.to(torch.int64).sum(0).cpu().numpy()
+    os.makedirs(d, exist_ok=True)
+    out = {"read_index": idx.astype(np.float64), "row_offset": lo.cpu().numpy().astype(np.float64),
+           "row_count": cnt.cpu().numpy().astype(np.float64), "status": status[it].cpu().numpy().astype(np.float32),
+           "rows": rows[src].cpu().numpy().astype(np.float64),
+           "summary": np.asarray([n, rows.shape[0], k, *colsum.tolist()], np.float64)}
+    for name, a in out.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in out.items()}
 
 
 def roofline_of(w, offcfg=()):
@@ -456,7 +492,11 @@ def main():
     ap.add_argument("--no-from-host", action="store_true")
     ap.add_argument("--no-other-configs", action="store_true", help="skip the records of the other BASELINE configs appended to the default line")
     ap.add_argument("--search-all", action="store_true", help="GENIE_OPT_SEARCH_ALL: look up every position, no sampling (A/B runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (rank 0; see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     cfg0 = CONFIGS[args.config]
     offcfg = []
@@ -493,6 +533,7 @@ def main():
     w = run_workload(args, args.config, mode, args.steps, args.warmup, world, rank, device, total_reads=args.reads,
                      read_kind=args.read_kind, read_len=args.read_len)
     cfg, ix, L, n_reads = w["cfg"], w["ix"], w["L"], w["n_reads"]
+    dumped = dump_outputs(args.dump_outputs, w) if args.dump_outputs and rank == 0 else None
 
     if rank == 0:
         roof, key, S, ms_step = roofline_of(w, offcfg)
@@ -526,6 +567,8 @@ def main():
                        "index_full_image_bytes": (w["rl"] or {}).get("full_image_bytes")},
             "roofline": roof,
         }
+        if dumped:
+            line["dumped_outputs"] = {"dir": args.dump_outputs, "shapes": dumped}
         lib = g._native.lib()
         if world == 1 and not args.no_from_host and n_reads <= 2_000_000 and L <= 255:
             saved_affinity = os.sched_getaffinity(0)

@@ -567,6 +567,31 @@ def main():
             json.dump(ds_known(data_dir), fh, indent=1, sort_keys=True)
         print("wrote known_answers.json", flush=True)
 
+    if want("checked_in"):
+        # the reference's own checked-in FM / LUT JSON fixtures, kept so the tests need no reference:
+        # small_data's sequence and FM json verbatim (5 kB); medium_data's sequence, FM suffix array
+        # and K=6 LUT as arrays (the two JSONs are 1.7 MB, mostly the BWT and occurrence matrix)
+        src = os.path.join(REF_SMEM, "data")
+        for f in ("small_data.fa", "small_data-FM.json"):
+            shutil.copy(os.path.join(src, f), os.path.join(HERE, f))
+            os.chmod(os.path.join(HERE, f), 0o644)
+        with open(os.path.join(src, "medium_data-FM.json")) as fh:
+            fm = json.load(fh)
+        with open(os.path.join(src, "medium_data-LUT.json")) as fh:
+            lut = json.load(fh)
+        keys = sorted(lut["lut"], key=int)
+        pos = [lut["lut"][k][1] for k in keys]
+        np.savez_compressed(
+            os.path.join(HERE, "medium_data_checked_in.npz"),
+            ref_codes=str_to_codes(read_fasta(os.path.join(src, "medium_data.fa"))),
+            fm_suffix_array=np.asarray(fm["suffix_array"], np.int32),
+            lut_size=np.asarray(lut["lut_size"]),
+            lut_codes=np.asarray([int(k) for k in keys], np.int64),
+            lut_interval=np.asarray([lut["lut"][k][0] for k in keys], np.int32),
+            lut_pos_off=np.cumsum([0] + [len(p) for p in pos]).astype(np.int64),
+            lut_pos=np.asarray([x for p in pos for x in p], np.int32))
+        print("wrote small_data.fa, small_data-FM.json, medium_data_checked_in.npz", flush=True)
+
     if want("medium_K6"):
         # reference's own 10 kb fixture files (FM + K=6 LUT are the checked-in JSONs, not rebuilt)
         codes = str_to_codes(read_fasta(os.path.join(data_dir, "medium_data.fa")))

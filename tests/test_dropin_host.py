@@ -53,9 +53,9 @@ def test_fasta_and_fm_json_schema(pkg, data_dir):
         pkg.ExactMatch("nothing.fa", data_dir=str(data_dir)).load_fm_index()
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/SMEM/data"), reason="reference data files not present")
 def test_fm_json_identical_to_reference_fixture(pkg, data_dir):
-    ref_dir = "/root/reference/SMEM/data"
+    """The reference's own checked-in small_data.fa and small_data-FM.json (kept in tests/golden/)."""
+    ref_dir = G.GOLDEN
     with open(os.path.join(ref_dir, "small_data.fa")) as fh:
         fh.readline()
         seq = "".join(line.strip() for line in fh)

@@ -96,24 +96,27 @@ def test_create_from_sa_rejects_garbage(pkg):
         pkg.GenieIndex.build(np.asarray([0, 4], np.uint8), 0)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/SMEM/data"), reason="reference data files not present")
 def test_reference_checked_in_fixtures(pkg):
-    """The reference's own FM / LUT json fixtures (read as data, only where the reference exists)."""
+    """The reference's own FM / LUT json fixtures (kept in tests/golden/: small_data's verbatim,
+    medium_data's suffix array and K=6 LUT as arrays, written by make_golden.py --only checked_in)."""
     import json
-    data = "/root/reference/SMEM/data"
-    for stem in ("small_data", "medium_data"):
-        with open(os.path.join(data, stem + ".fa")) as fh:
-            fh.readline()
-            seq = "".join(line.strip() for line in fh)
-        fm = json.load(open(os.path.join(data, stem + "-FM.json")))
-        ix = pkg.GenieIndex.build(G.str_to_codes(seq), 6)
-        assert ix.suffix_array().tolist() == fm["suffix_array"]
-    lut = json.load(open(os.path.join(data, "medium_data-LUT.json")))
-    assert lut["lut_size"] == 6
+    with open(os.path.join(G.GOLDEN, "small_data.fa")) as fh:
+        fh.readline()
+        seq = "".join(line.strip() for line in fh)
+    fm = json.load(open(os.path.join(G.GOLDEN, "small_data-FM.json")))
+    ix = pkg.GenieIndex.build(G.str_to_codes(seq), 6)
+    assert ix.suffix_array().tolist() == fm["suffix_array"]
+    z = np.load(os.path.join(G.GOLDEN, "medium_data_checked_in.npz"), allow_pickle=False)
+    ix = pkg.GenieIndex.build(z["ref_codes"], 6)
+    assert ix.suffix_array().tolist() == z["fm_suffix_array"].tolist()
+    assert int(z["lut_size"]) == 6
+    off, pos = z["lut_pos_off"], z["lut_pos"]
+    want = {str(int(c)): [[int(a), int(b)], pos[off[i]:off[i + 1]].tolist()]
+            for i, (c, (a, b)) in enumerate(zip(z["lut_codes"], z["lut_interval"]))}
     codes, lo, hi = ix.lut_arrays()
     sa = ix.suffix_array()
     got = {str(int(c)): [[int(a), int(b)], sa[a:b + 1].tolist()] for c, a, b in zip(codes, lo, hi)}
-    assert got == lut["lut"]
+    assert got == want
 
 
 # ------------------------------------------------------------------ image + prefix directory
