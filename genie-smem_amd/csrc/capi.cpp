@@ -39,6 +39,20 @@ int make_index(const uint8_t *codes, int64_t n, const int32_t *sa1, int32_t K, i
     return GENIE_OK;
 }
 
+// genie_index_create_ex's parameter rules; P, P2 and the table form of a build with these arguments
+int device_params(int64_t n, int32_t K, int32_t dir_bits, int32_t table_bits, int32_t *P, int32_t *P2, bool *compact)
+{
+    *P = (dir_bits <= 0 || dir_bits > GENIE_MAX_DIR_BITS) ? GENIE_MAX_DIR_BITS : dir_bits;
+    const int32_t fmt = table_bits >> 8;
+    table_bits &= 0xFF;
+    if (fmt < 0 || fmt > 2) return GENIE_E_INVALID;
+    if (table_bits != 0 && (table_bits <= *P || table_bits > 12)) return GENIE_E_INVALID;
+    if (n < 1 || n > 0x7ffffff0ll || K < 0 || K > GENIE_MAX_K) return GENIE_E_INVALID;
+    if (fmt == 2 && n >= kM16MaxN) return GENIE_E_INVALID;
+    *P2 = choose_p2(n, *P, table_bits);
+    *compact = fmt == 2 || (fmt == 0 && n < kM16MaxN);
+    return GENIE_OK;
+}
 }  // namespace
 
 static int ready(const genie_index *ix);
@@ -236,6 +250,49 @@ int genie_index_to_device(genie_index *ix, int32_t device)
     }
     free(host);
     return rc;
+}
+
+
+int64_t genie_index_device_image_bound(int64_t n, int32_t K, int32_t dir_bits, int32_t table_bits)
+{
+    int32_t P, P2;
+    bool compact;
+    const int rc = device_params(n, K, dir_bits, table_bits, &P, &P2, &compact);
+    return rc ? (int64_t)rc : device_image_bound(n, K, P, P2, compact);
+}
+
+int64_t genie_index_device_build_tmp_bytes(int64_t n, int32_t K, int32_t dir_bits, int32_t table_bits)
+{
+    int32_t P, P2;
+    bool compact;
+    const int rc = device_params(n, K, dir_bits, table_bits, &P, &P2, &compact);
+    return rc ? (int64_t)rc : device_build_tmp_bytes(n, K, P, P2);
+}
+
+int genie_index_create_device(const uint8_t *d_codes, int64_t n, int32_t K, int32_t dir_bits, int32_t table_bits,
+                              int32_t image_flags, void *d_image, int64_t image_cap, int64_t *image_bytes, void *d_tmp,
+                              int64_t tmp_bytes, int32_t device, void *stream, genie_index **out)
+{
+    if (!d_codes || !d_image || !image_bytes || !d_tmp || !out) return GENIE_E_INVALID;
+    if (image_flags & ~GENIE_IMAGE_NO_SEED_TABLE) return GENIE_E_INVALID;
+    if ((reinterpret_cast<uintptr_t>(d_image) & 255) != 0 || (reinterpret_cast<uintptr_t>(d_tmp) & 255) != 0) return GENIE_E_INVALID;
+    int32_t P, P2;
+    bool compact;
+    int rc = device_params(n, K, dir_bits, table_bits, &P, &P2, &compact);
+    if (rc) return rc;
+    if (image_cap < device_image_bound(n, K, P, P2, compact) || tmp_bytes < device_build_tmp_bytes(n, K, P, P2))
+        return GENIE_E_INVALID;
+    rc = check_hip(hipSetDevice(device), "hipSetDevice");
+    if (rc) return rc;
+    BlobHeader hdr;
+    rc = device_build(d_codes, n, K, P, P2, compact, image_flags, d_image, image_cap, d_tmp, tmp_bytes, stream, &hdr);
+    if (rc) return rc;
+    genie_index *ix = nullptr;
+    rc = genie_index_open(&hdr, d_image, hdr.total_bytes, device, &ix);
+    if (rc) return rc;
+    *image_bytes = hdr.total_bytes;
+    *out = ix;
+    return GENIE_OK;
 }
 
 void genie_index_destroy(genie_index *ix)

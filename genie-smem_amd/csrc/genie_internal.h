@@ -9,6 +9,9 @@
 
 #ifndef __HIPCC__
 struct uint2 { unsigned int x, y; };
+#define GENIE_HD
+#else
+#define GENIE_HD __host__ __device__
 #endif
 
 namespace genie {
@@ -205,7 +208,7 @@ struct DevIndex {
     int32_t P2;
 };
 
-inline uint32_t lut_hash(uint32_t code, uint32_t slots)
+GENIE_HD inline uint32_t lut_hash(uint32_t code, uint32_t slots)
 {
     return (uint32_t)(((uint64_t)(code * 0x9E3779B1u) * (uint64_t)slots) >> 32);
 }
@@ -236,6 +239,88 @@ struct HostIndex {
     std::vector<RmiModel> rmi;
     std::vector<int32_t> rmi_err;        // per leaf model (native training only)
 };
+
+// Everything the image layout depends on: the section sizes and the header scalars.  The host builder (fill_header) and
+// the device builder (index_build.hip, on the device) both lay out the header with layout_header below.
+struct ImageShape {
+    int64_t n;
+    int32_t K, P, P2, flags;                     // flags: kFlagDir16 | kFlagCompactTable (no image flags)
+    int64_t sa_rows, ref_recs, dir_entries, dir2_entries;
+    int64_t lut_slots, lut_keys;                 // lut_slots of the full seed table
+    int64_t rmi_models, rmi_err_entries;
+    int32_t nlev;
+    int32_t rmi_size[GENIE_MAX_RMI_LEVELS];
+    int32_t rmi_scale[GENIE_MAX_RMI_LEVELS];
+    int32_t rmi_off[GENIE_MAX_RMI_LEVELS + 1];
+    uint32_t padtail[8];
+    int64_t mtab_entries;                        // MatchRec16 entries when flags & kFlagCompactTable, else MatchRec
+    int64_t ov_entries;
+};
+
+GENIE_HD inline int64_t align_section(int64_t x) { return (x + kSectionAlign - 1) / kSectionAlign * kSectionAlign; }
+
+// image_flags: GENIE_IMAGE_* (genie_smem.h).  Sections follow the header in this order, each 256-byte aligned; an empty
+// RMI / range / error / overflow section still takes one element.
+GENIE_HD inline void layout_header(const ImageShape &s, BlobHeader *hdr, int32_t image_flags)
+{
+    const bool no_seed = (image_flags & GENIE_IMAGE_NO_SEED_TABLE) != 0;
+    unsigned char *z = reinterpret_cast<unsigned char *>(hdr);
+    for (size_t i = 0; i < sizeof(*hdr); i++) z[i] = 0;
+    hdr->magic = kMagic;
+    hdr->version = kBlobVersion;
+    hdr->header_bytes = GENIE_HEADER_BYTES;
+    hdr->n = s.n;
+    hdr->K = s.K;
+    hdr->P = s.P;
+    hdr->ref_recs = s.ref_recs;
+    hdr->dir_entries = s.dir_entries;
+    hdr->lut_slots = no_seed ? 8 : s.lut_slots;
+    hdr->lut_keys = s.lut_keys;
+    hdr->rmi_models = s.rmi_models;
+    hdr->P2 = s.P2;
+    hdr->flags = s.flags | (no_seed ? kFlagNoSeedTable : 0);
+    hdr->dir2_entries = s.dir2_entries;
+    hdr->nlev = s.nlev;
+    for (int l = 0; l < GENIE_MAX_RMI_LEVELS; l++) {
+        hdr->rmi_size[l] = s.rmi_size[l];
+        hdr->rmi_scale[l] = s.rmi_scale[l];
+    }
+    for (int l = 0; l <= GENIE_MAX_RMI_LEVELS; l++) hdr->rmi_off[l] = s.rmi_off[l];
+    for (int l = 0; l < 8; l++) hdr->padtail[l] = s.padtail[l];
+    int64_t off = GENIE_HEADER_BYTES;
+    hdr->off_sa = off;
+    off = align_section(off + s.sa_rows * (int64_t)sizeof(SaRec));
+    hdr->off_ref = off;
+    off = align_section(off + s.ref_recs * (int64_t)sizeof(RefRec));
+    hdr->off_dir = off;
+    off = align_section(off + s.dir_entries * 4);
+    hdr->off_lut = off;
+    off = align_section(off + hdr->lut_slots * (int64_t)sizeof(LutSlot));
+    hdr->off_rmi = off;
+    off = align_section(off + (s.rmi_models > 1 ? s.rmi_models : 1) * (int64_t)sizeof(RmiModel));
+    hdr->off_dir2 = off;
+    off = align_section(off + (s.dir2_entries > 1 ? s.dir2_entries : 1) * (int64_t)sizeof(HeadRec));
+    hdr->off_rmi_err = off;
+    hdr->rmi_err_entries = s.rmi_err_entries;
+    off = align_section(off + (s.rmi_err_entries > 1 ? s.rmi_err_entries : 1) * 4);
+    hdr->off_mtab = off;
+    const bool compact = (s.flags & kFlagCompactTable) != 0;
+    hdr->mtab_entries = s.mtab_entries;
+    off = align_section(off + s.mtab_entries * (int64_t)(compact ? sizeof(MatchRec16) : sizeof(MatchRec)));
+    hdr->off_ov = off;
+    hdr->ov_entries = s.ov_entries;
+    off = align_section(off + (s.ov_entries > 1 ? s.ov_entries : 1) * (int64_t)sizeof(MatchOv16));
+    hdr->total_bytes = off;
+}
+
+// P2 of the per-P2-mer tables (build_host_index): the smallest > P with 4^P2 >= n/4, or the caller's table_bits
+inline int32_t choose_p2(int64_t n, int32_t P, int32_t dir2_bits)
+{
+    int32_t P2 = P + 1;
+    while (P2 < 12 && ((int64_t)1 << (2 * P2)) < n / 4) P2++;
+    if (dir2_bits > P && dir2_bits <= 12) P2 = dir2_bits;
+    return P2;
+}
 
 // table_format: 0 = automatic (compact when n < kM16MaxN), 1 = 32-byte entries,
 // 2 = compact entries
@@ -298,6 +383,11 @@ int find_smems_geometry(const genie_index *ix, int32_t mode, int32_t max_len, in
 void find_smems_workspace_rows(int32_t max_len, int32_t out[4]);
 int search_kernel_name(const genie_index *ix, int32_t mode, int32_t max_len, char *buf, int32_t cap);
 int validate_image(const genie_index *ix, unsigned int *what, void *stream);
+// index_build.hip
+int64_t device_image_bound(int64_t n, int32_t K, int32_t P, int32_t P2, bool compact);
+int64_t device_build_tmp_bytes(int64_t n, int32_t K, int32_t P, int32_t P2);
+int device_build(const uint8_t *d_codes, int64_t n, int32_t K, int32_t P, int32_t P2, bool compact, int32_t image_flags,
+                 void *d_image, int64_t image_cap, void *d_tmp, int64_t tmp_bytes, void *stream, BlobHeader *hdr_out);
 void set_hip_error(const char *what, int code);
 const char *last_hip_error();
 }  // namespace genie

@@ -179,9 +179,7 @@ int build_host_index(const uint8_t *codes, int64_t n, const int32_t *sa_one_base
         // of (up to kMatchKeys of) its suffixes, in ONE 32-byte entry -- what the match-statistics kernel
         // reads instead of searching rows.
         {
-            int P2 = P + 1;
-            while (P2 < 12 && ((int64_t)1 << (2 * P2)) < n / 4) P2++;
-            if (dir2_bits > P && dir2_bits <= 12) P2 = dir2_bits;       // build-time tuning (genie_index_create_ex)
+            const int P2 = choose_p2(n, P, dir2_bits);                  // dir2_bits: build-time tuning (genie_index_create_ex)
             h->P2 = P2;
             const int64_t nb2 = (int64_t)1 << (2 * P2);
             // table form: the compact entries (genie_internal.h) wherever a row number fits their 24 bits -- they halve the
@@ -379,57 +377,32 @@ int build_host_index(const uint8_t *codes, int64_t n, const int32_t *sa_one_base
     return GENIE_OK;
 }
 
-static int64_t align_up(int64_t x) { return (x + kSectionAlign - 1) / kSectionAlign * kSectionAlign; }
-
 void fill_header(const HostIndex &h, BlobHeader *hdr, int32_t image_flags)
 {
-    const bool no_seed = (image_flags & GENIE_IMAGE_NO_SEED_TABLE) != 0;
-    memset(hdr, 0, sizeof(*hdr));
-    hdr->magic = kMagic;
-    hdr->version = kBlobVersion;
-    hdr->header_bytes = GENIE_HEADER_BYTES;
-    hdr->n = h.n;
-    hdr->K = h.K;
-    hdr->P = h.P;
-    hdr->ref_recs = (int64_t)h.ref.size();
-    hdr->dir_entries = (int64_t)h.dir.size();
-    hdr->lut_slots = no_seed ? 8 : (int64_t)h.lut_slots.size();
-    hdr->lut_keys = (int64_t)h.lut_code.size();
-    hdr->rmi_models = (int64_t)h.rmi.size();
-    hdr->P2 = h.P2;
-    hdr->flags = h.flags | (no_seed ? kFlagNoSeedTable : 0);
-    hdr->dir2_entries = (int64_t)h.dir2.size();
-    hdr->nlev = h.nlev;
+    ImageShape s;
+    s.n = h.n;
+    s.K = h.K;
+    s.P = h.P;
+    s.P2 = h.P2;
+    s.flags = h.flags;
+    s.sa_rows = (int64_t)h.sarec.size();
+    s.ref_recs = (int64_t)h.ref.size();
+    s.dir_entries = (int64_t)h.dir.size();
+    s.dir2_entries = (int64_t)h.dir2.size();
+    s.lut_slots = (int64_t)h.lut_slots.size();
+    s.lut_keys = (int64_t)h.lut_code.size();
+    s.rmi_models = (int64_t)h.rmi.size();
+    s.rmi_err_entries = (int64_t)h.rmi_err.size();
+    s.nlev = h.nlev;
     for (int l = 0; l < GENIE_MAX_RMI_LEVELS; l++) {
-        hdr->rmi_size[l] = h.rmi_size[l];
-        hdr->rmi_scale[l] = h.rmi_scale[l];
+        s.rmi_size[l] = h.rmi_size[l];
+        s.rmi_scale[l] = h.rmi_scale[l];
     }
-    for (int l = 0; l <= GENIE_MAX_RMI_LEVELS; l++) hdr->rmi_off[l] = h.rmi_off[l];
-    for (int l = 0; l < 8; l++) hdr->padtail[l] = h.padtail[l];
-    int64_t off = GENIE_HEADER_BYTES;
-    hdr->off_sa = off;
-    off = align_up(off + (int64_t)h.sarec.size() * (int64_t)sizeof(SaRec));
-    hdr->off_ref = off;
-    off = align_up(off + (int64_t)h.ref.size() * (int64_t)sizeof(RefRec));
-    hdr->off_dir = off;
-    off = align_up(off + (int64_t)h.dir.size() * 4);
-    hdr->off_lut = off;
-    off = align_up(off + hdr->lut_slots * (int64_t)sizeof(LutSlot));
-    hdr->off_rmi = off;
-    off = align_up(off + (int64_t)std::max<size_t>(h.rmi.size(), 1) * (int64_t)sizeof(RmiModel));
-    hdr->off_dir2 = off;
-    off = align_up(off + (int64_t)std::max<size_t>(h.dir2.size(), 1) * (int64_t)sizeof(HeadRec));
-    hdr->off_rmi_err = off;
-    hdr->rmi_err_entries = (int64_t)h.rmi_err.size();
-    off = align_up(off + (int64_t)std::max<size_t>(h.rmi_err.size(), 1) * 4);
-    hdr->off_mtab = off;
-    const bool compact = (h.flags & kFlagCompactTable) != 0;
-    hdr->mtab_entries = compact ? (int64_t)h.mtab16.size() : (int64_t)h.mtab.size();
-    off = align_up(off + (compact ? (int64_t)h.mtab16.size() * (int64_t)sizeof(MatchRec16) : (int64_t)h.mtab.size() * (int64_t)sizeof(MatchRec)));
-    hdr->off_ov = off;
-    hdr->ov_entries = (int64_t)h.ov.size();
-    off = align_up(off + (int64_t)std::max<size_t>(h.ov.size(), 1) * (int64_t)sizeof(MatchOv16));
-    hdr->total_bytes = off;
+    for (int l = 0; l <= GENIE_MAX_RMI_LEVELS; l++) s.rmi_off[l] = h.rmi_off[l];
+    for (int l = 0; l < 8; l++) s.padtail[l] = h.padtail[l];
+    s.mtab_entries = (h.flags & kFlagCompactTable) ? (int64_t)h.mtab16.size() : (int64_t)h.mtab.size();
+    s.ov_entries = (int64_t)h.ov.size();
+    layout_header(s, hdr, image_flags);
 }
 
 // ------------------------------------------------------------------ native RMI training

@@ -59,6 +59,43 @@ class GenieIndex:
         N.check(rc, "genie_index_create")
         return self
 
+    @classmethod
+    def build_on_device(cls, codes, K, dir_bits=7, table_bits=0, table_format="auto", seed_table=True, device="cuda"):
+        """Build the index image on the GPU (genie_index_create_device): the same image bytes as
+        build(...).serialize(seed_table), written straight into device memory and bound like to() does.
+        codes: numpy array or torch tensor of base codes 0..3 (uploaded if it is on the host).  The handle is
+        device-only: no host arrays and no RMI model (RMI mode gives GENIE_E_NO_MODEL)."""
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("GenieIndex.build_on_device: an MI355X device is required (no CPU fallback)")
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if not isinstance(codes, torch.Tensor):
+            codes = torch.as_tensor(np.ascontiguousarray(codes, np.uint8))
+        codes = codes.to(device=device, dtype=torch.uint8).contiguous().view(-1)
+        n = codes.numel()
+        tb = int(table_bits) | {"auto": 0, "wide": N.TABLE_WIDE, "compact": N.TABLE_COMPACT}[table_format]
+        L = N.lib()
+        cap = int(L.genie_index_device_image_bound(n, int(K), int(dir_bits), tb))
+        tmp_bytes = int(L.genie_index_device_build_tmp_bytes(n, int(K), int(dir_bits), tb))
+        if cap < 0 or tmp_bytes < 0:
+            raise N.GenieError(min(cap, tmp_bytes), "genie_index_device_image_bound")
+        image = torch.empty(cap, dtype=torch.uint8, device=device)     # torch allocations are 512-byte aligned
+        tmp = torch.empty(tmp_bytes, dtype=torch.uint8, device=device)
+        nbytes = C.c_int64(0)
+        self = cls()
+        with torch.cuda.device(device):
+            rc = L.genie_index_create_device(_ptr(codes), n, int(K), int(dir_bits), tb,
+                                             0 if seed_table else N.IMAGE_NO_SEED_TABLE, _ptr(image), cap, C.byref(nbytes),
+                                             _ptr(tmp), tmp_bytes, device.index, _stream(device), C.byref(self._h))
+        N.check(rc, "genie_index_create_device")
+        del tmp
+        # keep only the image itself (a copy, so the bound-sized buffer is released), then bind it as to() does
+        blob = image[:nbytes.value].clone()
+        del image
+        self._bind(blob, blob[:N.HEADER_BYTES].cpu())
+        return self
+
     def set_rmi(self, experts, coefs, icpts):
         """experts: the reference's list (RMI.experts); coefs/icpts: per-level float64 arrays."""
         sizes = np.asarray([len(c) for c in coefs], np.int32)

@@ -166,6 +166,34 @@ int genie_index_open(const void *host_header, const void *d_blob, int64_t blob_b
  * 64 RMI error bounds).  The drop-in calls it on every image it opens, also on one received by broadcast. */
 int genie_index_validate(const genie_index *ix, uint32_t *what, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Index construction on the device: genie_index_create_ex + genie_index_serialize_image + genie_index_open in one call,
+ * for a reference that is already in device memory.  The image bytes are the ones the host path writes (the host builder
+ * stays the specification; the tests compare the two byte for byte).
+ *   d_codes     n base codes (0..3) in device memory;
+ *   K, dir_bits, table_bits   as genie_index_create_ex (table_bits may carry GENIE_TABLE_WIDE / GENIE_TABLE_COMPACT);
+ *   image_flags GENIE_IMAGE_NO_SEED_TABLE or 0, as genie_index_serialize_image;
+ *   d_image     caller-owned, 256-byte aligned, image_cap >= genie_index_device_image_bound(...) bytes; *image_bytes gets
+ *               the size of the image written at its front (the rest of the buffer is unused);
+ *   d_tmp       caller-owned, 256-byte aligned scratch of genie_index_device_build_tmp_bytes(...) bytes: about 14 four-byte
+ *               words per base (suffix-array sort buffers, neighbour LCPs, the K-mer list and hash-table placement) plus
+ *               about 4.2 words per P2-mer (per-prefix row tables);
+ *   device, stream  the HIP device (made current) and stream of every launch; the call synchronizes `stream` once, at the
+ *               end (the header has to reach the host).
+ * Errors as genie_index_create_ex: GENIE_E_ALPHABET for a code > 3 (found on the device, reported after the build),
+ * GENIE_E_INVALID for n, K, table_bits or image_flags out of range, a null or misaligned pointer, or image_cap / tmp_bytes
+ * too small -- all checked before any device work.
+ * The returned handle is device-only, like one from genie_index_open on a received image: no host arrays
+ * (genie_index_suffix_array / genie_index_lut_arrays give NULL / GENIE_E_INVALID, genie_index_serialize* GENIE_E_INVALID),
+ * no RMI model (GENIE_MODE_RMI gives GENIE_E_NO_MODEL; genie_index_set_rmi / genie_index_train_rmi refuse it with
+ * GENIE_E_INVALID).  The image must outlive the handle; it can be broadcast and opened elsewhere like any other.
+ * The bound and scratch functions return GENIE_E_INVALID (negative) for arguments create_device would refuse. */
+int64_t genie_index_device_image_bound(int64_t n, int32_t K, int32_t dir_bits, int32_t table_bits);
+int64_t genie_index_device_build_tmp_bytes(int64_t n, int32_t K, int32_t dir_bits, int32_t table_bits);
+int genie_index_create_device(const uint8_t *d_codes, int64_t n, int32_t K, int32_t dir_bits, int32_t table_bits,
+                              int32_t image_flags, void *d_image, int64_t image_cap, int64_t *image_bytes, void *d_tmp,
+                              int64_t tmp_bytes, int32_t device, void *stream, genie_index **out);
+
 /* Convenience for non-torch callers: hipMalloc + upload an image owned by the handle. */
 int genie_index_to_device(genie_index *ix, int32_t device);
 
