@@ -1266,4 +1266,7 @@ int launch_locate(const genie_index *ix, const int32_t *d_lohi, int32_t stride, 
     return GENIE_OK;
 }
 
+// genie_find_smems_split: segments of reads with breaks through the pipeline above
+#include "split_reads.inc"
+
 }  // namespace genie

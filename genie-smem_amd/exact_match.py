@@ -77,6 +77,15 @@ class ExactMatch:
                     raise KeyError(ch)
         return codes
 
+    def encode_lenient(self, seq: str):
+        """Symbols -> codes, with every symbol outside the reference's alphabet (N, n, IUPAC codes, anything else) mapped to
+        code 4: a break for find_smems_split.  A symbol of the alphabet that never occurs in the reference keeps its code;
+        the device treats it as a break as well."""
+        if self._codes is None:
+            self.load_ref_sequence()
+        codes = self._enc[np.frombuffer(seq.encode("latin-1", "replace"), np.uint8)]
+        return np.where(codes == 255, np.uint8(4), codes).astype(np.uint8)
+
     def decode(self, codes):
         return "".join(self.alphabet[int(c)] for c in codes)
 

@@ -84,6 +84,26 @@ class SMEM:
     def find_smems_bwa(self, reads, minimum_length=1, lens=None):
         return self._find("bwa", reads, lens, minimum_length)
 
+    def find_smems_split(self, reads, minimum_length=1, lens=None):
+        """get_SMEMS over reads that may hold ambiguous bases (N): every symbol outside the reference's alphabet, and every
+        base the reference lacks, is a break, and a read's SMEMs are those of the runs between its breaks (start / end in
+        the whole read).  reads: list[str] (encoded with ExactMatch.encode_lenient), or numpy / torch uint8 codes (any code
+        > 3 is a break).  Host inputs travel as uint8 codes (the 2-bit packed host path cannot carry a break); results come
+        back on the device.  -> (offsets, smems[S, 4], status) like find_smems_bwa."""
+        ix = self.matcher.index(self.lut.lut_size)
+        if isinstance(reads, (torch.Tensor, np.ndarray)):
+            return ix.find_smems_split(reads, lens, minimum_length)
+        enc = [self.matcher.encode_lenient(r) for r in reads]
+        ln = np.asarray([len(e) for e in enc], np.int32)
+        width = int(ln.max()) if len(enc) else 0
+        mat = np.zeros((len(enc), max(width, 1)), np.uint8)
+        for i, e in enumerate(enc):
+            mat[i, :len(e)] = e
+        ragged = len(enc) > 0 and int(ln.min()) != width
+        if lens is None and ragged:
+            lens = ln
+        return ix.find_smems_split(mat if width else mat[:, :0], lens, minimum_length)
+
     def find_smems_lut(self, reads, lens=None):
         return self._find("lut", reads, lens, 1)
 

@@ -251,6 +251,27 @@ int genie_find_smems_csr(const genie_index *ix, int32_t mode, const uint8_t *d_r
                          int32_t *d_rows, int64_t out_cap_rows, int32_t *d_status, void *d_workspace,
                          int64_t workspace_bytes, void *stream);
 
+/* SMEMs of reads that contain breaks (ambiguous bases such as N), where genie_find_smems* flag the whole read instead.
+ * A break is a position whose code is > 3 (any byte 4..255) or whose base never occurs in the reference; a segment is a
+ * maximal run of positions that are not breaks.  No exact match covers a break, so the SMEMs of a read are the union of
+ * its segments' SMEMs: segments in read order, each with SMEM.get_SMEMS's emission order and min_len filter (the BWA
+ * traversal; a segment shorter than K is searched like any other), start / end positions in the whole read, lo / hi
+ * unchanged.  Inputs and outputs as genie_find_smems_csr (there is no mode argument): d_offsets[N+1], int32 rows
+ * (start, end, lo, hi), rows beyond out_cap_rows dropped with d_offsets[N] still the true total.  d_lens may be NULL;
+ * with d_lens, fixed_len is the longest length and every d_lens[r] must lie in [0, fixed_len] (GENIE_E_INVALID,
+ * found on the device, otherwise).  d_status[r] (may be NULL) = GENIE_READ_OK: a read of length 0 or made only of
+ * breaks has no rows.
+ * d_workspace: 256-byte aligned, genie_find_smems_split_workspace_bytes(N, max_len) bytes with max_len >= fixed_len
+ * (GENIE_E_CAPACITY when smaller).  Argument checks come before the device check, so they hold on any handle.
+ * Unlike the other hot-path calls this one synchronizes `stream`: once to learn whether any read has a break or is
+ * empty (when none has, the reads go through the genie_find_smems_csr pipeline unchanged, byte for byte the same output);
+ * otherwise once more for the segment totals, and once per extra pass when the segments outnumber what the workspace
+ * holds (passes of at least N segments). */
+int64_t genie_find_smems_split_workspace_bytes(int64_t N, int32_t max_len);
+int genie_find_smems_split(const genie_index *ix, const uint8_t *d_reads, const int32_t *d_lens, int64_t N, int32_t stride,
+                           int32_t fixed_len, int32_t min_len, int64_t *d_offsets, int32_t *d_rows, int64_t out_cap_rows,
+                           int32_t *d_status, void *d_workspace, int64_t workspace_bytes, void *stream);
+
 /* The same discovery for callers on the far side of a host link (SMEM.find_smems_* on host arrays): 2-bit packed reads in,
  * 8-byte rows out -- 40 instead of 150 bytes per 150-base read over PCIe, 8 instead of 16 per SMEM.  Reads of at most 255
  * bases.  Row r of d_reads2bit = stride_bytes bytes (a multiple of 4, >= 4 * ceil(max length / 16)): byte i holds bases
