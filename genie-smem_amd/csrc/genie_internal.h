@@ -371,6 +371,10 @@ int64_t find_smems_split_workspace_bytes(int64_t N, int32_t max_len);
 int launch_find_smems_split(const genie_index *ix, const uint8_t *d_reads, const int32_t *d_lens, int64_t N, int32_t stride,
                             int32_t fixed_len, int32_t min_len, int64_t *d_offsets, int32_t *d_rows, int64_t out_cap_rows,
                             int32_t *d_status, void *d_ws, int64_t ws_bytes, void *stream);
+int64_t find_smems_long_workspace_bytes(int64_t N, int64_t total_bases);
+int launch_find_smems_long(const genie_index *ix, int32_t mode, const uint8_t *d_bases, const int64_t *d_read_offsets, int64_t N,
+                           int64_t total_bases, int64_t max_len, int32_t min_len, int64_t *d_offsets, int32_t *d_rows,
+                           int64_t out_cap_rows, int32_t *d_status, void *d_ws, int64_t ws_bytes, void *stream);
 int launch_find_smems_packed(const genie_index *ix, int32_t mode, const uint8_t *d_reads2, const int32_t *d_lens, int64_t N,
                              int32_t stride_bytes, int32_t fixed_len, int32_t min_len, uint8_t *d_counts8, uint8_t *d_status8,
                              void *d_rows8, int64_t out_cap_rows, int64_t *d_totals, int64_t *d_escapes, int64_t cap_escapes,

@@ -1,0 +1,423 @@
+// long_reads.inc -- genie_find_smems_long: SMEMs of reads of any length, given as CSR (included by kernels.hip, inside
+// namespace genie; uses its launch plumbing and the match-statistics helpers of match_table_kernel.inc).
+//
+// The fixed-stride pipeline keeps a whole read in LDS and its positions in 16 bits.  Here nothing is per read except one
+// short serial pass: every stage is cut into WINDOWS of kLrWin positions (read-relative: window w of a read holds its
+// positions [w kLrWin, (w + 1) kLrWin)), handed out across all reads of the batch, so ten 10^6-base reads fill the chip
+// as well as 10^6 short ones.  Positions are 32-bit.
+//   LR0 lr_check_kernel   offsets non-decreasing, inside [0, total_bases], no read above max_len; the host reads the flag
+//                         (the one synchronisation of the call).  Too short for K in LUT / RMI mode: the read's status.
+//   LR1 lr_pack_kernel    one thread per 64-bit word of the packed stream (32 bases, plain big-endian words as QPlain
+//                         reads them); read r owns the words [Wd(r), Wd(r+1)), Wd(r) = off[r] / 32 + 3r, which leaves at
+//                         least two zero words behind every read (the padding every 32-base window relies on).  Bad base:
+//                         the read's status.
+//   LR2 lr_fwd_kernel     one wave per window: matching statistics fwd[a] (end of the longest match at a, 32-bit) from
+//                         one match-table lookup per position (mt_issue / mt_eval, as round 1 of K_A); positions the entry
+//                         cannot decide go to the slow list (mt_slow, the same code as K_A's), which compares the read with
+//                         the reference for as long as they agree -- past the window, to the end of the read.  Also:
+//                         the window's maximum of fwd[a] - a (first position on ties), the mark "some position's match
+//                         ends here" at fwd[a], and the absent-base flag (fwd[a] = a).
+//   LR3 lr_walk_kernel    one block per window, its fwd and the previous window's in LDS.  The traversal step of K_B depends only on the current end i: the
+//                         candidates are the positions b <= i with fwd[b] > i, a range [lo(i), i] (fwd[] is
+//                         non-decreasing), the winner b* the first maximum of fwd[b] - b, the next end fwd[b*].  Only
+//                         0 and the values of fwd[] can be ends, so only marked positions take the step: a scan down from i
+//                         that takes whole windows from their maxima (LR2) where fwd at the window's first position still
+//                         covers i.  Then pointer jumping in LDS (log2 kLrWin rounds) gives, for every marked position e,
+//                         the first end at or behind the window's end reached from e and the rows emitted on the way.
+//   LR4 lr_chain_kernel   one thread per read: the chain from 0, one step per window it enters (not per SMEM).  Writes the
+//                         window's entry end and the rows emitted before it in the read; the read's row count.
+//   scan                  compact_block_sums + scan_block_sums_kernel + lr_offsets_kernel: d_offsets.
+//   LR5 lr_emit_kernel    one thread per window the chain enters: its SMEMs in order, the SA interval of each from
+//                         sa_interval over the packed read (any length), each row written once, non-temporal.
+namespace {
+
+constexpr int kLrWin = 256;               // positions per window (a multiple of 64: one per lane of LR3's block)
+constexpr int kLrWinShift = 8;
+constexpr int kLrFwdWaves = 4;            // windows per LR2 block
+static_assert((1 << kLrWinShift) == kLrWin, "window shift");
+
+__device__ __forceinline__ long long lr_wd(const long long *off, long long r) { return off[r] / 32 + 3 * r; }          // first packed word
+__device__ __forceinline__ long long lr_wb(const long long *off, long long r) { return off[r] / kLrWin + r; }      // first window
+
+// The read r in [0, N) with key(r) <= g < key(r + 1) (key non-decreasing; r = 0 when g < key(0)).
+template <class F>
+__device__ __forceinline__ long long lr_find(long long N, long long g, F key)
+{
+    long long lo = 0, hi = N - 1;
+    while (lo < hi) {
+        const long long mid = (lo + hi + 1) >> 1;
+        if (key(mid) <= g) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+__device__ __forceinline__ unsigned long long lr_shfl_xor64(unsigned long long v, int m)
+{
+    const unsigned int lo = (unsigned)__shfl_xor((int)(unsigned)v, m, kWave);
+    const unsigned int hi = (unsigned)__shfl_xor((int)(unsigned)(v >> 32), m, kWave);
+    return ((unsigned long long)hi << 32) | lo;
+}
+
+// also the status of every read: 0, or GENIE_READ_TOO_SHORT (LUT / RMI mode, fewer than K bases -- empty reads too, as in
+// K_A); LR1 overwrites it with GENIE_READ_BAD_BASE, which takes precedence
+__global__ void __launch_bounds__(256) lr_check_kernel(const long long *__restrict__ off, long long N, long long total,
+                                                       long long max_len, int mode, int K, int *__restrict__ flag,
+                                                       int32_t *__restrict__ st)
+{
+    const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r > N) return;
+    const long long o = off[r];
+    bool bad = o < 0 || o > total;
+    if (r < N) {
+        const long long o2 = off[r + 1];
+        bad = bad || o2 < o || o2 - o > max_len;
+        st[r] = (mode != GENIE_MODE_BWA && o2 - o < K) ? GENIE_READ_TOO_SHORT : GENIE_READ_OK;
+    }
+    if (bad) atomicOr(flag, 1);
+}
+
+__global__ void __launch_bounds__(256) lr_pack_kernel(const uint8_t *__restrict__ bases, const long long *__restrict__ off, long long N,
+                                                      long long nwords, uint64_t *__restrict__ packed, int32_t *__restrict__ st)
+{
+    const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= nwords) return;
+    const long long r = lr_find(N, g, [&](long long x) { return lr_wd(off, x); });
+    const long long k = g - lr_wd(off, r);
+    const long long o = off[r], L = off[r + 1] - o;
+    uint64_t w = 0;
+    if (k >= 0 && 32 * k < L) {
+        const uint8_t *src = bases + o + 32 * k;
+        const int cnt = L - 32 * k < 32 ? (int)(L - 32 * k) : 32;
+        uint32_t bad = 0;
+        for (int j = 0; j < cnt; j++) {
+            const uint32_t c = src[j];
+            bad |= c;
+            w |= (uint64_t)(c & 3u) << (62 - 2 * j);
+        }
+        if (bad > 3u) st[r] = GENIE_READ_BAD_BASE;            // every writer stores the same value
+    }
+    packed[g] = w;
+}
+
+template <bool C16>
+__global__ void __launch_bounds__(kLrFwdWaves * 64) lr_fwd_kernel(DevIndex ix, int mode, const long long *__restrict__ off, long long N,
+                                                                  long long nwin, const uint64_t *__restrict__ packed,
+                                                                  int32_t *__restrict__ st, int32_t *__restrict__ fwd,
+                                                                  int2 *__restrict__ wmax, uint8_t *__restrict__ mark,
+                                                                  long long mtab_bytes)
+{
+    __shared__ uint16_t lists[kLrFwdWaves][kLrWin];
+    __shared__ int32_t rows[kLrFwdWaves][kLrWin];
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = rfl((int)(threadIdx.x >> 6));
+    const long long gw = (long long)blockIdx.x * kLrFwdWaves + wave;
+    if (gw >= nwin) return;                                      // wave-uniform; no block-wide barrier below
+    const long long r = lr_find(N, gw, [&](long long x) { return lr_wb(off, x); });
+    const long long w = gw - lr_wb(off, r);
+    const long long o = off[r], Ll = off[r + 1] - o;
+    if (w < 0 || w * kLrWin >= Ll) return;                     // a window past the read's end (at most one per read)
+    const int L = (int)Ll, w0 = (int)(w * kLrWin);
+    if (st[r] != GENIE_READ_OK) return;                         // bad base or too short (LR0 / LR1)
+    const __amdgpu_buffer_rsrc_t mtab =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<MatchRec *>(ix.mtab), 0, (int)mtab_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ov =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<MatchOv16 *>(ix.ov), 0, ix.ov_entries * (int)sizeof(MatchOv16), 0x00020000);
+    const uint64_t *q = packed + lr_wd(off, r);
+    const QPlain Q{q};
+    uint16_t *sl = lists[wave];
+    int32_t *fw = rows[wave];
+    const int nw = L - w0 < kLrWin ? L - w0 : kLrWin;
+    int nslow = 0;
+#pragma unroll
+    for (int k = 0; k < kLrWin / kWave; k++) {
+        const int t = k * kWave + lane, a = w0 + t;
+        bool slow = false;
+        if (t < nw) {
+            const uint64_t x = Q.win(a);
+            const MtProbe p = mt_issue<C16>(mtab, (uint32_t)(x >> 32), (uint32_t)x, ix.P2);
+            const mt_v4i rb = mt_second<C16>(mtab, p);
+            bool s;
+            const int b0 = mt_eval<C16>(p, rb, ix.P2, s);
+            const int m = L - a;
+            slow = s && m > b0;
+            fw[t] = a + (b0 < m ? b0 : m);
+        }
+        const uint64_t bal = __ballot(slow);
+        if (slow) sl[nslow + __popcll(bal & ((1ull << lane) - 1ull))] = (uint16_t)t;
+        nslow += __popcll(bal);
+    }
+    wave_lds_fence();
+    for (int c0 = 0; c0 < nslow; c0 += kWave)
+        mt_slow<true, C16, QPlain, int32_t>(ix, mtab, ov, mode, lane, c0, nslow, sl, reinterpret_cast<const uint32_t *>(q), 0, nullptr,
+                                            nullptr, 0, L, w0, fw);
+    wave_lds_fence();
+    unsigned long long best = 0;                                 // (fwd[a] - a) << 8 | 255 - (a - w0): the first maximum
+    bool absent = false;
+#pragma unroll
+    for (int k = 0; k < kLrWin / kWave; k++) {
+        const int t = k * kWave + lane, a = w0 + t;
+        if (t < nw) {
+            const int v = fw[t];
+            __builtin_nontemporal_store(v, fwd + o + a);
+            const unsigned long long key = ((unsigned long long)(uint32_t)(v - a) << kLrWinShift) | (unsigned)(kLrWin - 1 - t);
+            best = key > best ? key : best;
+            absent = absent || v == a;
+            if (v < L) mark[o + v] = 1;                          // every writer stores the same value
+        }
+    }
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) {
+        const unsigned long long x = lr_shfl_xor64(best, m);
+        best = x > best ? x : best;
+    }
+    const bool any_absent = __any(absent);
+    if (lane == 0) {
+        wmax[gw] = make_int2((int)(best >> kLrWinShift), w0 + kLrWin - 1 - (int)(best & (kLrWin - 1)));
+        if (any_absent) st[r] = GENIE_READ_ABSENT_BASE;
+    }
+}
+
+__global__ void __launch_bounds__(kLrWin) lr_walk_kernel(int mode, int min_len, const long long *__restrict__ off, long long N,
+                                                         const int32_t *__restrict__ st, const int32_t *__restrict__ fwd,
+                                                         const int2 *__restrict__ wmax, const uint8_t *__restrict__ mark,
+                                                         int32_t *__restrict__ bst, int2 *__restrict__ jc)
+{
+    __shared__ int sJ[kLrWin], sC[kLrWin];
+    __shared__ int32_t sf[2 * kLrWin];                         // fwd of the previous window and this one
+    const long long gw = blockIdx.x;
+    const long long r = lr_find(N, gw, [&](long long x) { return lr_wb(off, x); });
+    const long long wb = lr_wb(off, r);
+    const long long o = off[r], Ll = off[r + 1] - o;
+    if (gw - wb < 0 || (gw - wb) * kLrWin >= Ll || st[r] != GENIE_READ_OK) return;      // block-uniform
+    const int L = (int)Ll, w0 = (int)((gw - wb) * kLrWin);
+    const int t = threadIdx.x, i = w0 + t;
+    const int lim = L - w0 < kLrWin ? L : w0 + kLrWin;
+    const bool marked = i < L && (i == 0 || mark[o + i]);
+    const int32_t *f = fwd + o;
+    const int lds0 = w0 - kLrWin;                                // most scans end inside the two windows staged in LDS
+    for (int j = t; j < 2 * kLrWin; j += kLrWin) {
+        const int p = lds0 + j;
+        sf[j] = p >= 0 && p < L ? f[p] : 0;
+    }
+    __syncthreads();
+    auto fv = [&](int p) { return p >= lds0 ? sf[p - lds0] : f[p]; };      // p <= i < L
+    int J = lim, C = 0;
+    if (marked) {
+        int bl = 0, bb = i;
+        for (int b = i; b >= 0;) {
+            if ((b & (kLrWin - 1)) == kLrWin - 1 && fv(b - (kLrWin - 1)) > i) {   // the whole window [b - kLrWin + 1, b] covers i
+                const int2 m = wmax[wb + (b >> kLrWinShift)];
+                if (m.x >= bl) { bl = m.x; bb = m.y; }                           // going down: ties go to the smaller position
+                b -= kLrWin;
+                continue;
+            }
+            const int v = fv(b);
+            if (v <= i) break;
+            if (v - b >= bl) { bl = v - b; bb = b; }
+            b--;
+        }
+        if (bl > 0) {
+            J = bb + bl;
+            C = (mode != GENIE_MODE_BWA || bl >= min_len) ? 1 : 0;
+            bst[o + i] = bb;
+        } else {
+            J = L;                                               // read[i] occurs nowhere: the read is flagged (LR2)
+        }
+    }
+    sJ[t] = J;
+    sC[t] = C;
+    __syncthreads();
+    // an end inside the window is a value of fwd[], so it is marked and has its own step
+    for (int round = 0; round < kLrWinShift; round++) {
+        int nJ = J, nC = C;
+        if (marked && J < lim) {
+            nJ = sJ[J - w0];
+            nC = C + sC[J - w0];
+        }
+        __syncthreads();
+        J = nJ;
+        C = nC;
+        sJ[t] = J;
+        sC[t] = C;
+        __syncthreads();
+    }
+    if (marked) jc[o + i] = make_int2(J, C);
+}
+
+__global__ void __launch_bounds__(256) lr_chain_kernel(const long long *__restrict__ off, long long N, const int32_t *__restrict__ st,
+                                                       const int2 *__restrict__ jc, int32_t *__restrict__ entry,
+                                                       int32_t *__restrict__ base, int32_t *__restrict__ cnt)
+{
+    const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= N) return;
+    const long long o = off[r];
+    const int L = (int)(off[r + 1] - o);
+    int total = 0;
+    if (st[r] == GENIE_READ_OK && L > 0) {
+        const long long wb = lr_wb(off, r);
+        for (int e = 0; e < L;) {
+            const long long g = wb + (e >> kLrWinShift);
+            entry[g] = e;
+            base[g] = total;
+            const int2 v = jc[o + e];
+            total += v.y;
+            if (v.x <= e) break;                                 // cannot happen: every step leaves the window
+            e = v.x;
+        }
+    }
+    cnt[r] = total;
+}
+
+__global__ void __launch_bounds__(kScanBlock) lr_offsets_kernel(const int32_t *__restrict__ cnt, long long N,
+                                                                const unsigned long long *__restrict__ sums, long long nblocks,
+                                                                long long *__restrict__ offsets)
+{
+    __shared__ unsigned long long wave_total[kScanBlock / kWave];
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+    const long long i = (long long)blockIdx.x * kScanBlock + threadIdx.x;
+    const unsigned long long v = i < N ? (unsigned long long)cnt[i] : 0ull;
+    unsigned long long inc = v;
+#pragma unroll
+    for (int d = 1; d < kWave; d <<= 1) {
+        const unsigned int lo = (unsigned)__shfl_up((int)(unsigned)inc, d, kWave);
+        const unsigned int hi = (unsigned)__shfl_up((int)(unsigned)(inc >> 32), d, kWave);
+        if (lane >= d) inc += ((unsigned long long)hi << 32) | lo;
+    }
+    if (lane == kWave - 1) wave_total[wave] = inc;
+    __syncthreads();
+    unsigned long long before = sums[blockIdx.x];
+    for (int w = 0; w < wave; w++) before += wave_total[w];
+    if (i < N) __builtin_nontemporal_store((long long)(before + inc - v), offsets + i);
+    if (blockIdx.x == 0 && threadIdx.x == 0) __builtin_nontemporal_store((long long)sums[nblocks], offsets + N);
+}
+
+__global__ void __launch_bounds__(256) lr_emit_kernel(DevIndex ix, int mode, int min_len, const long long *__restrict__ off, long long N,
+                                                      long long nwin, const uint64_t *__restrict__ packed, const int32_t *__restrict__ fwd,
+                                                      const int32_t *__restrict__ bst, const int32_t *__restrict__ entry,
+                                                      const int32_t *__restrict__ base, const long long *__restrict__ offsets,
+                                                      int4 *__restrict__ rows, long long cap)
+{
+    const long long gw = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gw >= nwin) return;
+    const int e = entry[gw];
+    if (e < 0) return;                                           // a window the chain jumps over (or of a flagged read)
+    const long long r = lr_find(N, gw, [&](long long x) { return lr_wb(off, x); });
+    const long long o = off[r];
+    const int L = (int)(off[r + 1] - o);
+    const int w0 = (int)((gw - lr_wb(off, r)) * kLrWin);
+    const int lim = L - w0 < kLrWin ? L : w0 + kLrWin;
+    const QPlain Q{packed + lr_wd(off, r)};
+    long long k = offsets[r] + base[gw];
+    for (int i = e; i < lim;) {
+        const int b = bst[o + i], end = fwd[o + b];
+        if (mode != GENIE_MODE_BWA || end - b >= min_len) {
+            if (k < cap) {
+                const int2 iv = sa_interval(ix, ix.dir, Q, b, end - b);
+                store_nt(rows + k, make_uint4((uint32_t)b, (uint32_t)end, (uint32_t)iv.x, (uint32_t)iv.y));
+            }
+            k++;
+        }
+        i = end;
+    }
+}
+
+// workspace: every piece 256-byte aligned
+struct LongArea {
+    int *flag;
+    int32_t *st, *cnt;
+    unsigned long long *sums;
+    uint64_t *packed;
+    int32_t *fwd, *bst;
+    int2 *jc, *wmax;
+    uint8_t *mark;
+    int32_t *entry, *base;
+    long long nwords, nwin, nblocks;
+};
+
+inline int64_t long_area(int64_t N, int64_t total, uint8_t *p, LongArea *a)
+{
+    const int64_t nwords = total / 32 + 3 * N + 4, nwin = total / kLrWin + N + 1, nblocks = (N + kScanBlock - 1) / kScanBlock;
+    int64_t at = 0;
+    auto take = [&](int64_t bytes) { uint8_t *q = p ? p + at : nullptr; at += ws_align(bytes); return q; };
+    uint8_t *flag = take(256), *st = take(4 * N), *cnt = take(4 * N), *sums = take(8 * (nblocks + 1)), *packed = take(8 * nwords),
+            *fwd = take(4 * total), *bst = take(4 * total), *jc = take(8 * total), *mark = take(total), *wmax = take(8 * nwin),
+            *entry = take(4 * nwin), *base = take(4 * nwin);
+    if (a) {
+        a->flag = reinterpret_cast<int *>(flag);
+        a->st = reinterpret_cast<int32_t *>(st);
+        a->cnt = reinterpret_cast<int32_t *>(cnt);
+        a->sums = reinterpret_cast<unsigned long long *>(sums);
+        a->packed = reinterpret_cast<uint64_t *>(packed);
+        a->fwd = reinterpret_cast<int32_t *>(fwd);
+        a->bst = reinterpret_cast<int32_t *>(bst);
+        a->jc = reinterpret_cast<int2 *>(jc);
+        a->mark = mark;
+        a->wmax = reinterpret_cast<int2 *>(wmax);
+        a->entry = reinterpret_cast<int32_t *>(entry);
+        a->base = reinterpret_cast<int32_t *>(base);
+        a->nwords = nwords;
+        a->nwin = nwin;
+        a->nblocks = nblocks;
+    }
+    return at;
+}
+
+}  // namespace
+
+int64_t find_smems_long_workspace_bytes(int64_t N, int64_t total_bases) { return long_area(N, total_bases, nullptr, nullptr); }
+
+int launch_find_smems_long(const genie_index *ix, int32_t mode, const uint8_t *d_bases, const int64_t *d_read_offsets, int64_t N,
+                           int64_t total_bases, int64_t max_len, int32_t min_len, int64_t *d_offsets, int32_t *d_rows,
+                           int64_t out_cap_rows, int32_t *d_status, void *d_ws, int64_t ws_bytes, void *stream)
+{
+    (void)ws_bytes;
+    hipStream_t s = (hipStream_t)stream;
+    if (N == 0) {
+        HIP_TRY(hipMemsetAsync(d_offsets, 0, 8, s));
+        return GENIE_OK;
+    }
+    LongArea a;
+    long_area(N, total_bases, static_cast<uint8_t *>(d_ws), &a);
+    const long long *off = reinterpret_cast<const long long *>(d_read_offsets);
+    HIP_TRY(hipMemsetAsync(a.flag, 0, 4, s));
+    HIP_TRY(hipMemsetAsync(a.entry, 0xFF, a.nwin * 4, s));
+    if (total_bases > 0) HIP_TRY(hipMemsetAsync(a.mark, 0, total_bases, s));
+    hipLaunchKernelGGL(lr_check_kernel, dim3((unsigned)((N + 1 + 255) / 256)), dim3(256), 0, s, off, (long long)N, (long long)total_bases,
+                       (long long)max_len, mode, ix->dev.K, a.flag, a.st);
+    HIP_TRY(hipGetLastError());
+    int bad = 0;
+    HIP_TRY(hipMemcpyAsync(&bad, a.flag, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (bad) return GENIE_E_INVALID;
+
+    hipLaunchKernelGGL(lr_pack_kernel, dim3((unsigned)((a.nwords + 255) / 256)), dim3(256), 0, s, d_bases, off, (long long)N, a.nwords,
+                       a.packed, a.st);
+    HIP_TRY(hipGetLastError());
+    const dim3 fgrid((unsigned)((a.nwin + kLrFwdWaves - 1) / kLrFwdWaves)), fblock(kLrFwdWaves * 64);
+    if (ix->dev.flags & kFlagCompactTable)
+        hipLaunchKernelGGL(lr_fwd_kernel<true>, fgrid, fblock, 0, s, ix->dev, mode, off, (long long)N, a.nwin, a.packed, a.st, a.fwd, a.wmax,
+                           a.mark, table_bytes(ix));
+    else
+        hipLaunchKernelGGL(lr_fwd_kernel<false>, fgrid, fblock, 0, s, ix->dev, mode, off, (long long)N, a.nwin, a.packed, a.st, a.fwd,
+                           a.wmax, a.mark, table_bytes(ix));
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(lr_walk_kernel, dim3((unsigned)a.nwin), dim3(kLrWin), 0, s, mode, min_len, off, (long long)N, a.st, a.fwd, a.wmax,
+                       a.mark, a.bst, a.jc);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(lr_chain_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, off, (long long)N, a.st, a.jc, a.entry, a.base,
+                       a.cnt);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(compact_block_sums, dim3((unsigned)a.nblocks), dim3(kScanBlock), 0, s, a.cnt, (long long)N, 0x7fffffff, a.sums);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(scan_block_sums_kernel, dim3(1), dim3(kScanBlock), 0, s, a.sums, a.nblocks);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(lr_offsets_kernel, dim3((unsigned)a.nblocks), dim3(kScanBlock), 0, s, a.cnt, (long long)N, a.sums, a.nblocks,
+                       reinterpret_cast<long long *>(d_offsets));
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(lr_emit_kernel, dim3((unsigned)((a.nwin + 255) / 256)), dim3(256), 0, s, ix->dev, mode, min_len, off, (long long)N,
+                       a.nwin, a.packed, a.fwd, a.bst, a.entry, a.base, reinterpret_cast<const long long *>(d_offsets),
+                       reinterpret_cast<int4 *>(d_rows), (long long)out_cap_rows);
+    HIP_TRY(hipGetLastError());
+    if (d_status) HIP_TRY(hipMemcpyAsync(d_status, a.st, N * 4, hipMemcpyDeviceToDevice, s));
+    return GENIE_OK;
+}

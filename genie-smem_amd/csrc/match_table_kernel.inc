@@ -217,11 +217,13 @@ __device__ __forceinline__ MtQuad mt_quad_interior(const __amdgpu_buffer_rsrc_t 
 // Slow path over list[c0 .. c0 + 64): positions whose table entry could not decide.
 //   LONG = false: entries are (read << 8 | position) of a group of short reads, results go to their byte rows;
 //   LONG = true:  one long read of L0 bases; entries are positions relative to `wbase` (the window being worked
-//                 on), results go to the window's uint16 row `fwW`.
-template <bool LONG, bool C16>
+//                 on), results go to the window's row `fwW` (uint16; int32 for genie_find_smems_long).
+// QB: how the packed read is read -- QBits over Dp (LDS), or QPlain over plain 64-bit words (LONG only: Dp then points
+// at the words of the read).
+template <bool LONG, bool C16, class QB = QBits, class FW = uint16_t>
 __device__ __forceinline__ void mt_slow(const DevIndex &ix, const __amdgpu_buffer_rsrc_t mtab, const __amdgpu_buffer_rsrc_t ov, int mode, int lane, int c0,
                                         int count, const uint16_t *list, const uint32_t *Dp, int DW, const int *Ls,
-                                        uint8_t *fwL, int FS, int L0 = 0, int wbase = 0, uint16_t *fwW = nullptr)
+                                        uint8_t *fwL, int FS, int L0 = 0, int wbase = 0, FW *fwW = nullptr)
 {
     const int K = ix.K, P = ix.P, P2 = ix.P2;
     const int idx = c0 + lane;
@@ -230,10 +232,10 @@ __device__ __forceinline__ void mt_slow(const DevIndex &ix, const __amdgpu_buffe
     uint32_t mask = 0, lb = 0, c = 0, xmin = ~0u, xkq = 0;
     bool general = false;
     uint64_t w = 0, xq = 0;
-    QBits Q{Dp};
+    QB Q{reinterpret_cast<decltype(QB::p)>(Dp)};
     if (on) {
         const uint32_t e = (uint32_t)list[idx];
-        if (LONG) {
+        if constexpr (LONG) {
             a = wbase + (int)e;
             m = L0 - a;
         } else {
@@ -374,7 +376,7 @@ __device__ __forceinline__ void mt_slow(const DevIndex &ix, const __amdgpu_buffe
         }
     }
     if (on) {
-        if (LONG) fwW[a - wbase] = (uint16_t)(a + best);
+        if (LONG) fwW[a - wbase] = (FW)(a + best);
         else fwL[u * FS + a] = (uint8_t)(a + best);
     }
 }

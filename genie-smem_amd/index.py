@@ -417,6 +417,40 @@ class GenieIndex:
                 return offsets, rows[:total], status
             cap_rows = total                      # capacity guess too small: rerun with the exact size
 
+    def find_smems_long(self, mode, bases, read_offsets, min_len=1, rows_hint=None):
+        """SMEMs of reads of any length (genie_find_smems_long) -> (offsets int64[N+1], smems int32[S,4], status).
+        bases: uint8 codes of all reads back to back; read_offsets: int64[N+1], read r = bases[read_offsets[r] ..
+        read_offsets[r+1]).  Either may be on the device or the host.  Rows and status as find_smems."""
+        self._need_device()
+        bases = self._as_dev(bases, torch.uint8).reshape(-1)
+        read_offsets = self._as_dev(read_offsets, torch.int64).reshape(-1)
+        if read_offsets.numel() < 1:
+            raise ValueError("read_offsets needs N + 1 entries")
+        n_reads = read_offsets.numel() - 1
+        total = bases.numel()
+        max_len = int((read_offsets[1:] - read_offsets[:-1]).max().item()) if n_reads else 0
+        max_len = min(max(max_len, 0), 2**31 - 1)
+        if total == 0:
+            bases = torch.zeros(1, dtype=torch.uint8, device=self.device)
+        offsets = torch.empty(n_reads + 1, dtype=torch.int64, device=self.device)
+        status = torch.empty(n_reads, dtype=torch.int32, device=self.device)
+        ws_bytes = int(N.lib().genie_find_smems_long_workspace_bytes(n_reads, total, max_len))
+        if ws_bytes < 0:
+            raise N.GenieError(ws_bytes, "genie_find_smems_long_workspace_bytes")
+        ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=self.device)
+        cap_rows = int(rows_hint) if rows_hint else max(8 * n_reads, total // 6)
+        while True:
+            rows = torch.empty((max(cap_rows, 1), 4), dtype=torch.int32, device=self.device)
+            with torch.cuda.device(self.device):
+                N.check(N.lib().genie_find_smems_long(self._h, N.MODES[mode], _ptr(bases), _ptr(read_offsets), n_reads, total,
+                                                      max_len, int(min_len), _ptr(offsets), _ptr(rows), rows.shape[0],
+                                                      _ptr(status), _ptr(ws), ws_bytes, _stream(self.device)),
+                        "genie_find_smems_long")
+            got = int(offsets[-1].item())
+            if got <= rows.shape[0]:
+                return offsets, rows[:got], status
+            cap_rows = got                        # capacity guess too small: rerun with the exact size
+
     def find_smems_packed(self, mode, packed, max_len, lens=None, min_len=1, rows_hint=None, row_bytes=8):
         """genie_find_smems_packed (or, `row_bytes` = 6, genie_find_smems_packed6): 2-bit packed reads (packing.pack_reads;
         uint8 [N, stride] on the device) -> (counts8 uint8[N], status8 uint8[N], rows uint8[S, row_bytes], escapes int64[E, 2]);

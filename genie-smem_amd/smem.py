@@ -104,6 +104,19 @@ class SMEM:
             lens = ln
         return ix.find_smems_split(mat if width else mat[:, :0], lens, minimum_length)
 
+    def find_smems_long(self, reads, minimum_length=1, mode="bwa"):
+        """SMEMs of reads of any length (genie_find_smems_long).  reads: list[str], or (bases, read_offsets) -- uint8 codes
+        back to back and int64[N+1] offsets, numpy or torch.  -> (offsets, smems[S, 4], status) like find_smems_bwa."""
+        ix = self.matcher.index(self.lut.lut_size)
+        if isinstance(reads, tuple):
+            bases, read_offsets = reads
+            return ix.find_smems_long(mode, bases, read_offsets, minimum_length)
+        enc = [self.matcher.encode(r) for r in reads]
+        offs = np.zeros(len(enc) + 1, np.int64)
+        offs[1:] = np.cumsum([len(e) for e in enc]) if enc else []
+        bases = np.concatenate(enc).astype(np.uint8) if enc else np.zeros(0, np.uint8)
+        return ix.find_smems_long(mode, bases, offs, minimum_length)
+
     def find_smems_lut(self, reads, lens=None):
         return self._find("lut", reads, lens, 1)
 
@@ -117,7 +130,11 @@ class SMEM:
             if mode == "bwa":
                 return {}
             raise KeyError("")                                # SMEM.py:39 on an empty query
-        offsets, smems, status = self._find(mode, codes.reshape(1, -1), None, min_len)
+        if len(codes) > N.MAX_READ_LEN:                       # past the fixed-stride path's limit: the long-read path
+            ix = self.matcher.index(self.lut.lut_size)
+            offsets, smems, status = ix.find_smems_long(mode, codes, np.asarray([0, len(codes)], np.int64), min_len)
+        else:
+            offsets, smems, status = self._find(mode, codes.reshape(1, -1), None, min_len)
         st = int(status[0].item())
         if st == N.READ_ABSENT_BASE:
             raise KeyError("")            # reference: forward_match[0][""] (SMEM.py:39) / runaway loop

@@ -272,6 +272,22 @@ int genie_find_smems_split(const genie_index *ix, const uint8_t *d_reads, const 
                            int32_t fixed_len, int32_t min_len, int64_t *d_offsets, int32_t *d_rows, int64_t out_cap_rows,
                            int32_t *d_status, void *d_workspace, int64_t workspace_bytes, void *stream);
 
+/* SMEMs of reads of ANY length (genie_find_smems_csr is limited to GENIE_MAX_READ_LEN bases).  The reads come as CSR:
+ * read r is d_bases[d_read_offsets[r] .. d_read_offsets[r+1]) (codes 0..3; N+1 offsets, int64, on the device), any length
+ * from 0 to 2^31 - 1.  total_bases and max_len are host-side bounds: every offset must lie in [0, total_bases] and no read
+ * may be longer than max_len; offsets that decrease or break a bound give GENIE_E_INVALID (checked on the device).
+ * Output as genie_find_smems_csr: d_offsets[N+1], int32 rows (start, end, lo, hi) in input order and get_SMEMS order,
+ * min_len applied in BWA mode, rows past out_cap_rows dropped (d_offsets[N] still the true total), d_status[r] (may be
+ * NULL) the same GENIE_READ_* codes.  For every read that genie_find_smems_csr accepts, rows and status are the same bytes.
+ * d_rows 16-byte aligned; d_workspace 256-byte aligned, genie_find_smems_long_workspace_bytes(N, total_bases, max_len)
+ * bytes (GENIE_E_CAPACITY when smaller): about 17.3 bytes per base plus 48 per read.  Argument checks come before the
+ * device check.  This call synchronizes `stream` once, after the offset check and before any other kernel runs. */
+int64_t genie_find_smems_long_workspace_bytes(int64_t N, int64_t total_bases, int64_t max_len);
+int genie_find_smems_long(const genie_index *ix, int32_t mode, const uint8_t *d_bases, const int64_t *d_read_offsets,
+                          int64_t N, int64_t total_bases, int64_t max_len, int32_t min_len,
+                          int64_t *d_offsets, int32_t *d_rows, int64_t out_cap_rows, int32_t *d_status,
+                          void *d_workspace, int64_t workspace_bytes, void *stream);
+
 /* The same discovery for callers on the far side of a host link (SMEM.find_smems_* on host arrays): 2-bit packed reads in,
  * 8-byte rows out -- 40 instead of 150 bytes per 150-base read over PCIe, 8 instead of 16 per SMEM.  Reads of at most 255
  * bases.  Row r of d_reads2bit = stride_bytes bytes (a multiple of 4, >= 4 * ceil(max length / 16)): byte i holds bases
