@@ -553,6 +553,29 @@ __global__ void __launch_bounds__(256) seed_lookup_kernel(DevIndex ix, const uin
 // ------------------------------------------------------------------ compaction to CSR
 constexpr int kScanBlock = 1024;
 
+// 64-bit sums over a wave, two 32-bit shuffles per step: the sum in every lane, and the inclusive scan
+__device__ __forceinline__ unsigned long long wave_sum64(unsigned long long v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned int lo = (unsigned)__shfl_xor((int)(unsigned)v, off, kWave);
+        const unsigned int hi = (unsigned)__shfl_xor((int)(unsigned)(v >> 32), off, kWave);
+        v += ((unsigned long long)hi << 32) | lo;
+    }
+    return v;
+}
+
+__device__ __forceinline__ unsigned long long wave_inclusive_scan64(unsigned long long v, int lane)
+{
+#pragma unroll
+    for (int off = 1; off < kWave; off <<= 1) {
+        const unsigned int lo = (unsigned)__shfl_up((int)(unsigned)v, off, kWave);
+        const unsigned int hi = (unsigned)__shfl_up((int)(unsigned)(v >> 32), off, kWave);
+        if (lane >= off) v += ((unsigned long long)hi << 32) | lo;
+    }
+    return v;
+}
+
 __global__ void __launch_bounds__(kScanBlock) compact_block_sums(const int32_t *__restrict__ counts, long long N, int cap,
                                                                  unsigned long long *__restrict__ block_sums)
 {
@@ -560,12 +583,7 @@ __global__ void __launch_bounds__(kScanBlock) compact_block_sums(const int32_t *
     const long long i = (long long)blockIdx.x * kScanBlock + threadIdx.x;
     unsigned long long v = 0;                                  // 64-bit sums: interval sizes (genie_locate) can be large
     if (i < N) { const int c = counts[i]; v = (unsigned long long)(c < 0 ? 0 : (c < cap ? c : cap)); }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned int lo = (unsigned)__shfl_xor((int)(unsigned)v, off, kWave);
-        const unsigned int hi = (unsigned)__shfl_xor((int)(unsigned)(v >> 32), off, kWave);
-        v += ((unsigned long long)hi << 32) | lo;
-    }
+    v = wave_sum64(v);
     if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -575,34 +593,8 @@ __global__ void __launch_bounds__(kScanBlock) compact_block_sums(const int32_t *
     }
 }
 
-// single block: exclusive scan of the block sums in place (+ grand total at [nblocks])
-__global__ void __launch_bounds__(kScanBlock) compact_scan_sums(unsigned long long *__restrict__ block_sums, long long nblocks)
-{
-    __shared__ unsigned long long part[kScanBlock];
-    __shared__ unsigned long long carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (long long base = 0; base < nblocks; base += kScanBlock) {
-        const long long i = base + threadIdx.x;
-        const unsigned long long v = i < nblocks ? block_sums[i] : 0;
-        part[threadIdx.x] = v;
-        __syncthreads();
-        for (int off = 1; off < kScanBlock; off <<= 1) {           // Hillis-Steele inclusive scan
-            unsigned long long add = threadIdx.x >= off ? part[threadIdx.x - off] : 0;
-            __syncthreads();
-            part[threadIdx.x] += add;
-            __syncthreads();
-        }
-        if (i < nblocks) block_sums[i] = carry + part[threadIdx.x] - v;
-        __syncthreads();
-        if (threadIdx.x == 0) carry += part[kScanBlock - 1];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) block_sums[nblocks] = carry;
-}
-
-// single block: exclusive scan of the traversal kernels' block sums in place (+ grand total at [nblocks]); eight
-// values per thread and pass, so that 10^5 .. 10^6 sums (10^7 .. 10^8 reads) stay a few tens of microseconds
+// single block: exclusive scan of block sums in place (+ grand total at [nblocks]); eight values per thread and pass, so
+// that 10^5 .. 10^6 sums (10^7 .. 10^8 reads) stay a few tens of microseconds
 __global__ void __launch_bounds__(kScanBlock) scan_block_sums_kernel(unsigned long long *__restrict__ sums, long long nblocks)
 {
     constexpr int kPer = 8;
@@ -653,19 +645,16 @@ __global__ void __launch_bounds__(kScanBlock) compact_scatter(const int32_t *__r
                                                               long long *__restrict__ offsets, int4 *__restrict__ out,
                                                               long long out_cap_rows)
 {
-    __shared__ unsigned long long part[kScanBlock];
+    __shared__ unsigned long long wave_total[kScanBlock / kWave];
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
     const long long i = (long long)blockIdx.x * kScanBlock + threadIdx.x;
     unsigned long long v = 0;
     if (i < N) { const int c = counts[i]; v = (unsigned long long)(c < 0 ? 0 : (c < cap ? c : cap)); }
-    part[threadIdx.x] = v;
+    const unsigned long long inc = wave_inclusive_scan64(v, lane);
+    if (lane == kWave - 1) wave_total[wave] = inc;
     __syncthreads();
-    for (int off = 1; off < kScanBlock; off <<= 1) {
-        unsigned long long add = threadIdx.x >= off ? part[threadIdx.x - off] : 0;
-        __syncthreads();
-        part[threadIdx.x] += add;
-        __syncthreads();
-    }
-    const unsigned long long base = block_sums[blockIdx.x] + part[threadIdx.x] - v;
+    unsigned long long base = block_sums[blockIdx.x] + inc - v;
+    for (int w = 0; w < wave; w++) base += wave_total[w];
     if (i < N) {
         offsets[i] = (long long)base;
         if (i == N - 1) offsets[N] = (long long)(base + v);
@@ -687,6 +676,13 @@ std::string g_err;
     do {                                                                      \
         hipError_t e_ = (expr);                                               \
         if (e_ != hipSuccess) { set_hip_error(#expr, (int)e_); return GENIE_E_HIP; } \
+    } while (0)
+
+// a kernel launch and its check (a template instance with more than one argument goes in through a variable)
+#define LAUNCH(kernel, grid, block, lds, stream, ...)                         \
+    do {                                                                      \
+        hipLaunchKernelGGL(kernel, grid, block, lds, stream, __VA_ARGS__);    \
+        HIP_TRY(hipGetLastError());                                           \
     } while (0)
 
 inline long long table_bytes(const genie_index *ix)
@@ -775,33 +771,38 @@ struct Workspace {
 
 inline int64_t ws_align(int64_t x) { return (x + 255) & ~(int64_t)255; }
 
+// Cuts a workspace into pieces, one after another from `base`, each padded to a multiple of 256 bytes.  With a null base
+// every piece is null and only the bytes are counted: a workspace's size and its pieces come from one layout function.
+struct Carver {
+    uint8_t *base;
+    int64_t at = 0;
+    template <class T> void take(T *&piece, int64_t bytes)
+    {
+        piece = base ? reinterpret_cast<T *>(base + at) : nullptr;
+        at += ws_align(bytes);
+    }
+};
+
 // block sums of the traversal kernels (CSR form): one 64-bit word per block; the smallest block holds 16 reads
 inline int64_t block_sums_bytes(int64_t N) { return (N / 16 + 3) * 8; }
 
-inline int64_t workspace_bytes_for(int64_t N, int max_len)
+// the workspace of N reads of the shape `g`, and a 256-byte tail
+inline int64_t workspace_layout(uint8_t *base, int64_t N, const Geometry &g, Workspace *ws)
 {
-    Geometry g;
-    shape_for(max_len, &g);
-    return ws_align(N * (int64_t)g.fwd_stride) + ws_align(N * (int64_t)g.qp_stride * 16) + ws_align(N * 4) +
-           ws_align(N * (int64_t)g.kj_row * (g.wide ? 4 : 2)) + ws_align(N * 4) + ws_align(block_sums_bytes(N)) + 256;
+    Carver c{base};
+    c.take(ws->fwd, N * (int64_t)g.fwd_stride);
+    c.take(ws->qp, N * (int64_t)g.qp_stride * 16);
+    c.take(ws->status, N * 4);
+    c.take(ws->kj, N * (int64_t)g.kj_row * (g.wide ? 4 : 2));
+    c.take(ws->counts, N * 4);
+    c.take(ws->scan_tmp, block_sums_bytes(N));
+    return c.at + 256;
 }
 
 inline int carve_workspace(void *d_ws, int64_t ws_bytes, int64_t N, const Geometry &g, Workspace *ws)
 {
-    if (!d_ws || ws_bytes < workspace_bytes_for(N, g.max_len) || (reinterpret_cast<uintptr_t>(d_ws) & 255) != 0)
+    if (!d_ws || ws_bytes < workspace_layout(static_cast<uint8_t *>(d_ws), N, g, ws) || (reinterpret_cast<uintptr_t>(d_ws) & 255) != 0)
         return GENIE_E_CAPACITY;
-    uint8_t *p = reinterpret_cast<uint8_t *>(d_ws);
-    ws->fwd = p;
-    p += ws_align(N * (int64_t)g.fwd_stride);
-    ws->qp = reinterpret_cast<RefRec *>(p);
-    p += ws_align(N * (int64_t)g.qp_stride * 16);
-    ws->status = reinterpret_cast<int32_t *>(p);
-    p += ws_align(N * 4);
-    ws->kj = p;
-    p += ws_align(N * (int64_t)g.kj_row * (g.wide ? 4 : 2));
-    ws->counts = reinterpret_cast<int32_t *>(p);
-    p += ws_align(N * 4);
-    ws->scan_tmp = p;
     return GENIE_OK;
 }
 
@@ -834,20 +835,19 @@ int launch_pipeline(const genie_index *ix, const Geometry &g, const uint8_t *d_r
     if (WIDE) {
         auto km = c16 ? match_table_long_kernel<true> : match_table_long_kernel<false>;
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(km), hipFuncAttributeMaxDynamicSharedMemorySize, g.lds));
-        hipLaunchKernelGGL(km, dim3(g.grid), dim3(g.block), g.lds, s, ix->dev, (int)MODE, d_reads, d_lens, (long long)N, stride,
-                           fixed_len, reinterpret_cast<uint8_t *>(ws.fwd), g.fwd_stride, ws.qp, g.qp_recs, st,
-                           std::max(g.max_len, 1), mtab_bytes, ix->opt_search_all | ix->opt_scheduling << 16, ix->num_cus > 0 ? ix->num_cus : 256);
+        LAUNCH(km, dim3(g.grid), dim3(g.block), g.lds, s, ix->dev, (int)MODE, d_reads, d_lens, (long long)N, stride,
+               fixed_len, reinterpret_cast<uint8_t *>(ws.fwd), g.fwd_stride, ws.qp, g.qp_recs, st,
+               std::max(g.max_len, 1), mtab_bytes, ix->opt_search_all | ix->opt_scheduling << 16, ix->num_cus > 0 ? ix->num_cus : 256);
     } else {
         auto km = csr.packed ? (c16 ? (g.wps == 4 ? match_table_kernel<4, true, true> : match_table_kernel<6, true, true>)
                                     : (g.wps == 4 ? match_table_kernel<4, false, true> : match_table_kernel<8, false, true>))
                              : (c16 ? (g.wps == 4 ? match_table_kernel<4, true, false> : match_table_kernel<6, true, false>)
                                     : (g.wps == 4 ? match_table_kernel<4, false, false> : match_table_kernel<8, false, false>));
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(km), hipFuncAttributeMaxDynamicSharedMemorySize, g.lds));
-        hipLaunchKernelGGL(km, dim3(g.grid), dim3(g.block), g.lds, s, ix->dev, (int)MODE, d_reads, d_lens, (long long)N, stride,
-                           fixed_len, reinterpret_cast<uint8_t *>(ws.fwd), g.fwd_stride, ws.qp, g.qp_recs, g.qp_stride, st,
-                           g.grp, std::max(g.max_len, 1), mtab_bytes, ix->opt_search_all | ix->opt_debug << 8 | ix->opt_scheduling << 16, ix->num_cus > 0 ? ix->num_cus : 256);
+        LAUNCH(km, dim3(g.grid), dim3(g.block), g.lds, s, ix->dev, (int)MODE, d_reads, d_lens, (long long)N, stride,
+               fixed_len, reinterpret_cast<uint8_t *>(ws.fwd), g.fwd_stride, ws.qp, g.qp_recs, g.qp_stride, st,
+               g.grp, std::max(g.max_len, 1), mtab_bytes, ix->opt_search_all | ix->opt_debug << 8 | ix->opt_scheduling << 16, ix->num_cus > 0 ? ix->num_cus : 256);
     }
-    HIP_TRY(hipGetLastError());
     if (ix->ev_search_end) HIP_TRY(hipEventRecord((hipEvent_t)ix->ev_search_end, s));
     if (ix->opt_search_only) return GENIE_W_SEARCH_ONLY;   // timing experiments: no counts / offsets / rows were written
     // the head of a read's (count, pairs) row: behind its packed-read records (short reads) or the kj row itself
@@ -863,26 +863,22 @@ int launch_pipeline(const genie_index *ix, const Geometry &g, const uint8_t *d_r
         // bases 340 -> 270 us with two lanes; 18 750 x 8000 bases 410 us with 16 lanes, 690 us with four lanes of eight positions.
         const int lanes = N >= kLongTwoLaneReads ? 2 : 16;
         auto kl = lanes == 2 ? traverse_long_kernel<MODE, 2, 8> : traverse_long_kernel<MODE, 16, 1>;
-        hipLaunchKernelGGL(kl, dim3((unsigned)((N + tb / lanes - 1) / (tb / lanes))), dim3(tb), lanes == 2 ? (tb / lanes) * kLongRowBytes : 0, s, d_lens,
-                           (long long)N, fixed_len, min_len, ws.fwd, g.fwd_stride, cnt, reinterpret_cast<uint32_t *>(ws.kj),
-                           g.kj_row, csr.offsets ? g.kj_row : cap, st, bsums);
+        LAUNCH(kl, dim3((unsigned)((N + tb / lanes - 1) / (tb / lanes))), dim3(tb), lanes == 2 ? (tb / lanes) * kLongRowBytes : 0, s, d_lens,
+               (long long)N, fixed_len, min_len, ws.fwd, g.fwd_stride, cnt, reinterpret_cast<uint32_t *>(ws.kj),
+               g.kj_row, csr.offsets ? g.kj_row : cap, st, bsums);
         reads_per_block = tb / lanes;
     } else {                                 // one lane per read, rows staged in LDS
         auto kb = traverse_kernel<MODE>;
         const int lds_b = tb * g.fwd_lds;
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kb), hipFuncAttributeMaxDynamicSharedMemorySize, lds_b));
-        hipLaunchKernelGGL(kb, dim3((unsigned)((N + tb - 1) / tb)), dim3(tb), lds_b, s, ix->dev, d_lens, (long long)N,
-                           fixed_len, min_len, ws.fwd, g.fwd_stride, g.fwd_lds, cnt, ws.kj, g.kj_row, head, head_stride,
-                           csr.offsets ? g.kj_row : cap, st, bsums, csr.counts8, csr.status8);
+        LAUNCH(kb, dim3((unsigned)((N + tb - 1) / tb)), dim3(tb), lds_b, s, ix->dev, d_lens, (long long)N,
+               fixed_len, min_len, ws.fwd, g.fwd_stride, g.fwd_lds, cnt, ws.kj, g.kj_row, head, head_stride,
+               csr.offsets ? g.kj_row : cap, st, bsums, csr.counts8, csr.status8);
     }
-    HIP_TRY(hipGetLastError());
     int block_shift = 0;
     while ((1 << block_shift) < reads_per_block) block_shift++;
-    if (csr.offsets) {                       // scan of the traversal blocks' sums; K_C adds the in-block part
-        const long long nb = (N + reads_per_block - 1) / reads_per_block;
-        hipLaunchKernelGGL(scan_block_sums_kernel, dim3(1), dim3(kScanBlock), 0, s, bsums, nb);
-        HIP_TRY(hipGetLastError());
-    }
+    if (csr.offsets)                         // scan of the traversal blocks' sums; K_C adds the in-block part
+        LAUNCH(scan_block_sums_kernel, dim3(1), dim3(kScanBlock), 0, s, bsums, (N + reads_per_block - 1) / reads_per_block);
     // K_C: intervals + final rows, 16 lanes per read (4 reads per wave pass), persistent blocks
     const int cus = ix->num_cus > 0 ? ix->num_cus : 256;
     // (half the blocks help on the 1 Mb reference, 1.50 -> 1.40 ms per 4 x 10^6 reads, but cost at 300 kb, 0.215 -> 0.250 ms
@@ -899,22 +895,20 @@ int launch_pipeline(const genie_index *ix, const Geometry &g, const uint8_t *d_r
         HIP_TRY(hipMemsetAsync(csr.offsets, 0, 16, s));
         auto kp = csr.row_bytes == 6 ? (c16 ? interval_kernel<true, false, true, 2> : interval_kernel<true, false, false, 2>)
                                      : (c16 ? interval_kernel<true, false, true, 1> : interval_kernel<true, false, false, 1>);
-        hipLaunchKernelGGL(kp, dim3((unsigned)grid_c), dim3(kIvWaves * kWave), 0, s, ix->dev, (long long)N,
-                           ws.kj, g.kj_row, head, head_stride, ws.qp, g.qp_stride, reinterpret_cast<void *>(csr.rows), 0,
-                           reinterpret_cast<long long *>(csr.offsets), (long long)csr.cap_rows, bsums, cnt, block_shift, esc, sched_c);
-        HIP_TRY(hipGetLastError());
+        LAUNCH(kp, dim3((unsigned)grid_c), dim3(kIvWaves * kWave), 0, s, ix->dev, (long long)N,
+               ws.kj, g.kj_row, head, head_stride, ws.qp, g.qp_stride, reinterpret_cast<void *>(csr.rows), 0,
+               reinterpret_cast<long long *>(csr.offsets), (long long)csr.cap_rows, bsums, cnt, block_shift, esc, sched_c);
         return GENIE_OK;
     }
     auto kc = csr.offsets ? (c16 ? interval_kernel<true, WIDE, true> : interval_kernel<true, WIDE, false>)
                           : (c16 ? interval_kernel<false, WIDE, true> : interval_kernel<false, WIDE, false>);
     if (csr.offsets)
-        hipLaunchKernelGGL(kc, dim3((unsigned)grid_c), dim3(kIvWaves * kWave), 0, s, ix->dev, (long long)N,
-                           ws.kj, g.kj_row, head, head_stride, ws.qp, g.qp_stride, reinterpret_cast<void *>(csr.rows), 0,
-                           reinterpret_cast<long long *>(csr.offsets), (long long)csr.cap_rows, bsums, cnt, block_shift, esc, sched_c);
+        LAUNCH(kc, dim3((unsigned)grid_c), dim3(kIvWaves * kWave), 0, s, ix->dev, (long long)N,
+               ws.kj, g.kj_row, head, head_stride, ws.qp, g.qp_stride, reinterpret_cast<void *>(csr.rows), 0,
+               reinterpret_cast<long long *>(csr.offsets), (long long)csr.cap_rows, bsums, cnt, block_shift, esc, sched_c);
     else
-        hipLaunchKernelGGL(kc, dim3((unsigned)grid_c), dim3(kIvWaves * kWave), 0, s, ix->dev, (long long)N,
-                           ws.kj, g.kj_row, head, head_stride, ws.qp, g.qp_stride, reinterpret_cast<void *>(d_slots), cap, nullptr, 0ll, nullptr, nullptr, 0, esc, sched_c);
-    HIP_TRY(hipGetLastError());
+        LAUNCH(kc, dim3((unsigned)grid_c), dim3(kIvWaves * kWave), 0, s, ix->dev, (long long)N,
+               ws.kj, g.kj_row, head, head_stride, ws.qp, g.qp_stride, reinterpret_cast<void *>(d_slots), cap, nullptr, 0ll, nullptr, nullptr, 0, esc, sched_c);
     return GENIE_OK;
 }
 
@@ -971,7 +965,13 @@ int search_kernel_name(const genie_index *ix, int32_t mode, int32_t max_len, cha
     return GENIE_OK;
 }
 
-int64_t find_smems_workspace_bytes(int64_t N, int32_t max_len) { return workspace_bytes_for(N, max_len); }
+int64_t find_smems_workspace_bytes(int64_t N, int32_t max_len)
+{
+    Geometry g;
+    shape_for(max_len, &g);
+    Workspace ws;
+    return workspace_layout(nullptr, N, g, &ws);
+}
 
 void find_smems_workspace_rows(int32_t max_len, int32_t out[4])
 {
@@ -1070,9 +1070,8 @@ int launch_sa_interval(const genie_index *ix, const uint8_t *d_pats, const int32
     long long grid = std::min<long long>((N + waves - 1) / waves, (long long)cus * std::max(1, (160 * 1024) / lds));
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(sa_interval_kernel),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    hipLaunchKernelGGL(sa_interval_kernel, dim3((unsigned)grid), dim3(waves * kWave), lds, (hipStream_t)stream, ix->dev,
-                       d_pats, d_lens, (long long)N, stride, fixed_len, Lmax, reinterpret_cast<int2 *>(d_out));
-    HIP_TRY(hipGetLastError());
+    LAUNCH(sa_interval_kernel, dim3((unsigned)grid), dim3(waves * kWave), lds, (hipStream_t)stream, ix->dev,
+           d_pats, d_lens, (long long)N, stride, fixed_len, Lmax, reinterpret_cast<int2 *>(d_out));
     return GENIE_OK;
 }
 
@@ -1082,17 +1081,17 @@ int launch_seed_lookup(const genie_index *ix, int32_t mode, const uint8_t *d_kme
     if (N == 0) return GENIE_OK;
     const unsigned grid = (unsigned)((N + 255) / 256);
     if (mode == GENIE_MODE_LUT)
-        hipLaunchKernelGGL(seed_lookup_kernel<GENIE_MODE_LUT>, dim3(grid), dim3(256), 0, (hipStream_t)stream, ix->dev,
-                           d_kmers, (long long)N, reinterpret_cast<int2 *>(d_out), d_pred);
+        LAUNCH(seed_lookup_kernel<GENIE_MODE_LUT>, dim3(grid), dim3(256), 0, (hipStream_t)stream, ix->dev,
+               d_kmers, (long long)N, reinterpret_cast<int2 *>(d_out), d_pred);
     else if (mode == GENIE_MODE_RMI)
-        hipLaunchKernelGGL(seed_lookup_kernel<GENIE_MODE_RMI>, dim3(grid), dim3(256), 0, (hipStream_t)stream, ix->dev,
-                           d_kmers, (long long)N, reinterpret_cast<int2 *>(d_out), d_pred);
+        LAUNCH(seed_lookup_kernel<GENIE_MODE_RMI>, dim3(grid), dim3(256), 0, (hipStream_t)stream, ix->dev,
+               d_kmers, (long long)N, reinterpret_cast<int2 *>(d_out), d_pred);
     else
         return GENIE_E_INVALID;
-    HIP_TRY(hipGetLastError());
     return GENIE_OK;
 }
 
+// one piece, not padded to 256 bytes; launch_compact uses nblocks + 1 words of it (the block sums and their total)
 int64_t compact_tmp_bytes(int64_t N)
 {
     const int64_t nblocks = (N + kScanBlock - 1) / kScanBlock;
@@ -1109,12 +1108,10 @@ int launch_compact(const int32_t *d_counts, const int32_t *d_slots, int64_t N, i
     }
     const long long nblocks = (N + kScanBlock - 1) / kScanBlock;
     unsigned long long *sums = reinterpret_cast<unsigned long long *>(d_tmp);
-    hipLaunchKernelGGL(compact_block_sums, dim3((unsigned)nblocks), dim3(kScanBlock), 0, s, d_counts, (long long)N, cap, sums);
-    hipLaunchKernelGGL(compact_scan_sums, dim3(1), dim3(kScanBlock), 0, s, sums, nblocks);
-    hipLaunchKernelGGL(compact_scatter, dim3((unsigned)nblocks), dim3(kScanBlock), 0, s, d_counts,
-                       reinterpret_cast<const int4 *>(d_slots), (long long)N, cap, sums,
-                       reinterpret_cast<long long *>(d_offsets), reinterpret_cast<int4 *>(d_out), (long long)out_cap_rows);
-    HIP_TRY(hipGetLastError());
+    LAUNCH(compact_block_sums, dim3((unsigned)nblocks), dim3(kScanBlock), 0, s, d_counts, (long long)N, cap, sums);
+    LAUNCH(scan_block_sums_kernel, dim3(1), dim3(kScanBlock), 0, s, sums, nblocks);
+    LAUNCH(compact_scatter, dim3((unsigned)nblocks), dim3(kScanBlock), 0, s, d_counts, reinterpret_cast<const int4 *>(d_slots),
+           (long long)N, cap, sums, reinterpret_cast<long long *>(d_offsets), reinterpret_cast<int4 *>(d_out), (long long)out_cap_rows);
     return GENIE_OK;
 }
 
@@ -1243,7 +1240,25 @@ int validate_image(const genie_index *ix, unsigned int *what, void *stream)
     return h_bad ? GENIE_E_BAD_BLOB : GENIE_OK;
 }
 
-int64_t locate_tmp_bytes(int64_t S) { return ws_align(S * 4) + ws_align(compact_tmp_bytes(S)) + 256; }
+struct LocateArea {
+    int32_t *counts;     // rows per interval
+    uint8_t *scan_tmp;   // launch_compact's scratch
+};
+
+// the scratch of S intervals, and a 256-byte tail
+inline int64_t locate_layout(uint8_t *base, int64_t S, LocateArea *a)
+{
+    Carver c{base};
+    c.take(a->counts, S * 4);
+    c.take(a->scan_tmp, compact_tmp_bytes(S));
+    return c.at + 256;
+}
+
+int64_t locate_tmp_bytes(int64_t S)
+{
+    LocateArea a;
+    return locate_layout(nullptr, S, &a);
+}
 
 int launch_locate(const genie_index *ix, const int32_t *d_lohi, int32_t stride, int64_t S, int64_t *d_offsets,
                   int32_t *d_positions, int64_t cap, void *d_tmp, int64_t tmp_bytes, void *stream)
@@ -1253,16 +1268,15 @@ int launch_locate(const genie_index *ix, const int32_t *d_lohi, int32_t stride, 
         HIP_TRY(hipMemsetAsync(d_offsets, 0, 8, s));
         return GENIE_OK;
     }
-    if (!d_tmp || tmp_bytes < locate_tmp_bytes(S) || (reinterpret_cast<uintptr_t>(d_tmp) & 255) != 0) return GENIE_E_CAPACITY;
-    int32_t *counts = reinterpret_cast<int32_t *>(d_tmp);
-    void *scan_tmp = reinterpret_cast<uint8_t *>(d_tmp) + ws_align(S * 4);
+    LocateArea a;
+    if (!d_tmp || tmp_bytes < locate_layout(static_cast<uint8_t *>(d_tmp), S, &a) || (reinterpret_cast<uintptr_t>(d_tmp) & 255) != 0)
+        return GENIE_E_CAPACITY;
     const unsigned grid = (unsigned)((S + 255) / 256);
-    hipLaunchKernelGGL(locate_count_kernel, dim3(grid), dim3(256), 0, s, d_lohi, stride, (long long)S, counts);
-    int rc = launch_compact(counts, nullptr, S, 0x7FFFFFFF, d_offsets, nullptr, 0, scan_tmp, stream);
+    LAUNCH(locate_count_kernel, dim3(grid), dim3(256), 0, s, d_lohi, stride, (long long)S, a.counts);
+    int rc = launch_compact(a.counts, nullptr, S, 0x7FFFFFFF, d_offsets, nullptr, 0, a.scan_tmp, stream);
     if (rc) return rc;
-    hipLaunchKernelGGL(locate_scatter_kernel, dim3(grid), dim3(256), 0, s, ix->dev, d_lohi, stride, (long long)S,
-                       reinterpret_cast<const long long *>(d_offsets), d_positions, (long long)cap);
-    HIP_TRY(hipGetLastError());
+    LAUNCH(locate_scatter_kernel, dim3(grid), dim3(256), 0, s, ix->dev, d_lohi, stride, (long long)S,
+           reinterpret_cast<const long long *>(d_offsets), d_positions, (long long)cap);
     return GENIE_OK;
 }
 

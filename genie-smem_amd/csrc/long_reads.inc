@@ -26,7 +26,7 @@
 //                         the first end at or behind the window's end reached from e and the rows emitted on the way.
 //   LR4 lr_chain_kernel   one thread per read: the chain from 0, one step per window it enters (not per SMEM).  Writes the
 //                         window's entry end and the rows emitted before it in the read; the read's row count.
-//   scan                  compact_block_sums + scan_block_sums_kernel + lr_offsets_kernel: d_offsets.
+//   launch_compact        the read counts to d_offsets (offsets only).
 //   LR5 lr_emit_kernel    one thread per window the chain enters: its SMEMs in order, the SA interval of each from
 //                         sa_interval over the packed read (any length), each row written once, non-temporal.
 namespace {
@@ -268,29 +268,6 @@ __global__ void __launch_bounds__(256) lr_chain_kernel(const long long *__restri
     cnt[r] = total;
 }
 
-__global__ void __launch_bounds__(kScanBlock) lr_offsets_kernel(const int32_t *__restrict__ cnt, long long N,
-                                                                const unsigned long long *__restrict__ sums, long long nblocks,
-                                                                long long *__restrict__ offsets)
-{
-    __shared__ unsigned long long wave_total[kScanBlock / kWave];
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
-    const long long i = (long long)blockIdx.x * kScanBlock + threadIdx.x;
-    const unsigned long long v = i < N ? (unsigned long long)cnt[i] : 0ull;
-    unsigned long long inc = v;
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-        const unsigned int lo = (unsigned)__shfl_up((int)(unsigned)inc, d, kWave);
-        const unsigned int hi = (unsigned)__shfl_up((int)(unsigned)(inc >> 32), d, kWave);
-        if (lane >= d) inc += ((unsigned long long)hi << 32) | lo;
-    }
-    if (lane == kWave - 1) wave_total[wave] = inc;
-    __syncthreads();
-    unsigned long long before = sums[blockIdx.x];
-    for (int w = 0; w < wave; w++) before += wave_total[w];
-    if (i < N) __builtin_nontemporal_store((long long)(before + inc - v), offsets + i);
-    if (blockIdx.x == 0 && threadIdx.x == 0) __builtin_nontemporal_store((long long)sums[nblocks], offsets + N);
-}
-
 __global__ void __launch_bounds__(256) lr_emit_kernel(DevIndex ix, int mode, int min_len, const long long *__restrict__ off, long long N,
                                                       long long nwin, const uint64_t *__restrict__ packed, const int32_t *__restrict__ fwd,
                                                       const int32_t *__restrict__ bst, const int32_t *__restrict__ entry,
@@ -321,50 +298,45 @@ __global__ void __launch_bounds__(256) lr_emit_kernel(DevIndex ix, int mode, int
     }
 }
 
-// workspace: every piece 256-byte aligned
 struct LongArea {
     int *flag;
     int32_t *st, *cnt;
-    unsigned long long *sums;
+    uint8_t *sums;                   // launch_compact's scratch: nblocks + 1 words
     uint64_t *packed;
     int32_t *fwd, *bst;
     int2 *jc, *wmax;
     uint8_t *mark;
     int32_t *entry, *base;
-    long long nwords, nwin, nblocks;
+    long long nwords, nwin;
 };
 
-inline int64_t long_area(int64_t N, int64_t total, uint8_t *p, LongArea *a)
+inline int64_t long_layout(uint8_t *p, int64_t N, int64_t total, LongArea *a)
 {
-    const int64_t nwords = total / 32 + 3 * N + 4, nwin = total / kLrWin + N + 1, nblocks = (N + kScanBlock - 1) / kScanBlock;
-    int64_t at = 0;
-    auto take = [&](int64_t bytes) { uint8_t *q = p ? p + at : nullptr; at += ws_align(bytes); return q; };
-    uint8_t *flag = take(256), *st = take(4 * N), *cnt = take(4 * N), *sums = take(8 * (nblocks + 1)), *packed = take(8 * nwords),
-            *fwd = take(4 * total), *bst = take(4 * total), *jc = take(8 * total), *mark = take(total), *wmax = take(8 * nwin),
-            *entry = take(4 * nwin), *base = take(4 * nwin);
-    if (a) {
-        a->flag = reinterpret_cast<int *>(flag);
-        a->st = reinterpret_cast<int32_t *>(st);
-        a->cnt = reinterpret_cast<int32_t *>(cnt);
-        a->sums = reinterpret_cast<unsigned long long *>(sums);
-        a->packed = reinterpret_cast<uint64_t *>(packed);
-        a->fwd = reinterpret_cast<int32_t *>(fwd);
-        a->bst = reinterpret_cast<int32_t *>(bst);
-        a->jc = reinterpret_cast<int2 *>(jc);
-        a->mark = mark;
-        a->wmax = reinterpret_cast<int2 *>(wmax);
-        a->entry = reinterpret_cast<int32_t *>(entry);
-        a->base = reinterpret_cast<int32_t *>(base);
-        a->nwords = nwords;
-        a->nwin = nwin;
-        a->nblocks = nblocks;
-    }
-    return at;
+    a->nwords = total / 32 + 3 * N + 4;
+    a->nwin = total / kLrWin + N + 1;
+    Carver c{p};
+    c.take(a->flag, 256);
+    c.take(a->st, 4 * N);
+    c.take(a->cnt, 4 * N);
+    c.take(a->sums, 8 * ((N + kScanBlock - 1) / kScanBlock + 1));
+    c.take(a->packed, 8 * a->nwords);
+    c.take(a->fwd, 4 * total);
+    c.take(a->bst, 4 * total);
+    c.take(a->jc, 8 * total);
+    c.take(a->mark, total);
+    c.take(a->wmax, 8 * a->nwin);
+    c.take(a->entry, 4 * a->nwin);
+    c.take(a->base, 4 * a->nwin);
+    return c.at;
 }
 
 }  // namespace
 
-int64_t find_smems_long_workspace_bytes(int64_t N, int64_t total_bases) { return long_area(N, total_bases, nullptr, nullptr); }
+int64_t find_smems_long_workspace_bytes(int64_t N, int64_t total_bases)
+{
+    LongArea a;
+    return long_layout(nullptr, N, total_bases, &a);
+}
 
 int launch_find_smems_long(const genie_index *ix, int32_t mode, const uint8_t *d_bases, const int64_t *d_read_offsets, int64_t N,
                            int64_t total_bases, int64_t max_len, int32_t min_len, int64_t *d_offsets, int32_t *d_rows,
@@ -377,47 +349,36 @@ int launch_find_smems_long(const genie_index *ix, int32_t mode, const uint8_t *d
         return GENIE_OK;
     }
     LongArea a;
-    long_area(N, total_bases, static_cast<uint8_t *>(d_ws), &a);
+    long_layout(static_cast<uint8_t *>(d_ws), N, total_bases, &a);
     const long long *off = reinterpret_cast<const long long *>(d_read_offsets);
     HIP_TRY(hipMemsetAsync(a.flag, 0, 4, s));
     HIP_TRY(hipMemsetAsync(a.entry, 0xFF, a.nwin * 4, s));
     if (total_bases > 0) HIP_TRY(hipMemsetAsync(a.mark, 0, total_bases, s));
-    hipLaunchKernelGGL(lr_check_kernel, dim3((unsigned)((N + 1 + 255) / 256)), dim3(256), 0, s, off, (long long)N, (long long)total_bases,
-                       (long long)max_len, mode, ix->dev.K, a.flag, a.st);
-    HIP_TRY(hipGetLastError());
+    LAUNCH(lr_check_kernel, dim3((unsigned)((N + 1 + 255) / 256)), dim3(256), 0, s, off, (long long)N, (long long)total_bases,
+           (long long)max_len, mode, ix->dev.K, a.flag, a.st);
     int bad = 0;
     HIP_TRY(hipMemcpyAsync(&bad, a.flag, 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     if (bad) return GENIE_E_INVALID;
 
-    hipLaunchKernelGGL(lr_pack_kernel, dim3((unsigned)((a.nwords + 255) / 256)), dim3(256), 0, s, d_bases, off, (long long)N, a.nwords,
-                       a.packed, a.st);
-    HIP_TRY(hipGetLastError());
+    LAUNCH(lr_pack_kernel, dim3((unsigned)((a.nwords + 255) / 256)), dim3(256), 0, s, d_bases, off, (long long)N, a.nwords,
+           a.packed, a.st);
     const dim3 fgrid((unsigned)((a.nwin + kLrFwdWaves - 1) / kLrFwdWaves)), fblock(kLrFwdWaves * 64);
     if (ix->dev.flags & kFlagCompactTable)
-        hipLaunchKernelGGL(lr_fwd_kernel<true>, fgrid, fblock, 0, s, ix->dev, mode, off, (long long)N, a.nwin, a.packed, a.st, a.fwd, a.wmax,
-                           a.mark, table_bytes(ix));
+        LAUNCH(lr_fwd_kernel<true>, fgrid, fblock, 0, s, ix->dev, mode, off, (long long)N, a.nwin, a.packed, a.st, a.fwd, a.wmax,
+               a.mark, table_bytes(ix));
     else
-        hipLaunchKernelGGL(lr_fwd_kernel<false>, fgrid, fblock, 0, s, ix->dev, mode, off, (long long)N, a.nwin, a.packed, a.st, a.fwd,
-                           a.wmax, a.mark, table_bytes(ix));
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(lr_walk_kernel, dim3((unsigned)a.nwin), dim3(kLrWin), 0, s, mode, min_len, off, (long long)N, a.st, a.fwd, a.wmax,
-                       a.mark, a.bst, a.jc);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(lr_chain_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, off, (long long)N, a.st, a.jc, a.entry, a.base,
-                       a.cnt);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(compact_block_sums, dim3((unsigned)a.nblocks), dim3(kScanBlock), 0, s, a.cnt, (long long)N, 0x7fffffff, a.sums);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(scan_block_sums_kernel, dim3(1), dim3(kScanBlock), 0, s, a.sums, a.nblocks);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(lr_offsets_kernel, dim3((unsigned)a.nblocks), dim3(kScanBlock), 0, s, a.cnt, (long long)N, a.sums, a.nblocks,
-                       reinterpret_cast<long long *>(d_offsets));
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(lr_emit_kernel, dim3((unsigned)((a.nwin + 255) / 256)), dim3(256), 0, s, ix->dev, mode, min_len, off, (long long)N,
-                       a.nwin, a.packed, a.fwd, a.bst, a.entry, a.base, reinterpret_cast<const long long *>(d_offsets),
-                       reinterpret_cast<int4 *>(d_rows), (long long)out_cap_rows);
-    HIP_TRY(hipGetLastError());
+        LAUNCH(lr_fwd_kernel<false>, fgrid, fblock, 0, s, ix->dev, mode, off, (long long)N, a.nwin, a.packed, a.st, a.fwd,
+               a.wmax, a.mark, table_bytes(ix));
+    LAUNCH(lr_walk_kernel, dim3((unsigned)a.nwin), dim3(kLrWin), 0, s, mode, min_len, off, (long long)N, a.st, a.fwd, a.wmax,
+           a.mark, a.bst, a.jc);
+    LAUNCH(lr_chain_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, off, (long long)N, a.st, a.jc, a.entry, a.base,
+           a.cnt);
+    int rc = launch_compact(a.cnt, nullptr, N, 0x7fffffff, d_offsets, nullptr, 0, a.sums, stream);
+    if (rc) return rc;
+    LAUNCH(lr_emit_kernel, dim3((unsigned)((a.nwin + 255) / 256)), dim3(256), 0, s, ix->dev, mode, min_len, off, (long long)N,
+           a.nwin, a.packed, a.fwd, a.bst, a.entry, a.base, reinterpret_cast<const long long *>(d_offsets),
+           reinterpret_cast<int4 *>(d_rows), (long long)out_cap_rows);
     if (d_status) HIP_TRY(hipMemcpyAsync(d_status, a.st, N * 4, hipMemcpyDeviceToDevice, s));
     return GENIE_OK;
 }

@@ -295,23 +295,28 @@ __global__ void __launch_bounds__(256) split_remap_kernel(SplitPass ps, const lo
     }
 }
 
-// Workspace of the split call: the totals and segment scan for N reads, then one pass area (sized below).
-inline int64_t split_fixed_bytes(int64_t N)
+// Workspace of the split call: the totals and segment scan for N reads, then one pass area (below).
+struct SplitFixedArea {
+    unsigned long long *totals;      // K_S1's totals and K_S0's flags
+    int32_t *nseg;
+    unsigned long long *gsum;
+    long long *segoff;
+};
+
+inline int64_t split_fixed_layout(uint8_t *base, int64_t N, SplitFixedArea *a)
 {
-    const int64_t groups = (N + kSplitGroup - 1) / kSplitGroup;
-    return 256 + ws_align(N * 4) + ws_align((groups + 1) * 8) + ws_align((N + 1) * 8);
+    Carver c{base};
+    c.take(a->totals, 256);
+    c.take(a->nseg, N * 4);
+    c.take(a->gsum, ((N + kSplitGroup - 1) / kSplitGroup + 1) * 8);
+    c.take(a->segoff, (N + 1) * 8);
+    return c.at;
 }
 
 inline int split_gstride(int max_len) { return std::max(16, (max_len + 15) & ~15); }
 
 // a pass of C segments of at most max_len bases: segment table, segment status, the pass's CSR offsets, the gathered
 // bases and the find_smems workspace of the batch
-inline int64_t split_pass_bytes(int64_t C, int max_len)
-{
-    return 4 * ws_align(C * 4) + ws_align((C + 1) * 8) + ws_align(C * (int64_t)split_gstride(max_len) + 256) +
-           workspace_bytes_for(C, max_len);
-}
-
 struct SplitPassArea {
     int32_t *seg_read, *seg_start, *seg_len, *seg_status;
     long long *local_off;
@@ -320,29 +325,27 @@ struct SplitPassArea {
     int64_t csr_ws_bytes;
 };
 
-inline void carve_pass(uint8_t *p, int64_t C, int max_len, SplitPassArea *a)
+inline int64_t split_pass_layout(uint8_t *base, int64_t C, int max_len, SplitPassArea *a)
 {
-    a->seg_read = reinterpret_cast<int32_t *>(p);
-    p += ws_align(C * 4);
-    a->seg_start = reinterpret_cast<int32_t *>(p);
-    p += ws_align(C * 4);
-    a->seg_len = reinterpret_cast<int32_t *>(p);
-    p += ws_align(C * 4);
-    a->seg_status = reinterpret_cast<int32_t *>(p);
-    p += ws_align(C * 4);
-    a->local_off = reinterpret_cast<long long *>(p);
-    p += ws_align((C + 1) * 8);
-    a->gbuf = p;
-    p += ws_align(C * (int64_t)split_gstride(max_len) + 256);
-    a->csr_ws = p;
-    a->csr_ws_bytes = workspace_bytes_for(C, max_len);
+    Carver c{base};
+    c.take(a->seg_read, C * 4);
+    c.take(a->seg_start, C * 4);
+    c.take(a->seg_len, C * 4);
+    c.take(a->seg_status, C * 4);
+    c.take(a->local_off, (C + 1) * 8);
+    c.take(a->gbuf, C * (int64_t)split_gstride(max_len) + 256);
+    a->csr_ws_bytes = find_smems_workspace_bytes(C, max_len);
+    c.take(a->csr_ws, a->csr_ws_bytes);
+    return c.at;
 }
 
 }  // namespace
 
 int64_t find_smems_split_workspace_bytes(int64_t N, int32_t max_len)
 {
-    return split_fixed_bytes(N) + split_pass_bytes(std::max<int64_t>(N, 1), max_len);
+    SplitFixedArea f;
+    SplitPassArea a;
+    return split_fixed_layout(nullptr, N, &f) + split_pass_layout(nullptr, std::max<int64_t>(N, 1), max_len, &a);
 }
 
 int launch_find_smems_split(const genie_index *ix, const uint8_t *d_reads, const int32_t *d_lens, int64_t N, int32_t stride,
@@ -354,26 +357,19 @@ int launch_find_smems_split(const genie_index *ix, const uint8_t *d_reads, const
         HIP_TRY(hipMemsetAsync(d_offsets, 0, 8, s));
         return GENIE_OK;
     }
-    uint8_t *p = reinterpret_cast<uint8_t *>(d_ws);
-    unsigned long long *totals = reinterpret_cast<unsigned long long *>(p);
-    p += 256;
-    int32_t *nseg = reinterpret_cast<int32_t *>(p);
-    p += ws_align(N * 4);
+    SplitFixedArea f;
+    const int64_t fixed = split_fixed_layout(static_cast<uint8_t *>(d_ws), N, &f);
+    uint8_t *p = static_cast<uint8_t *>(d_ws) + fixed;        // the pass area
+    const int64_t pass_avail = ws_bytes - fixed;
     const long long groups = (N + kSplitGroup - 1) / kSplitGroup;
-    unsigned long long *gsum = reinterpret_cast<unsigned long long *>(p);
-    p += ws_align((groups + 1) * 8);
-    long long *segoff = reinterpret_cast<long long *>(p);
-    p += ws_align((N + 1) * 8);
-    const int64_t pass_avail = ws_bytes - split_fixed_bytes(N);
 
     const int cus = ix->num_cus > 0 ? ix->num_cus : 256;
-    HIP_TRY(hipMemsetAsync(totals, 0, 40, s));
+    HIP_TRY(hipMemsetAsync(f.totals, 0, 40, s));
     if (fixed_len > 0) {                                       // fast path: no break and no empty read -> the reads are the batch
-        unsigned int *flags = reinterpret_cast<unsigned int *>(totals + 4);
+        unsigned int *flags = reinterpret_cast<unsigned int *>(f.totals + 4);
         const long long work = std::max<long long>(N, N * (long long)stride / 16);
-        hipLaunchKernelGGL(split_check_kernel, dim3((unsigned)std::max<long long>(1, std::min<long long>((work + 255) / 256, (long long)cus * 8))),
-                           dim3(256), 0, s, ix->dev, d_reads, d_lens, (long long)N, stride, fixed_len, flags);
-        HIP_TRY(hipGetLastError());
+        LAUNCH(split_check_kernel, dim3((unsigned)std::max<long long>(1, std::min<long long>((work + 255) / 256, (long long)cus * 8))),
+               dim3(256), 0, s, ix->dev, d_reads, d_lens, (long long)N, stride, fixed_len, flags);
         unsigned int fl = 0;
         HIP_TRY(hipMemcpyAsync(&fl, flags, 4, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
@@ -382,11 +378,10 @@ int launch_find_smems_split(const genie_index *ix, const uint8_t *d_reads, const
             return launch_find_smems_csr(ix, GENIE_MODE_BWA, d_reads, d_lens, N, stride, fixed_len, min_len, d_offsets, d_rows,
                                          out_cap_rows, d_status, p, pass_avail, stream);
     }
-    hipLaunchKernelGGL(split_count_kernel, dim3((unsigned)std::min<long long>(groups, (long long)cus * 8)), dim3(kSplitWaves * 64), 0, s,
-                       ix->dev, d_reads, d_lens, (long long)N, stride, fixed_len, nseg, gsum, totals);
-    HIP_TRY(hipGetLastError());
+    LAUNCH(split_count_kernel, dim3((unsigned)std::min<long long>(groups, (long long)cus * 8)), dim3(kSplitWaves * 64), 0, s,
+           ix->dev, d_reads, d_lens, (long long)N, stride, fixed_len, f.nseg, f.gsum, f.totals);
     unsigned long long tot[3];
-    HIP_TRY(hipMemcpyAsync(tot, totals, sizeof(tot), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(tot, f.totals, sizeof(tot), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     if (tot[kSplitBadLen]) return GENIE_E_INVALID;             // a length outside [0, fixed_len]
 
@@ -399,41 +394,37 @@ int launch_find_smems_split(const genie_index *ix, const uint8_t *d_reads, const
     const int M = (int)tot[kSplitLongest];
     // segments per pass: as many as the workspace holds at this longest segment (at least N: the caller sized it for N reads
     // of fixed_len >= M bases)
+    SplitPassArea a;
     long long C = std::max<long long>(N, 1);
     {
         long long lo = C, hi = S;
         while (lo < hi) {
             const long long mid = lo + (hi - lo + 1) / 2;
-            if (split_pass_bytes(mid, M) <= pass_avail) lo = mid; else hi = mid - 1;
+            if (split_pass_layout(nullptr, mid, M, &a) <= pass_avail) lo = mid; else hi = mid - 1;
         }
         C = std::min(lo, S);
     }
-    hipLaunchKernelGGL(scan_block_sums_kernel, dim3(1), dim3(kScanBlock), 0, s, gsum, groups);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(split_offsets_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, nseg, gsum, (long long)N, segoff);
-    HIP_TRY(hipGetLastError());
+    LAUNCH(scan_block_sums_kernel, dim3(1), dim3(kScanBlock), 0, s, f.gsum, groups);
+    LAUNCH(split_offsets_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, f.nseg, f.gsum, (long long)N, f.segoff);
 
-    SplitPassArea a;
-    carve_pass(p, C, M, &a);
+    split_pass_layout(p, C, M, &a);
     long long row0 = 0;
     for (long long p0 = 0; p0 < S; p0 += C) {
         const long long p1 = std::min(S, p0 + C);
         const bool last = p1 == S;
         SplitPass ps{p0, p1, a.seg_read, a.seg_start, a.seg_len, a.gbuf, split_gstride(M)};
-        hipLaunchKernelGGL(split_fill_kernel, dim3((unsigned)((N + kSplitWaves - 1) / kSplitWaves)), dim3(kSplitWaves * 64), 0, s,
-                           ix->dev, d_reads, d_lens, (long long)N, stride, fixed_len, segoff, ps);
-        HIP_TRY(hipGetLastError());
+        LAUNCH(split_fill_kernel, dim3((unsigned)((N + kSplitWaves - 1) / kSplitWaves)), dim3(kSplitWaves * 64), 0, s,
+               ix->dev, d_reads, d_lens, (long long)N, stride, fixed_len, f.segoff, ps);
         const long long cap_left = std::max(0ll, (long long)out_cap_rows - row0);
         int rc = launch_find_smems_csr(ix, GENIE_MODE_BWA, a.gbuf, a.seg_len, p1 - p0, ps.gstride, M, min_len, reinterpret_cast<int64_t *>(a.local_off),
                                        cap_left > 0 ? d_rows + 4 * row0 : d_rows, cap_left, a.seg_status, a.csr_ws,
                                        a.csr_ws_bytes, stream);
         if (rc) return rc;
         const long long threads = std::max(p1 - p0, (long long)N);
-        hipLaunchKernelGGL(split_remap_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, ps,
-                           static_cast<const long long *>(a.local_off), static_cast<const int32_t *>(a.seg_status), row0,
-                           reinterpret_cast<int4 *>(d_rows), (long long)out_cap_rows, static_cast<const long long *>(segoff),
-                           (long long)N, last, reinterpret_cast<long long *>(d_offsets), d_status);
-        HIP_TRY(hipGetLastError());
+        LAUNCH(split_remap_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, ps,
+               static_cast<const long long *>(a.local_off), static_cast<const int32_t *>(a.seg_status), row0,
+               reinterpret_cast<int4 *>(d_rows), (long long)out_cap_rows, static_cast<const long long *>(f.segoff),
+               (long long)N, last, reinterpret_cast<long long *>(d_offsets), d_status);
         if (!last) {
             long long pass_rows = 0;
             HIP_TRY(hipMemcpyAsync(&pass_rows, a.local_off + (p1 - p0), 8, hipMemcpyDeviceToHost, s));
