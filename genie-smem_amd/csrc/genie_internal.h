@@ -367,6 +367,10 @@ int launch_find_smems_csr(const genie_index *ix, int32_t mode, const uint8_t *d_
                           int64_t N, int32_t stride, int32_t fixed_len, int32_t min_len, int64_t *d_offsets,
                           int32_t *d_rows, int64_t out_cap_rows, int32_t *d_status, void *d_ws, int64_t ws_bytes,
                           void *stream);
+int64_t find_smems_both_workspace_bytes(int64_t N, int32_t max_len);
+int launch_find_smems_both(const genie_index *ix, int32_t mode, const uint8_t *d_reads, const int32_t *d_lens, int64_t N,
+                           int32_t stride, int32_t fixed_len, int32_t min_len, int64_t *d_offsets, int32_t *d_rows,
+                           int64_t out_cap_rows, int32_t *d_status, void *d_ws, int64_t ws_bytes, void *stream);
 int64_t find_smems_split_workspace_bytes(int64_t N, int32_t max_len);
 int launch_find_smems_split(const genie_index *ix, const uint8_t *d_reads, const int32_t *d_lens, int64_t N, int32_t stride,
                             int32_t fixed_len, int32_t min_len, int64_t *d_offsets, int32_t *d_rows, int64_t out_cap_rows,

@@ -767,6 +767,7 @@ struct Workspace {
     uint8_t *kj;         // N x kj_row emitted (start | end << shift) entries of 2 or 4 bytes
     int32_t *counts;     // used by the CSR entry point
     uint8_t *scan_tmp;   // the traversal blocks' sums and their scan (CSR entry point)
+    int32_t *vlens;      // genie_find_smems_both with lengths: the length of every strand-read
 };
 
 inline int64_t ws_align(int64_t x) { return (x + 255) & ~(int64_t)255; }
@@ -786,8 +787,8 @@ struct Carver {
 // block sums of the traversal kernels (CSR form): one 64-bit word per block; the smallest block holds 16 reads
 inline int64_t block_sums_bytes(int64_t N) { return (N / 16 + 3) * 8; }
 
-// the workspace of N reads of the shape `g`, and a 256-byte tail
-inline int64_t workspace_layout(uint8_t *base, int64_t N, const Geometry &g, Workspace *ws)
+// the workspace of N reads of the shape `g` (and `vlens_n` strand-read lengths), and a 256-byte tail
+inline int64_t workspace_layout(uint8_t *base, int64_t N, const Geometry &g, Workspace *ws, int64_t vlens_n = 0)
 {
     Carver c{base};
     c.take(ws->fwd, N * (int64_t)g.fwd_stride);
@@ -796,12 +797,13 @@ inline int64_t workspace_layout(uint8_t *base, int64_t N, const Geometry &g, Wor
     c.take(ws->kj, N * (int64_t)g.kj_row * (g.wide ? 4 : 2));
     c.take(ws->counts, N * 4);
     c.take(ws->scan_tmp, block_sums_bytes(N));
+    c.take(ws->vlens, vlens_n * 4);
     return c.at + 256;
 }
 
-inline int carve_workspace(void *d_ws, int64_t ws_bytes, int64_t N, const Geometry &g, Workspace *ws)
+inline int carve_workspace(void *d_ws, int64_t ws_bytes, int64_t N, const Geometry &g, Workspace *ws, int64_t vlens_n = 0)
 {
-    if (!d_ws || ws_bytes < workspace_layout(static_cast<uint8_t *>(d_ws), N, g, ws) || (reinterpret_cast<uintptr_t>(d_ws) & 255) != 0)
+    if (!d_ws || ws_bytes < workspace_layout(static_cast<uint8_t *>(d_ws), N, g, ws, vlens_n) || (reinterpret_cast<uintptr_t>(d_ws) & 255) != 0)
         return GENIE_E_CAPACITY;
     return GENIE_OK;
 }
@@ -820,6 +822,8 @@ struct CsrOut {
     uint8_t *counts8 = nullptr, *status8 = nullptr;
     int64_t *escapes = nullptr;
     int64_t cap_escapes = 0;
+    // genie_find_smems_both: N counts strand-reads (read N / 2 as given, then its reverse complement), built by K_A
+    bool both = false;
 };
 
 template <int MODE, bool WIDE>
@@ -832,12 +836,27 @@ int launch_pipeline(const genie_index *ix, const Geometry &g, const uint8_t *d_r
     const bool c16 = (ix->dev.flags & kFlagCompactTable) != 0;
     const long long mtab_bytes = table_bytes(ix);
     if (ix->ev_search_begin) HIP_TRY(hipEventRecord((hipEvent_t)ix->ev_search_begin, s));
-    if (WIDE) {
+    if (WIDE && csr.both) {
+        auto km = c16 ? match_table_long_both_kernel<true> : match_table_long_both_kernel<false>;
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(km), hipFuncAttributeMaxDynamicSharedMemorySize, g.lds));
+        LAUNCH(km, dim3(g.grid), dim3(g.block), g.lds, s, ix->dev, (int)MODE, d_reads, d_lens, (long long)N, stride,
+               fixed_len, reinterpret_cast<uint8_t *>(ws.fwd), g.fwd_stride, ws.qp, g.qp_recs, st,
+               std::max(g.max_len, 1), mtab_bytes, ix->opt_search_all | ix->opt_scheduling << 16, ix->num_cus > 0 ? ix->num_cus : 256,
+               ws.vlens);
+    } else if (WIDE) {
         auto km = c16 ? match_table_long_kernel<true> : match_table_long_kernel<false>;
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(km), hipFuncAttributeMaxDynamicSharedMemorySize, g.lds));
         LAUNCH(km, dim3(g.grid), dim3(g.block), g.lds, s, ix->dev, (int)MODE, d_reads, d_lens, (long long)N, stride,
                fixed_len, reinterpret_cast<uint8_t *>(ws.fwd), g.fwd_stride, ws.qp, g.qp_recs, st,
                std::max(g.max_len, 1), mtab_bytes, ix->opt_search_all | ix->opt_scheduling << 16, ix->num_cus > 0 ? ix->num_cus : 256);
+    } else if (csr.both) {
+        auto km = c16 ? (g.wps == 4 ? match_table_both_kernel<4, true> : match_table_both_kernel<6, true>)
+                      : (g.wps == 4 ? match_table_both_kernel<4, false> : match_table_both_kernel<8, false>);
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(km), hipFuncAttributeMaxDynamicSharedMemorySize, g.lds));
+        LAUNCH(km, dim3(g.grid), dim3(g.block), g.lds, s, ix->dev, (int)MODE, d_reads, d_lens, (long long)N, stride,
+               fixed_len, reinterpret_cast<uint8_t *>(ws.fwd), g.fwd_stride, ws.qp, g.qp_recs, g.qp_stride, st,
+               g.grp, std::max(g.max_len, 1), mtab_bytes, ix->opt_search_all | ix->opt_debug << 8 | ix->opt_scheduling << 16, ix->num_cus > 0 ? ix->num_cus : 256,
+               ws.vlens);
     } else {
         auto km = csr.packed ? (c16 ? (g.wps == 4 ? match_table_kernel<4, true, true> : match_table_kernel<6, true, true>)
                                     : (g.wps == 4 ? match_table_kernel<4, false, true> : match_table_kernel<8, false, true>))
@@ -850,6 +869,8 @@ int launch_pipeline(const genie_index *ix, const Geometry &g, const uint8_t *d_r
     }
     if (ix->ev_search_end) HIP_TRY(hipEventRecord((hipEvent_t)ix->ev_search_end, s));
     if (ix->opt_search_only) return GENIE_W_SEARCH_ONLY;   // timing experiments: no counts / offsets / rows were written
+    // both strands: K_B reads the strand-reads' lengths that K_A wrote (or fixed_len for all)
+    if (csr.both && d_lens) d_lens = ws.vlens;
     // the head of a read's (count, pairs) row: behind its packed-read records (short reads) or the kj row itself
     uint8_t *head = WIDE ? ws.kj : reinterpret_cast<uint8_t *>(ws.qp) + g.qp_recs * 16;
     const int head_stride = WIDE ? g.kj_row * 4 : g.qp_stride * 16;
@@ -918,7 +939,7 @@ int launch_find_mode(const genie_index *ix, const Geometry &g, const uint8_t *d_
                      int32_t cap, int32_t *d_status, void *d_ws, int64_t ws_bytes, const CsrOut &csr, hipStream_t s)
 {
     Workspace ws;
-    int rc = carve_workspace(d_ws, ws_bytes, N, g, &ws);
+    int rc = carve_workspace(d_ws, ws_bytes, N, g, &ws, csr.both ? N : 0);
     if (rc) return rc;
     if (g.wide)
         return launch_pipeline<MODE, true>(ix, g, d_reads, d_lens, N, stride, fixed_len, min_len, d_counts, d_slots, cap, d_status, ws, csr, s);
@@ -989,6 +1010,9 @@ static int launch_find_any(const genie_index *ix, int32_t mode, const uint8_t *d
 {
     Geometry g;
     // with ragged lengths `fixed_len` carries the maximum length (host contract)
+    // (genie_find_smems_both: N strand-reads, the group size unchanged -- an even group holds whole pairs; an odd one splits
+    // every other pair over two consecutive groups, which waves of the same block take, so the row is in its L2 either way.
+    // Rounding 5 reads of 150 bases down to 4 left a fifth of round 1's lanes idle.)
     int rc = plan_find_smems(ix, mode, fixed_len, N, &g);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
@@ -1028,6 +1052,31 @@ int launch_find_smems_csr(const genie_index *ix, int32_t mode, const uint8_t *d_
     csr.rows = d_rows;
     csr.cap_rows = out_cap_rows;
     return launch_find_any(ix, mode, d_reads, d_lens, N, stride, fixed_len, min_len, nullptr, nullptr, 0, d_status, d_ws,
+                           ws_bytes, csr, stream);
+}
+
+int64_t find_smems_both_workspace_bytes(int64_t N, int32_t max_len)
+{
+    Geometry g;
+    shape_for(max_len, &g);
+    Workspace ws;
+    return workspace_layout(nullptr, 2 * N, g, &ws, 2 * N);
+}
+
+int launch_find_smems_both(const genie_index *ix, int32_t mode, const uint8_t *d_reads, const int32_t *d_lens, int64_t N,
+                           int32_t stride, int32_t fixed_len, int32_t min_len, int64_t *d_offsets, int32_t *d_rows,
+                           int64_t out_cap_rows, int32_t *d_status, void *d_ws, int64_t ws_bytes, void *stream)
+{
+    if (N == 0) {
+        HIP_TRY(hipMemsetAsync(d_offsets, 0, 8, (hipStream_t)stream));
+        return GENIE_OK;
+    }
+    CsrOut csr;
+    csr.offsets = d_offsets;
+    csr.rows = d_rows;
+    csr.cap_rows = out_cap_rows;
+    csr.both = true;
+    return launch_find_any(ix, mode, d_reads, d_lens, 2 * N, stride, fixed_len, min_len, nullptr, nullptr, 0, d_status, d_ws,
                            ws_bytes, csr, stream);
 }
 

@@ -378,6 +378,45 @@ class GenieIndex:
                 return offsets, rows[:total], status
             cap_rows = total                      # capacity guess too small: rerun with the exact size
 
+    def find_smems_both(self, mode, reads, lens=None, min_len=1, rows_hint=None):
+        """SMEMs of both strands of every read (genie_find_smems_both) -> (offsets int64[2N+1], smems int32[S,4], status
+        int32[2N]).  Strand-read 2i is read i, 2i + 1 its reverse complement (packing.reverse_complement); the result is that
+        of find_smems on the interleaved batch [r0, rc(r0), r1, rc(r1), ...], with start / end of a strand-1 row positions in
+        the reverse-complemented read (forward coordinates: L - end, L - start).  reads: [N, stride] uint8 codes (device or
+        host: uploaded as uint8 codes)."""
+        self._need_device()
+        reads = self._as_dev(reads, torch.uint8)
+        if reads.dim() != 2:
+            raise ValueError("reads must be [N, stride]")
+        n_reads, stride = reads.shape
+        fixed = stride
+        if lens is not None:
+            lens = self._as_dev(lens, torch.int32)
+            fixed = int(lens.max().item()) if n_reads else 0
+            if fixed > stride or (n_reads and int(lens.min().item()) < 0):
+                raise ValueError("read length outside [0, stride]")
+        if stride == 0:
+            reads = torch.zeros((n_reads, 1), dtype=torch.uint8, device=self.device)
+            stride = 1
+        offsets = torch.empty(2 * n_reads + 1, dtype=torch.int64, device=self.device)
+        status = torch.empty(2 * n_reads, dtype=torch.int32, device=self.device)
+        ws_bytes = int(N.lib().genie_find_smems_both_workspace_bytes(n_reads, fixed))
+        if ws_bytes < 0:
+            raise N.GenieError(ws_bytes, "genie_find_smems_both_workspace_bytes")
+        ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=self.device)
+        cap_rows = int(rows_hint) if rows_hint else 2 * n_reads * max(8, fixed // 6)
+        while True:
+            rows = torch.empty((max(cap_rows, 1), 4), dtype=torch.int32, device=self.device)
+            with torch.cuda.device(self.device):
+                N.check(N.lib().genie_find_smems_both(self._h, N.MODES[mode], _ptr(reads), _ptr(lens), n_reads, stride, fixed,
+                                                      int(min_len), _ptr(offsets), _ptr(rows), rows.shape[0], _ptr(status),
+                                                      _ptr(ws), ws_bytes, _stream(self.device)),
+                        "genie_find_smems_both")
+            total = int(offsets[-1].item())
+            if total <= rows.shape[0]:
+                return offsets, rows[:total], status
+            cap_rows = total                      # capacity guess too small: rerun with the exact size
+
     def find_smems_split(self, reads, lens=None, min_len=1, rows_hint=None):
         """SMEMs of reads that may contain breaks (genie_find_smems_split) -> (offsets int64[N+1], smems int32[S,4], status).
         reads: [N, stride] uint8 codes on the device or the host (uploaded as uint8 codes: the 2-bit packed host path cannot

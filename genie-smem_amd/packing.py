@@ -82,3 +82,27 @@ def unpack_rows(counts8, rows8, escapes=None, row_bytes=8):
             raise ValueError("escape list does not cover the rows with a saturated span")
         rows[wide, 3] = esc[:, 1]
     return offsets, rows
+
+
+def reverse_complement(codes, lens=None):
+    """The reverse complement of every read: row i's first lens[i] codes (all of them without `lens`) reversed, each code c
+    mapped to c ^ 3 (3 - c on 0..3; a code > 3 stays > 3); bytes past a read's length are left as they are.  codes: uint8
+    [N, L] (or one read, [L]) -> a new array of the same shape.  Strand-read 2i + 1 of genie_find_smems_both is
+    reverse_complement(read i)."""
+    codes = np.asarray(codes, np.uint8)
+    if codes.ndim == 1:
+        return reverse_complement(codes[None, :], None if lens is None else np.asarray(lens).reshape(1))[0]
+    if codes.ndim != 2:
+        raise ValueError("reads must be [N, L]")
+    if lens is None:
+        return np.ascontiguousarray(codes[:, ::-1] ^ np.uint8(3))
+    lens = np.asarray(lens).reshape(-1)
+    if lens.shape[0] != codes.shape[0] or (lens.size and (int(lens.min()) < 0 or int(lens.max()) > codes.shape[1])):
+        raise ValueError("lens must hold one length in [0, L] per read")
+    out = np.array(codes, np.uint8, copy=True)
+    for length in np.unique(lens):                        # one slice per distinct length
+        length = int(length)
+        if length:
+            sel = np.nonzero(lens == length)[0]
+            out[sel, :length] = codes[sel, length - 1::-1] ^ np.uint8(3)
+    return out

@@ -63,14 +63,15 @@ class SMEM:
         ragged = len(enc) > 0 and int(lens.min()) != width
         return torch.as_tensor(mat).to(ix_dev), (torch.as_tensor(lens).to(ix_dev) if ragged else None)
 
-    def _find(self, mode, reads, lens, min_len):
-        K = self.lut.lut_size
+    def _mode_index(self, mode):
         if mode == "rmi":
             if self.rmi_lut is None:
                 self.rmi_lut = RMI_LUT.load("rmi_file.npz", matcher=self.matcher)     # cf. SMEM.py:207
-            ix = self.rmi_lut._index()
-        else:
-            ix = self.matcher.index(K)
+            return self.rmi_lut._index()
+        return self.matcher.index(self.lut.lut_size)
+
+    def _find(self, mode, reads, lens, min_len):
+        ix = self._mode_index(mode)
         if not isinstance(reads, torch.Tensor):
             # host inputs: 2-bit packed over the host link, 8-byte rows back (genie_find_smems_packed); results on the host
             codes, l2 = self._reads_codes(reads)
@@ -103,6 +104,15 @@ class SMEM:
         if lens is None and ragged:
             lens = ln
         return ix.find_smems_split(mat if width else mat[:, :0], lens, minimum_length)
+
+    def find_smems_both(self, reads, mode="lut", minimum_length=1, lens=None):
+        """SMEMs of both strands of every read in one call (genie_find_smems_both).  reads: list[str], or numpy / torch uint8
+        codes.  -> (offsets int64[2N+1], smems[S, 4], status int32[2N]) on the device: strand-read 2i is read i, 2i + 1 its
+        reverse complement, whose rows are those get_SMEMS / get_smems_lut / get_smems_rmi give for that reverse complement
+        (start / end in it; forward coordinates L - end, L - start).  Host inputs travel as uint8 codes."""
+        ix = self._mode_index(mode)
+        t, l2 = self._reads_tensor(reads)
+        return ix.find_smems_both(mode, t, lens if lens is not None else l2, minimum_length)
 
     def find_smems_long(self, reads, minimum_length=1, mode="bwa"):
         """SMEMs of reads of any length (genie_find_smems_long).  reads: list[str], or (bases, read_offsets) -- uint8 codes

@@ -251,6 +251,32 @@ int genie_find_smems_csr(const genie_index *ix, int32_t mode, const uint8_t *d_r
                          int32_t *d_rows, int64_t out_cap_rows, int32_t *d_status, void *d_workspace,
                          int64_t workspace_bytes, void *stream);
 
+/* SMEMs of both strands of every read in one call.  Inputs as genie_find_smems_csr: uint8 [N, stride] codes, d_lens (may
+ * be NULL: fixed_len for every read; with d_lens, fixed_len is the longest length), reads of at most GENIE_MAX_READ_LEN
+ * bases, every mode, min_len applied in BWA mode.  The output covers 2N strand-reads, interleaved: strand-read 2i + s is
+ * read i when s = 0 and its reverse complement rc(read i) when s = 1 (reversed, code c -> 3 - c).
+ *   d_offsets[2N+1]  offsets of the CSR rows;  d_rows  int32 rows (start, end, lo, hi), 16-byte aligned;
+ *   d_status[2N]     one GENIE_READ_* code per strand-read (may be NULL): a reference without T gives
+ *                    GENIE_READ_ABSENT_BASE on the reverse strand of a read that holds an A and GENIE_READ_OK on its forward one;
+ *   rows past out_cap_rows are dropped, d_offsets[2N] still holds the true total.
+ * Defining property: the output is byte for byte what genie_find_smems_csr returns for the batch
+ * [r0, rc(r0), r1, rc(r1), ...] with each length given twice.  The reverse complement is never written to memory: the
+ * match-statistics kernel builds it while packing the read.
+ * On strand 1, start / end are positions in the reverse-complemented read (the rows SMEM.get_SMEMS(rc(q), m) /
+ * get_smems_lut / get_smems_rmi give); in forward coordinates of a read of length L the SMEM covers
+ * [L - end, L - start).  The rows are left as they are.  The two strands' sets are computed independently: a
+ * reverse-strand SMEM contained in a forward one is not removed (as with two calls).
+ * d_workspace: 256-byte aligned, genie_find_smems_both_workspace_bytes(N, max_len) bytes with max_len >= fixed_len
+ * (at least genie_find_smems_workspace_bytes(2N, max_len)).  Argument checks come before the device check, so they hold on
+ * any handle: bad pointers or sizes (stride < fixed_len included) give GENIE_E_INVALID, fixed_len > GENIE_MAX_READ_LEN
+ * GENIE_E_TOO_LONG, a small or misaligned workspace GENIE_E_CAPACITY.  N = 0 writes d_offsets[0] = 0.  No stream
+ * synchronization.  The workspace size function returns GENIE_E_INVALID for negative arguments and GENIE_E_TOO_LONG
+ * above GENIE_MAX_READ_LEN. */
+int64_t genie_find_smems_both_workspace_bytes(int64_t N, int32_t max_len);
+int genie_find_smems_both(const genie_index *ix, int32_t mode, const uint8_t *d_reads, const int32_t *d_lens, int64_t N,
+                          int32_t stride, int32_t fixed_len, int32_t min_len, int64_t *d_offsets, int32_t *d_rows,
+                          int64_t out_cap_rows, int32_t *d_status, void *d_workspace, int64_t workspace_bytes, void *stream);
+
 /* SMEMs of reads that contain breaks (ambiguous bases such as N), where genie_find_smems* flag the whole read instead.
  * A break is a position whose code is > 3 (any byte 4..255) or whose base never occurs in the reference; a segment is a
  * maximal run of positions that are not breaks.  No exact match covers a break, so the SMEMs of a read are the union of
