@@ -310,6 +310,13 @@ static int ready(const genie_index *ix)
     return GENIE_OK;
 }
 
+// the tables an SMEM search of `mode` needs: the K-mer table (LUT / RMI) and the model (RMI)
+static int mode_tables(const genie_index *ix, int32_t mode)
+{
+    if (mode != GENIE_MODE_BWA && ix->dev.K < 1) return GENIE_E_NO_LUT;
+    return mode == GENIE_MODE_RMI && ix->dev.nlev < 1 ? GENIE_E_NO_MODEL : GENIE_OK;
+}
+
 int genie_sa_interval(const genie_index *ix, const uint8_t *d_pats, const int32_t *d_lens, int64_t N,
                       int32_t stride, int32_t fixed_len, int32_t *d_out_lohi, void *stream)
 {
@@ -343,11 +350,10 @@ int genie_find_smems(const genie_index *ix, int32_t mode, const uint8_t *d_reads
         return GENIE_E_INVALID;
     if (mode < GENIE_MODE_BWA || mode > GENIE_MODE_RMI) return GENIE_E_INVALID;
     if (fixed_len > GENIE_MAX_READ_LEN) return GENIE_E_TOO_LONG;
-    if (mode != GENIE_MODE_BWA && ix->dev.K < 1) return GENIE_E_NO_LUT;
-    if (mode == GENIE_MODE_RMI && ix->dev.nlev < 1) return GENIE_E_NO_MODEL;
+    if ((rc = mode_tables(ix, mode))) return rc;
     if ((reinterpret_cast<uintptr_t>(d_slots) & 15) != 0) return GENIE_E_INVALID;
-    return launch_find_smems(ix, mode, d_reads, d_lens, N, stride, fixed_len, min_len, d_counts, d_slots, cap,
-                             d_status, d_workspace, workspace_bytes, stream);
+    return launch_find_smems(ix, mode, {d_reads, d_lens, N, stride, fixed_len, min_len, d_status, d_workspace, workspace_bytes},
+                             d_counts, d_slots, cap, stream);
 }
 
 int genie_find_smems_csr(const genie_index *ix, int32_t mode, const uint8_t *d_reads, const int32_t *d_lens,
@@ -361,11 +367,10 @@ int genie_find_smems_csr(const genie_index *ix, int32_t mode, const uint8_t *d_r
         return GENIE_E_INVALID;
     if (mode < GENIE_MODE_BWA || mode > GENIE_MODE_RMI) return GENIE_E_INVALID;
     if (fixed_len > GENIE_MAX_READ_LEN) return GENIE_E_TOO_LONG;
-    if (mode != GENIE_MODE_BWA && ix->dev.K < 1) return GENIE_E_NO_LUT;
-    if (mode == GENIE_MODE_RMI && ix->dev.nlev < 1) return GENIE_E_NO_MODEL;
+    if ((rc = mode_tables(ix, mode))) return rc;
     if ((reinterpret_cast<uintptr_t>(d_rows) & 15) != 0) return GENIE_E_INVALID;
-    return launch_find_smems_csr(ix, mode, d_reads, d_lens, N, stride, fixed_len, min_len, d_offsets, d_rows, out_cap_rows,
-                                 d_status, d_workspace, workspace_bytes, stream);
+    return launch_find_smems_csr(ix, mode, {d_reads, d_lens, N, stride, fixed_len, min_len, d_status, d_workspace, workspace_bytes},
+                                 d_offsets, d_rows, out_cap_rows, stream);
 }
 
 int64_t genie_find_smems_both_workspace_bytes(int64_t N, int32_t max_len)
@@ -391,11 +396,9 @@ int genie_find_smems_both(const genie_index *ix, int32_t mode, const uint8_t *d_
     if (N > 0 && ((reinterpret_cast<uintptr_t>(d_workspace) & 255) != 0 || workspace_bytes < find_smems_both_workspace_bytes(N, fixed_len)))
         return GENIE_E_CAPACITY;
     int rc = ready(ix);
-    if (rc) return rc;
-    if (mode != GENIE_MODE_BWA && ix->dev.K < 1) return GENIE_E_NO_LUT;
-    if (mode == GENIE_MODE_RMI && ix->dev.nlev < 1) return GENIE_E_NO_MODEL;
-    return launch_find_smems_both(ix, mode, d_reads, d_lens, N, stride, fixed_len, min_len, d_offsets, d_rows, out_cap_rows, d_status,
-                                  d_workspace, workspace_bytes, stream);
+    if (rc || (rc = mode_tables(ix, mode))) return rc;
+    return launch_find_smems_both(ix, mode, {d_reads, d_lens, N, stride, fixed_len, min_len, d_status, d_workspace, workspace_bytes},
+                                  d_offsets, d_rows, out_cap_rows, stream);
 }
 
 int64_t genie_find_smems_split_workspace_bytes(int64_t N, int32_t max_len)
@@ -441,9 +444,7 @@ int genie_find_smems_long(const genie_index *ix, int32_t mode, const uint8_t *d_
     if ((reinterpret_cast<uintptr_t>(d_rows) & 15) != 0 || (reinterpret_cast<uintptr_t>(d_workspace) & 255) != 0) return GENIE_E_INVALID;
     if (N > 0 && workspace_bytes < find_smems_long_workspace_bytes(N, total_bases)) return GENIE_E_CAPACITY;
     int rc = ready(ix);
-    if (rc) return rc;
-    if (mode != GENIE_MODE_BWA && ix->dev.K < 1) return GENIE_E_NO_LUT;
-    if (mode == GENIE_MODE_RMI && ix->dev.nlev < 1) return GENIE_E_NO_MODEL;
+    if (rc || (rc = mode_tables(ix, mode))) return rc;
     return launch_find_smems_long(ix, mode, d_bases, d_read_offsets, N, total_bases, max_len, min_len, d_offsets, d_rows, out_cap_rows,
                                   d_status, d_workspace, workspace_bytes, stream);
 }
@@ -465,10 +466,9 @@ static int find_smems_packed_any(const genie_index *ix, int32_t mode, const uint
     if ((reinterpret_cast<uintptr_t>(d_reads2bit) & 3) != 0 || (reinterpret_cast<uintptr_t>(d_rows) & (row_bytes == 6 ? 1 : 7)) != 0 ||
         (reinterpret_cast<uintptr_t>(d_totals) & 7) != 0)
         return GENIE_E_INVALID;
-    if (mode != GENIE_MODE_BWA && ix->dev.K < 1) return GENIE_E_NO_LUT;
-    if (mode == GENIE_MODE_RMI && ix->dev.nlev < 1) return GENIE_E_NO_MODEL;
-    return launch_find_smems_packed(ix, mode, d_reads2bit, d_lens, N, stride_bytes, fixed_len, min_len, d_counts8, d_status8,
-                                    d_rows, out_cap_rows, d_totals, d_escapes, cap_escapes, d_workspace, workspace_bytes, stream, row_bytes);
+    if ((rc = mode_tables(ix, mode))) return rc;
+    return launch_find_smems_packed(ix, mode, {d_reads2bit, d_lens, N, stride_bytes, fixed_len, min_len, nullptr, d_workspace, workspace_bytes},
+                                    d_counts8, d_status8, d_rows, out_cap_rows, d_totals, d_escapes, cap_escapes, stream, row_bytes);
 }
 
 int genie_find_smems_packed(const genie_index *ix, int32_t mode, const uint8_t *d_reads2bit, const int32_t *d_lens, int64_t N,

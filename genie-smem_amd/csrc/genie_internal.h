@@ -359,18 +359,25 @@ int launch_sa_interval(const genie_index *ix, const uint8_t *d_pats, const int32
                        int32_t stride, int32_t fixed_len, int32_t *d_out, void *stream);
 int launch_seed_lookup(const genie_index *ix, int32_t mode, const uint8_t *d_kmers, int64_t N, int32_t *d_out,
                        double *d_pred, void *stream);
-int launch_find_smems(const genie_index *ix, int32_t mode, const uint8_t *d_reads, const int32_t *d_lens,
-                      int64_t N, int32_t stride, int32_t fixed_len, int32_t min_len, int32_t *d_counts,
-                      int32_t *d_slots, int32_t cap, int32_t *d_status, void *d_ws, int64_t ws_bytes, void *stream);
+// The batch of an SMEM call: N reads of `stride` bytes (2-bit packed for genie_find_smems_packed), their lengths or null
+// (`fixed_len` is then the length of all, else the longest), a status per read or null, and the caller's workspace.
+struct FindBatch {
+    const uint8_t *reads;
+    const int32_t *lens;
+    int64_t N;
+    int32_t stride, fixed_len, min_len;
+    int32_t *status;
+    void *ws;
+    int64_t ws_bytes;
+};
+int launch_find_smems(const genie_index *ix, int32_t mode, const FindBatch &b, int32_t *d_counts, int32_t *d_slots, int32_t cap,
+                      void *stream);
 int64_t find_smems_workspace_bytes(int64_t N, int32_t max_len);
-int launch_find_smems_csr(const genie_index *ix, int32_t mode, const uint8_t *d_reads, const int32_t *d_lens,
-                          int64_t N, int32_t stride, int32_t fixed_len, int32_t min_len, int64_t *d_offsets,
-                          int32_t *d_rows, int64_t out_cap_rows, int32_t *d_status, void *d_ws, int64_t ws_bytes,
-                          void *stream);
+int launch_find_smems_csr(const genie_index *ix, int32_t mode, const FindBatch &b, int64_t *d_offsets, int32_t *d_rows,
+                          int64_t out_cap_rows, void *stream);
 int64_t find_smems_both_workspace_bytes(int64_t N, int32_t max_len);
-int launch_find_smems_both(const genie_index *ix, int32_t mode, const uint8_t *d_reads, const int32_t *d_lens, int64_t N,
-                           int32_t stride, int32_t fixed_len, int32_t min_len, int64_t *d_offsets, int32_t *d_rows,
-                           int64_t out_cap_rows, int32_t *d_status, void *d_ws, int64_t ws_bytes, void *stream);
+int launch_find_smems_both(const genie_index *ix, int32_t mode, const FindBatch &b, int64_t *d_offsets, int32_t *d_rows,
+                           int64_t out_cap_rows, void *stream);
 int64_t find_smems_split_workspace_bytes(int64_t N, int32_t max_len);
 int launch_find_smems_split(const genie_index *ix, const uint8_t *d_reads, const int32_t *d_lens, int64_t N, int32_t stride,
                             int32_t fixed_len, int32_t min_len, int64_t *d_offsets, int32_t *d_rows, int64_t out_cap_rows,
@@ -379,10 +386,9 @@ int64_t find_smems_long_workspace_bytes(int64_t N, int64_t total_bases);
 int launch_find_smems_long(const genie_index *ix, int32_t mode, const uint8_t *d_bases, const int64_t *d_read_offsets, int64_t N,
                            int64_t total_bases, int64_t max_len, int32_t min_len, int64_t *d_offsets, int32_t *d_rows,
                            int64_t out_cap_rows, int32_t *d_status, void *d_ws, int64_t ws_bytes, void *stream);
-int launch_find_smems_packed(const genie_index *ix, int32_t mode, const uint8_t *d_reads2, const int32_t *d_lens, int64_t N,
-                             int32_t stride_bytes, int32_t fixed_len, int32_t min_len, uint8_t *d_counts8, uint8_t *d_status8,
+int launch_find_smems_packed(const genie_index *ix, int32_t mode, const FindBatch &b, uint8_t *d_counts8, uint8_t *d_status8,
                              void *d_rows8, int64_t out_cap_rows, int64_t *d_totals, int64_t *d_escapes, int64_t cap_escapes,
-                             void *d_ws, int64_t ws_bytes, void *stream, int row_bytes = 8);
+                             void *stream, int row_bytes = 8);
 int launch_compact(const int32_t *d_counts, const int32_t *d_slots, int64_t N, int32_t cap, int64_t *d_offsets,
                    int32_t *d_out, int64_t out_cap_rows, void *d_tmp, void *stream);
 int64_t compact_tmp_bytes(int64_t N);

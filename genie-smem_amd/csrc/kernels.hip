@@ -811,8 +811,12 @@ inline int carve_workspace(void *d_ws, int64_t ws_bytes, int64_t N, const Geomet
 // long reads: lanes per read of the traversal kernel by batch size (measured, from-ref reads on the 100 kb reference: below)
 constexpr long long kLongTwoLaneReads = 32768;
 
-struct CsrOut {
-    int64_t *offsets = nullptr;      // non-null => write CSR rows to `rows`, else slots
+// One SMEM call: the batch, and where its output goes.  Without `offsets` K_C writes slots (`counts`, `slots`, `cap`); with
+// it CSR rows (`rows`, `cap_rows`).
+struct FindRequest : FindBatch {
+    int32_t *counts = nullptr, *slots = nullptr;
+    int32_t cap = 0;
+    int64_t *offsets = nullptr;
     int32_t *rows = nullptr;
     int64_t cap_rows = 0;
     // genie_find_smems_packed: 2-bit packed reads in; 8-byte rows, a count byte and a status byte per read out.
@@ -824,59 +828,65 @@ struct CsrOut {
     int64_t cap_escapes = 0;
     // genie_find_smems_both: N counts strand-reads (read N / 2 as given, then its reverse complement), built by K_A
     bool both = false;
+
+    explicit FindRequest(const FindBatch &b) : FindBatch(b) {}
 };
 
-template <int MODE, bool WIDE>
-int launch_pipeline(const genie_index *ix, const Geometry &g, const uint8_t *d_reads, const int32_t *d_lens, int64_t N,
-                    int32_t stride, int32_t fixed_len, int32_t min_len, int32_t *d_counts, int32_t *d_slots, int32_t cap,
-                    int32_t *d_status, const Workspace &ws, const CsrOut &csr, hipStream_t s)
+// K_A: every instance asks for more dynamic LDS than the default limit
+template <class Kernel, class... Args>
+int launch_match_table(Kernel km, const Geometry &g, hipStream_t s, Args... args)
 {
-    int32_t *st = d_status ? d_status : ws.status;
-    int32_t *cnt = d_counts ? d_counts : ws.counts;
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(km), hipFuncAttributeMaxDynamicSharedMemorySize, g.lds));
+    LAUNCH(km, dim3(g.grid), dim3(g.block), g.lds, s, args...);
+    return GENIE_OK;
+}
+
+template <int MODE, bool WIDE>
+int launch_pipeline(const genie_index *ix, const Geometry &g, const FindRequest &r, const Workspace &ws, hipStream_t s)
+{
+    int32_t *st = r.status ? r.status : ws.status;
+    int32_t *cnt = r.counts ? r.counts : ws.counts;
     const bool c16 = (ix->dev.flags & kFlagCompactTable) != 0;
     const long long mtab_bytes = table_bytes(ix);
+    const int cus = ix->num_cus > 0 ? ix->num_cus : 256;
+    const int max_len = std::max(g.max_len, 1);
+    const int long_flags = ix->opt_search_all | ix->opt_scheduling << 16, flags = long_flags | ix->opt_debug << 8;
     if (ix->ev_search_begin) HIP_TRY(hipEventRecord((hipEvent_t)ix->ev_search_begin, s));
-    if (WIDE && csr.both) {
-        auto km = c16 ? match_table_long_both_kernel<true> : match_table_long_both_kernel<false>;
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(km), hipFuncAttributeMaxDynamicSharedMemorySize, g.lds));
-        LAUNCH(km, dim3(g.grid), dim3(g.block), g.lds, s, ix->dev, (int)MODE, d_reads, d_lens, (long long)N, stride,
-               fixed_len, reinterpret_cast<uint8_t *>(ws.fwd), g.fwd_stride, ws.qp, g.qp_recs, st,
-               std::max(g.max_len, 1), mtab_bytes, ix->opt_search_all | ix->opt_scheduling << 16, ix->num_cus > 0 ? ix->num_cus : 256,
-               ws.vlens);
-    } else if (WIDE) {
-        auto km = c16 ? match_table_long_kernel<true> : match_table_long_kernel<false>;
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(km), hipFuncAttributeMaxDynamicSharedMemorySize, g.lds));
-        LAUNCH(km, dim3(g.grid), dim3(g.block), g.lds, s, ix->dev, (int)MODE, d_reads, d_lens, (long long)N, stride,
-               fixed_len, reinterpret_cast<uint8_t *>(ws.fwd), g.fwd_stride, ws.qp, g.qp_recs, st,
-               std::max(g.max_len, 1), mtab_bytes, ix->opt_search_all | ix->opt_scheduling << 16, ix->num_cus > 0 ? ix->num_cus : 256);
-    } else if (csr.both) {
-        auto km = c16 ? (g.wps == 4 ? match_table_both_kernel<4, true> : match_table_both_kernel<6, true>)
-                      : (g.wps == 4 ? match_table_both_kernel<4, false> : match_table_both_kernel<8, false>);
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(km), hipFuncAttributeMaxDynamicSharedMemorySize, g.lds));
-        LAUNCH(km, dim3(g.grid), dim3(g.block), g.lds, s, ix->dev, (int)MODE, d_reads, d_lens, (long long)N, stride,
-               fixed_len, reinterpret_cast<uint8_t *>(ws.fwd), g.fwd_stride, ws.qp, g.qp_recs, g.qp_stride, st,
-               g.grp, std::max(g.max_len, 1), mtab_bytes, ix->opt_search_all | ix->opt_debug << 8 | ix->opt_scheduling << 16, ix->num_cus > 0 ? ix->num_cus : 256,
-               ws.vlens);
-    } else {
-        auto km = csr.packed ? (c16 ? (g.wps == 4 ? match_table_kernel<4, true, true> : match_table_kernel<6, true, true>)
-                                    : (g.wps == 4 ? match_table_kernel<4, false, true> : match_table_kernel<8, false, true>))
-                             : (c16 ? (g.wps == 4 ? match_table_kernel<4, true, false> : match_table_kernel<6, true, false>)
-                                    : (g.wps == 4 ? match_table_kernel<4, false, false> : match_table_kernel<8, false, false>));
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(km), hipFuncAttributeMaxDynamicSharedMemorySize, g.lds));
-        LAUNCH(km, dim3(g.grid), dim3(g.block), g.lds, s, ix->dev, (int)MODE, d_reads, d_lens, (long long)N, stride,
-               fixed_len, reinterpret_cast<uint8_t *>(ws.fwd), g.fwd_stride, ws.qp, g.qp_recs, g.qp_stride, st,
-               g.grp, std::max(g.max_len, 1), mtab_bytes, ix->opt_search_all | ix->opt_debug << 8 | ix->opt_scheduling << 16, ix->num_cus > 0 ? ix->num_cus : 256);
-    }
+    int rc;
+    if (WIDE && r.both)
+        rc = launch_match_table(c16 ? match_table_long_both_kernel<true> : match_table_long_both_kernel<false>, g, s, ix->dev,
+                                (int)MODE, r.reads, r.lens, (long long)r.N, r.stride, r.fixed_len, reinterpret_cast<uint8_t *>(ws.fwd),
+                                g.fwd_stride, ws.qp, g.qp_recs, st, max_len, mtab_bytes, long_flags, cus, ws.vlens);
+    else if (WIDE)
+        rc = launch_match_table(c16 ? match_table_long_kernel<true> : match_table_long_kernel<false>, g, s, ix->dev, (int)MODE,
+                                r.reads, r.lens, (long long)r.N, r.stride, r.fixed_len, reinterpret_cast<uint8_t *>(ws.fwd),
+                                g.fwd_stride, ws.qp, g.qp_recs, st, max_len, mtab_bytes, long_flags, cus);
+    else if (r.both)
+        rc = launch_match_table(c16 ? (g.wps == 4 ? match_table_both_kernel<4, true> : match_table_both_kernel<6, true>)
+                                    : (g.wps == 4 ? match_table_both_kernel<4, false> : match_table_both_kernel<8, false>),
+                                g, s, ix->dev, (int)MODE, r.reads, r.lens, (long long)r.N, r.stride, r.fixed_len,
+                                reinterpret_cast<uint8_t *>(ws.fwd), g.fwd_stride, ws.qp, g.qp_recs, g.qp_stride, st, g.grp,
+                                max_len, mtab_bytes, flags, cus, ws.vlens);
+    else
+        rc = launch_match_table(r.packed ? (c16 ? (g.wps == 4 ? match_table_kernel<4, true, true> : match_table_kernel<6, true, true>)
+                                                : (g.wps == 4 ? match_table_kernel<4, false, true> : match_table_kernel<8, false, true>))
+                                         : (c16 ? (g.wps == 4 ? match_table_kernel<4, true, false> : match_table_kernel<6, true, false>)
+                                                : (g.wps == 4 ? match_table_kernel<4, false, false> : match_table_kernel<8, false, false>)),
+                                g, s, ix->dev, (int)MODE, r.reads, r.lens, (long long)r.N, r.stride, r.fixed_len,
+                                reinterpret_cast<uint8_t *>(ws.fwd), g.fwd_stride, ws.qp, g.qp_recs, g.qp_stride, st, g.grp,
+                                max_len, mtab_bytes, flags, cus);
+    if (rc) return rc;
     if (ix->ev_search_end) HIP_TRY(hipEventRecord((hipEvent_t)ix->ev_search_end, s));
     if (ix->opt_search_only) return GENIE_W_SEARCH_ONLY;   // timing experiments: no counts / offsets / rows were written
+    const long long N = r.N;
     // both strands: K_B reads the strand-reads' lengths that K_A wrote (or fixed_len for all)
-    if (csr.both && d_lens) d_lens = ws.vlens;
+    const int32_t *lens = r.both && r.lens ? ws.vlens : r.lens;
     // the head of a read's (count, pairs) row: behind its packed-read records (short reads) or the kj row itself
     uint8_t *head = WIDE ? ws.kj : reinterpret_cast<uint8_t *>(ws.qp) + g.qp_recs * 16;
     const int head_stride = WIDE ? g.kj_row * 4 : g.qp_stride * 16;
     const int tb = 256;
     int reads_per_block = tb;                // of the traversal kernel
-    unsigned long long *bsums = csr.offsets ? reinterpret_cast<unsigned long long *>(ws.scan_tmp) : nullptr;
+    unsigned long long *bsums = r.offsets ? reinterpret_cast<unsigned long long *>(ws.scan_tmp) : nullptr;
     if (WIDE) {
         // lanes per read: 2, each taking eight positions per pass from LDS windows of the row, when the batch is large enough to
         // give every SIMD several such waves; else 16 lanes of one position each (few reads: the chip needs the lanes).
@@ -884,24 +894,23 @@ int launch_pipeline(const genie_index *ix, const Geometry &g, const uint8_t *d_r
         // bases 340 -> 270 us with two lanes; 18 750 x 8000 bases 410 us with 16 lanes, 690 us with four lanes of eight positions.
         const int lanes = N >= kLongTwoLaneReads ? 2 : 16;
         auto kl = lanes == 2 ? traverse_long_kernel<MODE, 2, 8> : traverse_long_kernel<MODE, 16, 1>;
-        LAUNCH(kl, dim3((unsigned)((N + tb / lanes - 1) / (tb / lanes))), dim3(tb), lanes == 2 ? (tb / lanes) * kLongRowBytes : 0, s, d_lens,
-               (long long)N, fixed_len, min_len, ws.fwd, g.fwd_stride, cnt, reinterpret_cast<uint32_t *>(ws.kj),
-               g.kj_row, csr.offsets ? g.kj_row : cap, st, bsums);
+        LAUNCH(kl, dim3((unsigned)((N + tb / lanes - 1) / (tb / lanes))), dim3(tb), lanes == 2 ? (tb / lanes) * kLongRowBytes : 0, s, lens,
+               N, r.fixed_len, r.min_len, ws.fwd, g.fwd_stride, cnt, reinterpret_cast<uint32_t *>(ws.kj),
+               g.kj_row, r.offsets ? g.kj_row : r.cap, st, bsums);
         reads_per_block = tb / lanes;
     } else {                                 // one lane per read, rows staged in LDS
         auto kb = traverse_kernel<MODE>;
         const int lds_b = tb * g.fwd_lds;
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kb), hipFuncAttributeMaxDynamicSharedMemorySize, lds_b));
-        LAUNCH(kb, dim3((unsigned)((N + tb - 1) / tb)), dim3(tb), lds_b, s, ix->dev, d_lens, (long long)N,
-               fixed_len, min_len, ws.fwd, g.fwd_stride, g.fwd_lds, cnt, ws.kj, g.kj_row, head, head_stride,
-               csr.offsets ? g.kj_row : cap, st, bsums, csr.counts8, csr.status8);
+        LAUNCH(kb, dim3((unsigned)((N + tb - 1) / tb)), dim3(tb), lds_b, s, ix->dev, lens, N,
+               r.fixed_len, r.min_len, ws.fwd, g.fwd_stride, g.fwd_lds, cnt, ws.kj, g.kj_row, head, head_stride,
+               r.offsets ? g.kj_row : r.cap, st, bsums, r.counts8, r.status8);
     }
     int block_shift = 0;
     while ((1 << block_shift) < reads_per_block) block_shift++;
-    if (csr.offsets)                         // scan of the traversal blocks' sums; K_C adds the in-block part
+    if (r.offsets)                           // scan of the traversal blocks' sums; K_C adds the in-block part
         LAUNCH(scan_block_sums_kernel, dim3(1), dim3(kScanBlock), 0, s, bsums, (N + reads_per_block - 1) / reads_per_block);
     // K_C: intervals + final rows, 16 lanes per read (4 reads per wave pass), persistent blocks
-    const int cus = ix->num_cus > 0 ? ix->num_cus : 256;
     // (half the blocks help on the 1 Mb reference, 1.50 -> 1.40 ms per 4 x 10^6 reads, but cost at 300 kb, 0.215 -> 0.250 ms
     // per 10^6, with the same 8 MB table: not worth a rule)
     long long grid_c = (long long)cus * (32 / kIvWaves);
@@ -909,41 +918,32 @@ int launch_pipeline(const genie_index *ix, const Geometry &g, const uint8_t *d_r
     if (grid_c > need_c) grid_c = need_c;
     RowEscapes esc{nullptr, nullptr, 0};
     const int sched_c = ((ix->opt_scheduling >> 2) & 1) | cus << 8;  // bit 0: no priority rotation; bits 8..: CUs (blocks per round)
-    if (csr.packed) {
-        esc.count = reinterpret_cast<unsigned long long *>(csr.offsets) + 1;
-        esc.list = reinterpret_cast<long long *>(csr.escapes);
-        esc.cap = csr.cap_escapes;
-        HIP_TRY(hipMemsetAsync(csr.offsets, 0, 16, s));
-        auto kp = csr.row_bytes == 6 ? (c16 ? interval_kernel<true, false, true, 2> : interval_kernel<true, false, false, 2>)
-                                     : (c16 ? interval_kernel<true, false, true, 1> : interval_kernel<true, false, false, 1>);
-        LAUNCH(kp, dim3((unsigned)grid_c), dim3(kIvWaves * kWave), 0, s, ix->dev, (long long)N,
-               ws.kj, g.kj_row, head, head_stride, ws.qp, g.qp_stride, reinterpret_cast<void *>(csr.rows), 0,
-               reinterpret_cast<long long *>(csr.offsets), (long long)csr.cap_rows, bsums, cnt, block_shift, esc, sched_c);
-        return GENIE_OK;
+    if (r.packed) {
+        esc.count = reinterpret_cast<unsigned long long *>(r.offsets) + 1;
+        esc.list = reinterpret_cast<long long *>(r.escapes);
+        esc.cap = r.cap_escapes;
+        HIP_TRY(hipMemsetAsync(r.offsets, 0, 16, s));
     }
-    auto kc = csr.offsets ? (c16 ? interval_kernel<true, WIDE, true> : interval_kernel<true, WIDE, false>)
-                          : (c16 ? interval_kernel<false, WIDE, true> : interval_kernel<false, WIDE, false>);
-    if (csr.offsets)
-        LAUNCH(kc, dim3((unsigned)grid_c), dim3(kIvWaves * kWave), 0, s, ix->dev, (long long)N,
-               ws.kj, g.kj_row, head, head_stride, ws.qp, g.qp_stride, reinterpret_cast<void *>(csr.rows), 0,
-               reinterpret_cast<long long *>(csr.offsets), (long long)csr.cap_rows, bsums, cnt, block_shift, esc, sched_c);
-    else
-        LAUNCH(kc, dim3((unsigned)grid_c), dim3(kIvWaves * kWave), 0, s, ix->dev, (long long)N,
-               ws.kj, g.kj_row, head, head_stride, ws.qp, g.qp_stride, reinterpret_cast<void *>(d_slots), cap, nullptr, 0ll, nullptr, nullptr, 0, esc, sched_c);
+    auto kc = r.packed ? (r.row_bytes == 6 ? (c16 ? interval_kernel<true, false, true, 2> : interval_kernel<true, false, false, 2>)
+                                           : (c16 ? interval_kernel<true, false, true, 1> : interval_kernel<true, false, false, 1>))
+            : r.offsets ? (c16 ? interval_kernel<true, WIDE, true> : interval_kernel<true, WIDE, false>)
+                        : (c16 ? interval_kernel<false, WIDE, true> : interval_kernel<false, WIDE, false>);
+    // CSR rows: through the scanned block sums and the counts; slots: `cap` per read
+    LAUNCH(kc, dim3((unsigned)grid_c), dim3(kIvWaves * kWave), 0, s, ix->dev, N, ws.kj, g.kj_row, head, head_stride, ws.qp,
+           g.qp_stride, r.offsets ? reinterpret_cast<void *>(r.rows) : reinterpret_cast<void *>(r.slots), r.offsets ? 0 : r.cap,
+           reinterpret_cast<long long *>(r.offsets), r.offsets ? (long long)r.cap_rows : 0ll, bsums, r.offsets ? cnt : nullptr,
+           r.offsets ? block_shift : 0, esc, sched_c);
     return GENIE_OK;
 }
 
 template <int MODE>
-int launch_find_mode(const genie_index *ix, const Geometry &g, const uint8_t *d_reads, const int32_t *d_lens, int64_t N,
-                     int32_t stride, int32_t fixed_len, int32_t min_len, int32_t *d_counts, int32_t *d_slots,
-                     int32_t cap, int32_t *d_status, void *d_ws, int64_t ws_bytes, const CsrOut &csr, hipStream_t s)
+int launch_find_mode(const genie_index *ix, const Geometry &g, const FindRequest &r, hipStream_t s)
 {
     Workspace ws;
-    int rc = carve_workspace(d_ws, ws_bytes, N, g, &ws, csr.both ? N : 0);
+    int rc = carve_workspace(r.ws, r.ws_bytes, r.N, g, &ws, r.both ? r.N : 0);
     if (rc) return rc;
-    if (g.wide)
-        return launch_pipeline<MODE, true>(ix, g, d_reads, d_lens, N, stride, fixed_len, min_len, d_counts, d_slots, cap, d_status, ws, csr, s);
-    return launch_pipeline<MODE, false>(ix, g, d_reads, d_lens, N, stride, fixed_len, min_len, d_counts, d_slots, cap, d_status, ws, csr, s);
+    if (g.wide) return launch_pipeline<MODE, true>(ix, g, r, ws, s);
+    return launch_pipeline<MODE, false>(ix, g, r, ws, s);
 }
 
 }  // namespace
@@ -972,17 +972,18 @@ int find_smems_geometry(const genie_index *ix, int32_t mode, int32_t max_len, in
     return GENIE_OK;
 }
 
-// Name of the match-statistics kernel the plan picks (as rocprofv3 prints it, without the argument list).
+// Name of the match-statistics kernel the plan picks (as rocprofv3 prints it, without the argument list): the instance for
+// unpacked reads of one strand, which bench.py times.
 int search_kernel_name(const genie_index *ix, int32_t mode, int32_t max_len, char *buf, int32_t cap)
 {
-    (void)mode;
-    // match_table_kernel<waves per SIMD, compact table, packed reads> (the unpacked-reads instance: what bench.py times)
-    const bool big = table_bytes(ix) > kTableFitsL2, c16 = (ix->dev.flags & kFlagCompactTable) != 0;
-    const char *name = max_len > 255 ? (c16 ? "match_table_long_kernel<true>" : "match_table_long_kernel<false>")
-                                     : (big ? (c16 ? "match_table_kernel<4, true, false>" : "match_table_kernel<4, false, false>")
-                                            : (c16 ? "match_table_kernel<6, true, false>" : "match_table_kernel<8, false, false>"));
-    if (!buf || cap < (int)strlen(name) + 1) return GENIE_E_CAPACITY;
-    memcpy(buf, name, strlen(name) + 1);
+    Geometry g;
+    int rc = plan_find_smems(ix, mode, max_len, 1ll << 40, &g);
+    if (rc) return rc;
+    const std::string c16 = (ix->dev.flags & kFlagCompactTable) ? "true" : "false";
+    const std::string name = g.wide ? "match_table_long_kernel<" + c16 + ">"
+                                    : "match_table_kernel<" + std::to_string(g.wps) + ", " + c16 + ", false>";
+    if (!buf || cap < (int)name.size() + 1) return GENIE_E_CAPACITY;
+    memcpy(buf, name.c_str(), name.size() + 1);
     return GENIE_OK;
 }
 
@@ -1004,55 +1005,46 @@ void find_smems_workspace_rows(int32_t max_len, int32_t out[4])
     out[3] = g.kj_row * (g.wide ? 4 : 2);
 }
 
-static int launch_find_any(const genie_index *ix, int32_t mode, const uint8_t *d_reads, const int32_t *d_lens, int64_t N,
-                           int32_t stride, int32_t fixed_len, int32_t min_len, int32_t *d_counts, int32_t *d_slots,
-                           int32_t cap, int32_t *d_status, void *d_ws, int64_t ws_bytes, const CsrOut &csr, void *stream)
+static int launch_find_any(const genie_index *ix, int32_t mode, const FindRequest &r, void *stream)
 {
+    hipStream_t s = (hipStream_t)stream;
+    if (r.N == 0) {                          // no reads: an empty CSR (packed: both totals), and nothing for slots
+        if (r.offsets) HIP_TRY(hipMemsetAsync(r.offsets, 0, r.packed ? 16 : 8, s));
+        return GENIE_OK;
+    }
     Geometry g;
     // with ragged lengths `fixed_len` carries the maximum length (host contract)
     // (genie_find_smems_both: N strand-reads, the group size unchanged -- an even group holds whole pairs; an odd one splits
     // every other pair over two consecutive groups, which waves of the same block take, so the row is in its L2 either way.
     // Rounding 5 reads of 150 bases down to 4 left a fifth of round 1's lanes idle.)
-    int rc = plan_find_smems(ix, mode, fixed_len, N, &g);
+    int rc = plan_find_smems(ix, mode, r.fixed_len, r.N, &g);
     if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
     switch (mode) {
-    case GENIE_MODE_BWA:
-        return launch_find_mode<GENIE_MODE_BWA>(ix, g, d_reads, d_lens, N, stride, fixed_len, min_len, d_counts, d_slots,
-                                                cap, d_status, d_ws, ws_bytes, csr, s);
-    case GENIE_MODE_LUT:
-        return launch_find_mode<GENIE_MODE_LUT>(ix, g, d_reads, d_lens, N, stride, fixed_len, min_len, d_counts, d_slots,
-                                                cap, d_status, d_ws, ws_bytes, csr, s);
-    case GENIE_MODE_RMI:
-        return launch_find_mode<GENIE_MODE_RMI>(ix, g, d_reads, d_lens, N, stride, fixed_len, min_len, d_counts, d_slots,
-                                                cap, d_status, d_ws, ws_bytes, csr, s);
+    case GENIE_MODE_BWA: return launch_find_mode<GENIE_MODE_BWA>(ix, g, r, s);
+    case GENIE_MODE_LUT: return launch_find_mode<GENIE_MODE_LUT>(ix, g, r, s);
+    case GENIE_MODE_RMI: return launch_find_mode<GENIE_MODE_RMI>(ix, g, r, s);
     }
     return GENIE_E_INVALID;
 }
 
-int launch_find_smems(const genie_index *ix, int32_t mode, const uint8_t *d_reads, const int32_t *d_lens, int64_t N,
-                      int32_t stride, int32_t fixed_len, int32_t min_len, int32_t *d_counts, int32_t *d_slots,
-                      int32_t cap, int32_t *d_status, void *d_ws, int64_t ws_bytes, void *stream)
+int launch_find_smems(const genie_index *ix, int32_t mode, const FindBatch &b, int32_t *d_counts, int32_t *d_slots, int32_t cap,
+                      void *stream)
 {
-    if (N == 0) return GENIE_OK;
-    return launch_find_any(ix, mode, d_reads, d_lens, N, stride, fixed_len, min_len, d_counts, d_slots, cap, d_status, d_ws,
-                           ws_bytes, CsrOut{}, stream);
+    FindRequest r(b);
+    r.counts = d_counts;
+    r.slots = d_slots;
+    r.cap = cap;
+    return launch_find_any(ix, mode, r, stream);
 }
 
-int launch_find_smems_csr(const genie_index *ix, int32_t mode, const uint8_t *d_reads, const int32_t *d_lens, int64_t N,
-                          int32_t stride, int32_t fixed_len, int32_t min_len, int64_t *d_offsets, int32_t *d_rows,
-                          int64_t out_cap_rows, int32_t *d_status, void *d_ws, int64_t ws_bytes, void *stream)
+int launch_find_smems_csr(const genie_index *ix, int32_t mode, const FindBatch &b, int64_t *d_offsets, int32_t *d_rows,
+                          int64_t out_cap_rows, void *stream)
 {
-    if (N == 0) {
-        HIP_TRY(hipMemsetAsync(d_offsets, 0, 8, (hipStream_t)stream));
-        return GENIE_OK;
-    }
-    CsrOut csr;
-    csr.offsets = d_offsets;
-    csr.rows = d_rows;
-    csr.cap_rows = out_cap_rows;
-    return launch_find_any(ix, mode, d_reads, d_lens, N, stride, fixed_len, min_len, nullptr, nullptr, 0, d_status, d_ws,
-                           ws_bytes, csr, stream);
+    FindRequest r(b);
+    r.offsets = d_offsets;
+    r.rows = d_rows;
+    r.cap_rows = out_cap_rows;
+    return launch_find_any(ix, mode, r, stream);
 }
 
 int64_t find_smems_both_workspace_bytes(int64_t N, int32_t max_len)
@@ -1063,44 +1055,33 @@ int64_t find_smems_both_workspace_bytes(int64_t N, int32_t max_len)
     return workspace_layout(nullptr, 2 * N, g, &ws, 2 * N);
 }
 
-int launch_find_smems_both(const genie_index *ix, int32_t mode, const uint8_t *d_reads, const int32_t *d_lens, int64_t N,
-                           int32_t stride, int32_t fixed_len, int32_t min_len, int64_t *d_offsets, int32_t *d_rows,
-                           int64_t out_cap_rows, int32_t *d_status, void *d_ws, int64_t ws_bytes, void *stream)
+int launch_find_smems_both(const genie_index *ix, int32_t mode, const FindBatch &b, int64_t *d_offsets, int32_t *d_rows,
+                           int64_t out_cap_rows, void *stream)
 {
-    if (N == 0) {
-        HIP_TRY(hipMemsetAsync(d_offsets, 0, 8, (hipStream_t)stream));
-        return GENIE_OK;
-    }
-    CsrOut csr;
-    csr.offsets = d_offsets;
-    csr.rows = d_rows;
-    csr.cap_rows = out_cap_rows;
-    csr.both = true;
-    return launch_find_any(ix, mode, d_reads, d_lens, 2 * N, stride, fixed_len, min_len, nullptr, nullptr, 0, d_status, d_ws,
-                           ws_bytes, csr, stream);
+    FindRequest r(b);
+    r.N = 2 * b.N;
+    r.offsets = d_offsets;
+    r.rows = d_rows;
+    r.cap_rows = out_cap_rows;
+    r.both = true;
+    return launch_find_any(ix, mode, r, stream);
 }
 
-int launch_find_smems_packed(const genie_index *ix, int32_t mode, const uint8_t *d_reads2, const int32_t *d_lens, int64_t N,
-                             int32_t stride_bytes, int32_t fixed_len, int32_t min_len, uint8_t *d_counts8, uint8_t *d_status8,
+int launch_find_smems_packed(const genie_index *ix, int32_t mode, const FindBatch &b, uint8_t *d_counts8, uint8_t *d_status8,
                              void *d_rows8, int64_t out_cap_rows, int64_t *d_totals, int64_t *d_escapes, int64_t cap_escapes,
-                             void *d_ws, int64_t ws_bytes, void *stream, int row_bytes)
+                             void *stream, int row_bytes)
 {
-    if (N == 0) {
-        HIP_TRY(hipMemsetAsync(d_totals, 0, 16, (hipStream_t)stream));
-        return GENIE_OK;
-    }
-    CsrOut csr;
-    csr.offsets = d_totals;
-    csr.rows = reinterpret_cast<int32_t *>(d_rows8);
-    csr.cap_rows = out_cap_rows;
-    csr.packed = true;
-    csr.row_bytes = row_bytes;
-    csr.counts8 = d_counts8;
-    csr.status8 = d_status8;
-    csr.escapes = d_escapes;
-    csr.cap_escapes = cap_escapes;
-    return launch_find_any(ix, mode, d_reads2, d_lens, N, stride_bytes, fixed_len, min_len, nullptr, nullptr, 0, nullptr, d_ws,
-                           ws_bytes, csr, stream);
+    FindRequest r(b);
+    r.offsets = d_totals;
+    r.rows = reinterpret_cast<int32_t *>(d_rows8);
+    r.cap_rows = out_cap_rows;
+    r.packed = true;
+    r.row_bytes = row_bytes;
+    r.counts8 = d_counts8;
+    r.status8 = d_status8;
+    r.escapes = d_escapes;
+    r.cap_escapes = cap_escapes;
+    return launch_find_any(ix, mode, r, stream);
 }
 
 int launch_sa_interval(const genie_index *ix, const uint8_t *d_pats, const int32_t *d_lens, int64_t N, int32_t stride,

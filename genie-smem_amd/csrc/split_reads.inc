@@ -375,8 +375,8 @@ int launch_find_smems_split(const genie_index *ix, const uint8_t *d_reads, const
         HIP_TRY(hipStreamSynchronize(s));
         if (fl & 2u) return GENIE_E_INVALID;                   // a length outside [0, fixed_len]
         if (fl == 0)
-            return launch_find_smems_csr(ix, GENIE_MODE_BWA, d_reads, d_lens, N, stride, fixed_len, min_len, d_offsets, d_rows,
-                                         out_cap_rows, d_status, p, pass_avail, stream);
+            return launch_find_smems_csr(ix, GENIE_MODE_BWA, {d_reads, d_lens, N, stride, fixed_len, min_len, d_status, p, pass_avail},
+                                         d_offsets, d_rows, out_cap_rows, stream);
     }
     LAUNCH(split_count_kernel, dim3((unsigned)std::min<long long>(groups, (long long)cus * 8)), dim3(kSplitWaves * 64), 0, s,
            ix->dev, d_reads, d_lens, (long long)N, stride, fixed_len, f.nseg, f.gsum, f.totals);
@@ -416,9 +416,9 @@ int launch_find_smems_split(const genie_index *ix, const uint8_t *d_reads, const
         LAUNCH(split_fill_kernel, dim3((unsigned)((N + kSplitWaves - 1) / kSplitWaves)), dim3(kSplitWaves * 64), 0, s,
                ix->dev, d_reads, d_lens, (long long)N, stride, fixed_len, f.segoff, ps);
         const long long cap_left = std::max(0ll, (long long)out_cap_rows - row0);
-        int rc = launch_find_smems_csr(ix, GENIE_MODE_BWA, a.gbuf, a.seg_len, p1 - p0, ps.gstride, M, min_len, reinterpret_cast<int64_t *>(a.local_off),
-                                       cap_left > 0 ? d_rows + 4 * row0 : d_rows, cap_left, a.seg_status, a.csr_ws,
-                                       a.csr_ws_bytes, stream);
+        int rc = launch_find_smems_csr(ix, GENIE_MODE_BWA, {a.gbuf, a.seg_len, p1 - p0, ps.gstride, M, min_len, a.seg_status, a.csr_ws,
+                                                            a.csr_ws_bytes},
+                                       reinterpret_cast<int64_t *>(a.local_off), cap_left > 0 ? d_rows + 4 * row0 : d_rows, cap_left, stream);
         if (rc) return rc;
         const long long threads = std::max(p1 - p0, (long long)N);
         LAUNCH(split_remap_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, ps,

@@ -226,27 +226,56 @@ class GenieIndex:
         t = t.to(device=self.device, dtype=dtype)
         return t.contiguous()
 
-    def sa_interval(self, pats, lens=None):
-        """Batched exact_match_back_prop.  pats: [N, stride] uint8 codes; lens: [N] or None.
-        Returns int32 [N, 2] (lo, hi); (-1,-1) absent; (-2,-2) code > 3."""
+    def _batch(self, reads, lens, names=("reads", "read")):
+        """A batch of [N, stride] uint8 codes and its optional int32 lengths on the device -> (reads, lens, N, stride,
+        fixed): fixed is the longest length, or stride without lengths."""
         self._need_device()
-        pats = self._as_dev(pats, torch.uint8)
-        if pats.dim() != 2:
-            raise ValueError("pats must be [N, stride]")
-        n_pat, stride = pats.shape
+        reads = self._as_dev(reads, torch.uint8)
+        if reads.dim() != 2:
+            raise ValueError(f"{names[0]} must be [N, stride]")
+        n, stride = reads.shape
         fixed = stride
         if lens is not None:
             lens = self._as_dev(lens, torch.int32)
-            fixed = int(lens.max().item()) if n_pat else 0
-            if fixed > stride or (n_pat and int(lens.min().item()) < 0):
-                raise ValueError("pattern length outside [0, stride]")
+            fixed = int(lens.max().item()) if n else 0
+            if fixed > stride or (n and int(lens.min().item()) < 0):
+                raise ValueError(f"{names[1]} length outside [0, stride]")
+        return reads, lens, n, stride, fixed
+
+    def _workspace(self, size_fn, *args):
+        """(device buffer, bytes) of the workspace the C size function `size_fn` asks for."""
+        nbytes = int(getattr(N.lib(), size_fn)(*args))
+        if nbytes < 0:
+            raise N.GenieError(nbytes, size_fn)
+        return torch.empty(max(nbytes, 256), dtype=torch.uint8, device=self.device), nbytes
+
+    def _run(self, name, *args):
+        """Call the C entry point `name` on this handle with `args`, on the current stream of the index's device."""
+        with torch.cuda.device(self.device):
+            N.check(getattr(N.lib(), name)(self._h, *args, _stream(self.device)), name)
+
+    def _run_csr(self, name, head, n_rows, cap_rows, tail):
+        """Run a CSR entry point, name(handle, *head, offsets, rows, rows capacity, status, *tail, stream), with room for
+        `cap_rows` rows, rerun with the exact size if they do not fit -> (offsets int64[n_rows+1], smems int32[S,4], status)."""
+        offsets = torch.empty(n_rows + 1, dtype=torch.int64, device=self.device)
+        status = torch.empty(n_rows, dtype=torch.int32, device=self.device)
+        while True:
+            rows = torch.empty((max(cap_rows, 1), 4), dtype=torch.int32, device=self.device)
+            self._run(name, *head, _ptr(offsets), _ptr(rows), rows.shape[0], _ptr(status), *tail)
+            total = int(offsets[-1].item())
+            if total <= rows.shape[0]:
+                return offsets, rows[:total], status
+            cap_rows = total                      # capacity guess too small: rerun with the exact size
+
+    def sa_interval(self, pats, lens=None):
+        """Batched exact_match_back_prop.  pats: [N, stride] uint8 codes; lens: [N] or None.
+        Returns int32 [N, 2] (lo, hi); (-1,-1) absent; (-2,-2) code > 3."""
+        pats, lens, n_pat, stride, fixed = self._batch(pats, lens, ("pats", "pattern"))
         if stride == 0:
             pats = torch.zeros((n_pat, 1), dtype=torch.uint8, device=self.device)
             stride = 1
         out = torch.empty((n_pat, 2), dtype=torch.int32, device=self.device)
-        with torch.cuda.device(self.device):
-            N.check(N.lib().genie_sa_interval(self._h, _ptr(pats), _ptr(lens), n_pat, stride, fixed, _ptr(out),
-                                              _stream(self.device)), "genie_sa_interval")
+        self._run("genie_sa_interval", _ptr(pats), _ptr(lens), n_pat, stride, fixed, _ptr(out))
         return out
 
     def seed_lookup(self, mode, kmers, want_pred=False):
@@ -257,25 +286,13 @@ class GenieIndex:
             raise ValueError("kmers must be [N, K]")
         out = torch.empty((kmers.shape[0], 2), dtype=torch.int32, device=self.device)
         pred = torch.empty(kmers.shape[0], dtype=torch.float64, device=self.device) if want_pred else None
-        with torch.cuda.device(self.device):
-            N.check(N.lib().genie_seed_lookup(self._h, N.MODES[mode], _ptr(kmers), kmers.shape[0], _ptr(out),
-                                              _ptr(pred), _stream(self.device)), "genie_seed_lookup")
+        self._run("genie_seed_lookup", N.MODES[mode], _ptr(kmers), kmers.shape[0], _ptr(out), _ptr(pred))
         return (out, pred) if want_pred else out
 
     def find_smems_slots(self, mode, reads, lens=None, min_len=1, cap=None):
         """One launch of the SMEM kernel.  reads: [N, stride] uint8 codes on the device.
         Returns (counts int32[N], slots int32[N, cap, 4], status int32[N])."""
-        self._need_device()
-        reads = self._as_dev(reads, torch.uint8)
-        if reads.dim() != 2:
-            raise ValueError("reads must be [N, stride]")
-        n_reads, stride = reads.shape
-        fixed = stride
-        if lens is not None:
-            lens = self._as_dev(lens, torch.int32)
-            fixed = int(lens.max().item()) if n_reads else 0
-            if fixed > stride or (n_reads and int(lens.min().item()) < 0):
-                raise ValueError("read length outside [0, stride]")
+        reads, lens, n_reads, stride, fixed = self._batch(reads, lens)
         if cap is None:
             cap = max(1, fixed)
         counts = torch.empty(n_reads, dtype=torch.int32, device=self.device)
@@ -285,12 +302,9 @@ class GenieIndex:
             counts.zero_()
             status.zero_()
             return counts, slots, status
-        ws_bytes = int(N.lib().genie_find_smems_workspace_bytes(n_reads, fixed))
-        ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=self.device)
-        with torch.cuda.device(self.device):
-            N.check(N.lib().genie_find_smems(self._h, N.MODES[mode], _ptr(reads), _ptr(lens), n_reads, stride, fixed,
-                                             int(min_len), _ptr(counts), _ptr(slots), cap, _ptr(status), _ptr(ws),
-                                             ws_bytes, _stream(self.device)), "genie_find_smems")
+        ws, ws_bytes = self._workspace("genie_find_smems_workspace_bytes", n_reads, fixed)
+        self._run("genie_find_smems", N.MODES[mode], _ptr(reads), _ptr(lens), n_reads, stride, fixed, int(min_len),
+                  _ptr(counts), _ptr(slots), cap, _ptr(status), _ptr(ws), ws_bytes)
         return counts, slots, status
 
     def compact(self, counts, slots, out=None):
@@ -323,17 +337,12 @@ class GenieIndex:
         iv = iv.contiguous()
         S, width = iv.shape
         offsets = torch.empty(S + 1, dtype=torch.int64, device=self.device)
-        tmp_bytes = int(N.lib().genie_locate_tmp_bytes(S))
-        tmp = torch.empty(max(tmp_bytes, 256), dtype=torch.uint8, device=self.device)
-        base = iv.data_ptr() + (8 if width == 4 else 0)
-        with torch.cuda.device(self.device):
-            st = _stream(self.device)
-            N.check(N.lib().genie_locate(self._h, C.c_void_p(base), width, S, _ptr(offsets), C.c_void_p(0), 0, _ptr(tmp),
-                                         tmp_bytes, st), "genie_locate")
-            total = int(offsets[-1].item())
-            pos = torch.empty(max(total, 1), dtype=torch.int32, device=self.device)
-            N.check(N.lib().genie_locate(self._h, C.c_void_p(base), width, S, _ptr(offsets), _ptr(pos), total, _ptr(tmp),
-                                         tmp_bytes, st), "genie_locate")
+        tmp, tmp_bytes = self._workspace("genie_locate_tmp_bytes", S)
+        base = C.c_void_p(iv.data_ptr() + (8 if width == 4 else 0))
+        self._run("genie_locate", base, width, S, _ptr(offsets), C.c_void_p(0), 0, _ptr(tmp), tmp_bytes)
+        total = int(offsets[-1].item())
+        pos = torch.empty(max(total, 1), dtype=torch.int32, device=self.device)
+        self._run("genie_locate", base, width, S, _ptr(offsets), _ptr(pos), total, _ptr(tmp), tmp_bytes)
         pos = pos[:total]
         if sort and total:
             # ascending inside every interval: one sort on (interval, position) keys -- torch plumbing
@@ -345,38 +354,16 @@ class GenieIndex:
     def find_smems(self, mode, reads, lens=None, min_len=1, cap=None, rows_hint=None):
         """Batched SMEM discovery -> (offsets int64[N+1], smems int32[S,4] = (start,end,lo,hi), status).
         Uses the fused CSR entry point (genie_find_smems_csr) unless an explicit slot capacity is asked for."""
-        self._need_device()
-        reads = self._as_dev(reads, torch.uint8)
-        if reads.dim() != 2:
-            raise ValueError("reads must be [N, stride]")
-        n_reads, stride = reads.shape
-        fixed = stride
-        if lens is not None:
-            lens = self._as_dev(lens, torch.int32)
-            fixed = int(lens.max().item()) if n_reads else 0
-            if fixed > stride or (n_reads and int(lens.min().item()) < 0):
-                raise ValueError("read length outside [0, stride]")
+        reads, lens, n_reads, stride, fixed = self._batch(reads, lens)
         if cap is not None or n_reads == 0 or stride == 0:
             counts, slots, status = self.find_smems_slots(mode, reads, lens, min_len, cap)
             offsets, out = self.compact(counts, slots)
             total = int(offsets[-1].item())
             return offsets, out[:total], status
-        offsets = torch.empty(n_reads + 1, dtype=torch.int64, device=self.device)
-        status = torch.empty(n_reads, dtype=torch.int32, device=self.device)
-        ws_bytes = int(N.lib().genie_find_smems_workspace_bytes(n_reads, fixed))
-        ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=self.device)
-        cap_rows = int(rows_hint) if rows_hint else n_reads * max(8, fixed // 6)
-        while True:
-            rows = torch.empty((max(cap_rows, 1), 4), dtype=torch.int32, device=self.device)
-            with torch.cuda.device(self.device):
-                N.check(N.lib().genie_find_smems_csr(self._h, N.MODES[mode], _ptr(reads), _ptr(lens), n_reads, stride,
-                                                     fixed, int(min_len), _ptr(offsets), _ptr(rows), rows.shape[0],
-                                                     _ptr(status), _ptr(ws), ws_bytes, _stream(self.device)),
-                        "genie_find_smems_csr")
-            total = int(offsets[-1].item())
-            if total <= rows.shape[0]:
-                return offsets, rows[:total], status
-            cap_rows = total                      # capacity guess too small: rerun with the exact size
+        ws, ws_bytes = self._workspace("genie_find_smems_workspace_bytes", n_reads, fixed)
+        return self._run_csr("genie_find_smems_csr", (N.MODES[mode], _ptr(reads), _ptr(lens), n_reads, stride, fixed,
+                                                      int(min_len)),
+                             n_reads, int(rows_hint) if rows_hint else n_reads * max(8, fixed // 6), (_ptr(ws), ws_bytes))
 
     def find_smems_both(self, mode, reads, lens=None, min_len=1, rows_hint=None):
         """SMEMs of both strands of every read (genie_find_smems_both) -> (offsets int64[2N+1], smems int32[S,4], status
@@ -384,38 +371,15 @@ class GenieIndex:
         of find_smems on the interleaved batch [r0, rc(r0), r1, rc(r1), ...], with start / end of a strand-1 row positions in
         the reverse-complemented read (forward coordinates: L - end, L - start).  reads: [N, stride] uint8 codes (device or
         host: uploaded as uint8 codes)."""
-        self._need_device()
-        reads = self._as_dev(reads, torch.uint8)
-        if reads.dim() != 2:
-            raise ValueError("reads must be [N, stride]")
-        n_reads, stride = reads.shape
-        fixed = stride
-        if lens is not None:
-            lens = self._as_dev(lens, torch.int32)
-            fixed = int(lens.max().item()) if n_reads else 0
-            if fixed > stride or (n_reads and int(lens.min().item()) < 0):
-                raise ValueError("read length outside [0, stride]")
+        reads, lens, n_reads, stride, fixed = self._batch(reads, lens)
         if stride == 0:
             reads = torch.zeros((n_reads, 1), dtype=torch.uint8, device=self.device)
             stride = 1
-        offsets = torch.empty(2 * n_reads + 1, dtype=torch.int64, device=self.device)
-        status = torch.empty(2 * n_reads, dtype=torch.int32, device=self.device)
-        ws_bytes = int(N.lib().genie_find_smems_both_workspace_bytes(n_reads, fixed))
-        if ws_bytes < 0:
-            raise N.GenieError(ws_bytes, "genie_find_smems_both_workspace_bytes")
-        ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=self.device)
-        cap_rows = int(rows_hint) if rows_hint else 2 * n_reads * max(8, fixed // 6)
-        while True:
-            rows = torch.empty((max(cap_rows, 1), 4), dtype=torch.int32, device=self.device)
-            with torch.cuda.device(self.device):
-                N.check(N.lib().genie_find_smems_both(self._h, N.MODES[mode], _ptr(reads), _ptr(lens), n_reads, stride, fixed,
-                                                      int(min_len), _ptr(offsets), _ptr(rows), rows.shape[0], _ptr(status),
-                                                      _ptr(ws), ws_bytes, _stream(self.device)),
-                        "genie_find_smems_both")
-            total = int(offsets[-1].item())
-            if total <= rows.shape[0]:
-                return offsets, rows[:total], status
-            cap_rows = total                      # capacity guess too small: rerun with the exact size
+        ws, ws_bytes = self._workspace("genie_find_smems_both_workspace_bytes", n_reads, fixed)
+        return self._run_csr("genie_find_smems_both", (N.MODES[mode], _ptr(reads), _ptr(lens), n_reads, stride, fixed,
+                                                       int(min_len)),
+                             2 * n_reads, int(rows_hint) if rows_hint else 2 * n_reads * max(8, fixed // 6),
+                             (_ptr(ws), ws_bytes))
 
     def find_smems_split(self, reads, lens=None, min_len=1, rows_hint=None):
         """SMEMs of reads that may contain breaks (genie_find_smems_split) -> (offsets int64[N+1], smems int32[S,4], status).
@@ -423,38 +387,13 @@ class GenieIndex:
         carry a break).  A break is any code > 3 or a base that never occurs in the reference; the SMEMs of a read are those
         of its segments (the runs between breaks), in read order, each found like get_SMEMS with min_len, with start / end
         positions in the whole read.  A read of length 0 or made only of breaks has no rows and status 0."""
-        self._need_device()
-        reads = self._as_dev(reads, torch.uint8)
-        if reads.dim() != 2:
-            raise ValueError("reads must be [N, stride]")
-        n_reads, stride = reads.shape
-        fixed = stride
-        if lens is not None:
-            lens = self._as_dev(lens, torch.int32)
-            fixed = int(lens.max().item()) if n_reads else 0
-            if fixed > stride or (n_reads and int(lens.min().item()) < 0):
-                raise ValueError("read length outside [0, stride]")
+        reads, lens, n_reads, stride, fixed = self._batch(reads, lens)
         if stride == 0:
             reads = torch.zeros((n_reads, 1), dtype=torch.uint8, device=self.device)
             stride = 1
-        offsets = torch.empty(n_reads + 1, dtype=torch.int64, device=self.device)
-        status = torch.empty(n_reads, dtype=torch.int32, device=self.device)
-        ws_bytes = int(N.lib().genie_find_smems_split_workspace_bytes(n_reads, fixed))
-        if ws_bytes < 0:
-            raise N.GenieError(ws_bytes, "genie_find_smems_split_workspace_bytes")
-        ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=self.device)
-        cap_rows = int(rows_hint) if rows_hint else n_reads * max(8, fixed // 6)
-        while True:
-            rows = torch.empty((max(cap_rows, 1), 4), dtype=torch.int32, device=self.device)
-            with torch.cuda.device(self.device):
-                N.check(N.lib().genie_find_smems_split(self._h, _ptr(reads), _ptr(lens), n_reads, stride, fixed, int(min_len),
-                                                       _ptr(offsets), _ptr(rows), rows.shape[0], _ptr(status), _ptr(ws),
-                                                       ws_bytes, _stream(self.device)),
-                        "genie_find_smems_split")
-            total = int(offsets[-1].item())
-            if total <= rows.shape[0]:
-                return offsets, rows[:total], status
-            cap_rows = total                      # capacity guess too small: rerun with the exact size
+        ws, ws_bytes = self._workspace("genie_find_smems_split_workspace_bytes", n_reads, fixed)
+        return self._run_csr("genie_find_smems_split", (_ptr(reads), _ptr(lens), n_reads, stride, fixed, int(min_len)),
+                             n_reads, int(rows_hint) if rows_hint else n_reads * max(8, fixed // 6), (_ptr(ws), ws_bytes))
 
     def find_smems_long(self, mode, bases, read_offsets, min_len=1, rows_hint=None):
         """SMEMs of reads of any length (genie_find_smems_long) -> (offsets int64[N+1], smems int32[S,4], status).
@@ -471,24 +410,10 @@ class GenieIndex:
         max_len = min(max(max_len, 0), 2**31 - 1)
         if total == 0:
             bases = torch.zeros(1, dtype=torch.uint8, device=self.device)
-        offsets = torch.empty(n_reads + 1, dtype=torch.int64, device=self.device)
-        status = torch.empty(n_reads, dtype=torch.int32, device=self.device)
-        ws_bytes = int(N.lib().genie_find_smems_long_workspace_bytes(n_reads, total, max_len))
-        if ws_bytes < 0:
-            raise N.GenieError(ws_bytes, "genie_find_smems_long_workspace_bytes")
-        ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=self.device)
-        cap_rows = int(rows_hint) if rows_hint else max(8 * n_reads, total // 6)
-        while True:
-            rows = torch.empty((max(cap_rows, 1), 4), dtype=torch.int32, device=self.device)
-            with torch.cuda.device(self.device):
-                N.check(N.lib().genie_find_smems_long(self._h, N.MODES[mode], _ptr(bases), _ptr(read_offsets), n_reads, total,
-                                                      max_len, int(min_len), _ptr(offsets), _ptr(rows), rows.shape[0],
-                                                      _ptr(status), _ptr(ws), ws_bytes, _stream(self.device)),
-                        "genie_find_smems_long")
-            got = int(offsets[-1].item())
-            if got <= rows.shape[0]:
-                return offsets, rows[:got], status
-            cap_rows = got                        # capacity guess too small: rerun with the exact size
+        ws, ws_bytes = self._workspace("genie_find_smems_long_workspace_bytes", n_reads, total, max_len)
+        return self._run_csr("genie_find_smems_long", (N.MODES[mode], _ptr(bases), _ptr(read_offsets), n_reads, total,
+                                                       max_len, int(min_len)),
+                             n_reads, int(rows_hint) if rows_hint else max(8 * n_reads, total // 6), (_ptr(ws), ws_bytes))
 
     def find_smems_packed(self, mode, packed, max_len, lens=None, min_len=1, rows_hint=None, row_bytes=8):
         """genie_find_smems_packed (or, `row_bytes` = 6, genie_find_smems_packed6): 2-bit packed reads (packing.pack_reads;
@@ -496,7 +421,7 @@ class GenieIndex:
         packing.unpack_rows turns them into the offsets / int32 rows of find_smems.  Reads of at most 255 bases."""
         if row_bytes not in (6, 8):
             raise ValueError("row_bytes is 6 or 8")
-        entry = N.lib().genie_find_smems_packed if row_bytes == 8 else N.lib().genie_find_smems_packed6
+        entry = "genie_find_smems_packed" if row_bytes == 8 else "genie_find_smems_packed6"
         self._need_device()
         packed = self._as_dev(packed, torch.uint8)
         if packed.dim() != 2:
@@ -509,18 +434,15 @@ class GenieIndex:
         totals = torch.zeros(2, dtype=torch.int64, device=self.device)
         if n_reads == 0:
             return counts8, status8, torch.zeros((0, row_bytes), dtype=torch.uint8, device=self.device), torch.zeros((0, 2), dtype=torch.int64, device=self.device)
-        ws_bytes = int(N.lib().genie_find_smems_workspace_bytes(n_reads, int(max_len)))
-        ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=self.device)
+        ws, ws_bytes = self._workspace("genie_find_smems_workspace_bytes", n_reads, int(max_len))
         cap_rows = int(rows_hint) if rows_hint else n_reads * max(8, int(max_len) // 6)
         cap_esc = 1024
         while True:
             rows8 = torch.empty((max(cap_rows, 1), row_bytes), dtype=torch.uint8, device=self.device)
             esc = torch.empty((max(cap_esc, 1), 2), dtype=torch.int64, device=self.device)
-            with torch.cuda.device(self.device):
-                N.check(entry(self._h, N.MODES[mode], _ptr(packed), _ptr(lens), n_reads, stride,
-                                                        int(max_len), int(min_len), _ptr(counts8), _ptr(status8), _ptr(rows8),
-                                                        rows8.shape[0], _ptr(totals), _ptr(esc), esc.shape[0], _ptr(ws), ws_bytes,
-                                                        _stream(self.device)), "genie_find_smems_packed")
+            self._run(entry, N.MODES[mode], _ptr(packed), _ptr(lens), n_reads, stride, int(max_len), int(min_len),
+                      _ptr(counts8), _ptr(status8), _ptr(rows8), rows8.shape[0], _ptr(totals), _ptr(esc), esc.shape[0],
+                      _ptr(ws), ws_bytes)
             total, n_esc = (int(x) for x in totals.cpu())
             if total <= rows8.shape[0] and n_esc <= esc.shape[0]:
                 return counts8, status8, rows8[:total], esc[:n_esc]

@@ -34,18 +34,25 @@ class SMEM:
         self.rmi_lut = None
 
     # ------------------------------------------------------------------ batched entry points
-    def _reads_codes(self, reads):
-        """list[str] | ndarray -> (uint8 [N, width] numpy codes, int32 lens or None)."""
-        if isinstance(reads, np.ndarray):
-            return np.ascontiguousarray(reads, np.uint8), None
-        enc = [self.matcher.encode(r) for r in reads]
+    @staticmethod
+    def _encode_batch(reads, encode):
+        """list[str] -> (uint8 [N, max(width, 1)] codes, zero-padded; int32 lens, or None when every read has the same
+        length; width: the longest read's length, 0 for no reads)."""
+        enc = [encode(r) for r in reads]
         lens = np.asarray([len(e) for e in enc], np.int32)
-        width = int(lens.max()) if len(enc) else 1
+        width = int(lens.max()) if len(enc) else 0
         mat = np.zeros((len(enc), max(width, 1)), np.uint8)
         for i, e in enumerate(enc):
             mat[i, :len(e)] = e
         ragged = len(enc) > 0 and int(lens.min()) != width
-        return mat, (lens if ragged else None)
+        return mat, (lens if ragged else None), width
+
+    def _reads_codes(self, reads):
+        """list[str] | ndarray -> (uint8 [N, width] numpy codes, int32 lens or None)."""
+        if isinstance(reads, np.ndarray):
+            return np.ascontiguousarray(reads, np.uint8), None
+        mat, lens, _ = self._encode_batch(reads, self.matcher.encode)
+        return mat, lens
 
     def _reads_tensor(self, reads):
         """list[str] | ndarray | tensor -> (uint8 [N, stride] on the device, lens or None)."""
@@ -54,14 +61,8 @@ class SMEM:
             return reads, None
         if isinstance(reads, np.ndarray):
             return torch.as_tensor(np.ascontiguousarray(reads, np.uint8)).to(ix_dev), None
-        enc = [self.matcher.encode(r) for r in reads]
-        lens = np.asarray([len(e) for e in enc], np.int32)
-        width = int(lens.max()) if len(enc) else 1
-        mat = np.zeros((len(enc), max(width, 1)), np.uint8)
-        for i, e in enumerate(enc):
-            mat[i, :len(e)] = e
-        ragged = len(enc) > 0 and int(lens.min()) != width
-        return torch.as_tensor(mat).to(ix_dev), (torch.as_tensor(lens).to(ix_dev) if ragged else None)
+        mat, lens, _ = self._encode_batch(reads, self.matcher.encode)
+        return torch.as_tensor(mat).to(ix_dev), (torch.as_tensor(lens).to(ix_dev) if lens is not None else None)
 
     def _mode_index(self, mode):
         if mode == "rmi":
@@ -94,14 +95,8 @@ class SMEM:
         ix = self.matcher.index(self.lut.lut_size)
         if isinstance(reads, (torch.Tensor, np.ndarray)):
             return ix.find_smems_split(reads, lens, minimum_length)
-        enc = [self.matcher.encode_lenient(r) for r in reads]
-        ln = np.asarray([len(e) for e in enc], np.int32)
-        width = int(ln.max()) if len(enc) else 0
-        mat = np.zeros((len(enc), max(width, 1)), np.uint8)
-        for i, e in enumerate(enc):
-            mat[i, :len(e)] = e
-        ragged = len(enc) > 0 and int(ln.min()) != width
-        if lens is None and ragged:
+        mat, ln, width = self._encode_batch(reads, self.matcher.encode_lenient)
+        if lens is None:
             lens = ln
         return ix.find_smems_split(mat if width else mat[:, :0], lens, minimum_length)
 
