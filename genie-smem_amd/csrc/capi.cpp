@@ -449,6 +449,33 @@ int genie_find_smems_long(const genie_index *ix, int32_t mode, const uint8_t *d_
                                   d_status, d_workspace, workspace_bytes, stream);
 }
 
+int64_t genie_find_smems_long_ex_workspace_bytes(int64_t N, int64_t total_bases, int64_t max_len, int32_t flags)
+{
+    if (N < 0 || total_bases < 0 || max_len < 0 || max_len > 0x7fffffffll) return (int64_t)GENIE_E_INVALID;
+    if (flags & ~(GENIE_READS_BOTH_STRANDS | GENIE_READS_SPLIT_BREAKS)) return (int64_t)GENIE_E_INVALID;
+    return find_smems_long_ex_workspace_bytes(N, total_bases, flags);
+}
+
+int genie_find_smems_long_ex(const genie_index *ix, int32_t mode, int32_t flags, const uint8_t *d_bases, const int64_t *d_read_offsets,
+                             int64_t N, int64_t total_bases, int64_t max_len, int32_t min_len, int64_t *d_offsets, int32_t *d_rows,
+                             int64_t out_cap_rows, int32_t *d_status, void *d_workspace, int64_t workspace_bytes, void *stream)
+{
+    // argument checks first: they need no device image
+    if (!ix) return GENIE_E_INVALID;
+    if (N < 0 || total_bases < 0 || max_len < 0 || max_len > 0x7fffffffll || out_cap_rows < 0 || !d_offsets ||
+        (N > 0 && (!d_read_offsets || !d_rows || !d_workspace)) || (total_bases > 0 && !d_bases))
+        return GENIE_E_INVALID;
+    if (mode < GENIE_MODE_BWA || mode > GENIE_MODE_RMI) return GENIE_E_INVALID;
+    if (flags & ~(GENIE_READS_BOTH_STRANDS | GENIE_READS_SPLIT_BREAKS)) return GENIE_E_INVALID;
+    if ((flags & GENIE_READS_SPLIT_BREAKS) && mode != GENIE_MODE_BWA) return GENIE_E_INVALID;
+    if ((reinterpret_cast<uintptr_t>(d_rows) & 15) != 0 || (reinterpret_cast<uintptr_t>(d_workspace) & 255) != 0) return GENIE_E_INVALID;
+    if (N > 0 && workspace_bytes < find_smems_long_ex_workspace_bytes(N, total_bases, flags)) return GENIE_E_CAPACITY;
+    int rc = ready(ix);
+    if (rc || (rc = mode_tables(ix, mode))) return rc;
+    return launch_find_smems_long_ex(ix, mode, flags, d_bases, d_read_offsets, N, total_bases, max_len, min_len, d_offsets, d_rows,
+                                     out_cap_rows, d_status, d_workspace, workspace_bytes, stream);
+}
+
 static int find_smems_packed_any(const genie_index *ix, int32_t mode, const uint8_t *d_reads2bit, const int32_t *d_lens, int64_t N,
                                  int32_t stride_bytes, int32_t fixed_len, int32_t min_len, uint8_t *d_counts8, uint8_t *d_status8,
                                  void *d_rows, int64_t out_cap_rows, int64_t *d_totals, int64_t *d_escapes, int64_t cap_escapes,

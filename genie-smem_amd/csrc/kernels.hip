@@ -1313,5 +1313,6 @@ int launch_locate(const genie_index *ix, const int32_t *d_lohi, int32_t stride, 
 // genie_find_smems_split: segments of reads with breaks through the pipeline above
 #include "split_reads.inc"
 #include "long_reads.inc"
+#include "long_units.inc"
 
 }  // namespace genie

@@ -395,10 +395,16 @@ class GenieIndex:
         return self._run_csr("genie_find_smems_split", (_ptr(reads), _ptr(lens), n_reads, stride, fixed, int(min_len)),
                              n_reads, int(rows_hint) if rows_hint else n_reads * max(8, fixed // 6), (_ptr(ws), ws_bytes))
 
-    def find_smems_long(self, mode, bases, read_offsets, min_len=1, rows_hint=None):
+    def find_smems_long(self, mode, bases, read_offsets, min_len=1, rows_hint=None, both_strands=False, split_breaks=False):
         """SMEMs of reads of any length (genie_find_smems_long) -> (offsets int64[N+1], smems int32[S,4], status).
         bases: uint8 codes of all reads back to back; read_offsets: int64[N+1], read r = bases[read_offsets[r] ..
-        read_offsets[r+1]).  Either may be on the device or the host.  Rows and status as find_smems."""
+        read_offsets[r+1]).  Either may be on the device or the host.  Rows and status as find_smems.
+        both_strands / split_breaks (genie_find_smems_long_ex): with both_strands the result covers 2N strand-reads,
+        interleaved as find_smems_both (2i is read i, 2i + 1 its reverse complement, rows in its own coordinates); with
+        split_breaks (mode "bwa" only) codes > 3 and bases the reference lacks cut a strand-read into segments, as
+        find_smems_split."""
+        if split_breaks and mode != "bwa":
+            raise ValueError("split_breaks needs mode 'bwa' (genie_find_smems_split has no other traversal)")
         self._need_device()
         bases = self._as_dev(bases, torch.uint8).reshape(-1)
         read_offsets = self._as_dev(read_offsets, torch.int64).reshape(-1)
@@ -410,10 +416,18 @@ class GenieIndex:
         max_len = min(max(max_len, 0), 2**31 - 1)
         if total == 0:
             bases = torch.zeros(1, dtype=torch.uint8, device=self.device)
-        ws, ws_bytes = self._workspace("genie_find_smems_long_workspace_bytes", n_reads, total, max_len)
-        return self._run_csr("genie_find_smems_long", (N.MODES[mode], _ptr(bases), _ptr(read_offsets), n_reads, total,
-                                                       max_len, int(min_len)),
-                             n_reads, int(rows_hint) if rows_hint else max(8 * n_reads, total // 6), (_ptr(ws), ws_bytes))
+        if not both_strands and not split_breaks:
+            ws, ws_bytes = self._workspace("genie_find_smems_long_workspace_bytes", n_reads, total, max_len)
+            return self._run_csr("genie_find_smems_long", (N.MODES[mode], _ptr(bases), _ptr(read_offsets), n_reads, total,
+                                                           max_len, int(min_len)),
+                                 n_reads, int(rows_hint) if rows_hint else max(8 * n_reads, total // 6), (_ptr(ws), ws_bytes))
+        flags = (N.READS_BOTH_STRANDS if both_strands else 0) | (N.READS_SPLIT_BREAKS if split_breaks else 0)
+        strands = 2 if both_strands else 1
+        ws, ws_bytes = self._workspace("genie_find_smems_long_ex_workspace_bytes", n_reads, total, max_len, flags)
+        return self._run_csr("genie_find_smems_long_ex", (N.MODES[mode], flags, _ptr(bases), _ptr(read_offsets), n_reads, total,
+                                                          max_len, int(min_len)),
+                             strands * n_reads, int(rows_hint) if rows_hint else strands * max(8 * n_reads, total // 6),
+                             (_ptr(ws), ws_bytes))
 
     def find_smems_packed(self, mode, packed, max_len, lens=None, min_len=1, rows_hint=None, row_bytes=8):
         """genie_find_smems_packed (or, `row_bytes` = 6, genie_find_smems_packed6): 2-bit packed reads (packing.pack_reads;

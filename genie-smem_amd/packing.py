@@ -87,8 +87,8 @@ def unpack_rows(counts8, rows8, escapes=None, row_bytes=8):
 def reverse_complement(codes, lens=None):
     """The reverse complement of every read: row i's first lens[i] codes (all of them without `lens`) reversed, each code c
     mapped to c ^ 3 (3 - c on 0..3; a code > 3 stays > 3); bytes past a read's length are left as they are.  codes: uint8
-    [N, L] (or one read, [L]) -> a new array of the same shape.  Strand-read 2i + 1 of genie_find_smems_both is
-    reverse_complement(read i)."""
+    [N, L] (or one read, [L]) -> a new array of the same shape.  Strand-read 2i + 1 of genie_find_smems_both, and of
+    genie_find_smems_long_ex with GENIE_READS_BOTH_STRANDS, is reverse_complement(read i)."""
     codes = np.asarray(codes, np.uint8)
     if codes.ndim == 1:
         return reverse_complement(codes[None, :], None if lens is None else np.asarray(lens).reshape(1))[0]

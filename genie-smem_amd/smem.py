@@ -109,18 +109,22 @@ class SMEM:
         t, l2 = self._reads_tensor(reads)
         return ix.find_smems_both(mode, t, lens if lens is not None else l2, minimum_length)
 
-    def find_smems_long(self, reads, minimum_length=1, mode="bwa"):
+    def find_smems_long(self, reads, minimum_length=1, mode="bwa", both_strands=False, split_breaks=False):
         """SMEMs of reads of any length (genie_find_smems_long).  reads: list[str], or (bases, read_offsets) -- uint8 codes
-        back to back and int64[N+1] offsets, numpy or torch.  -> (offsets, smems[S, 4], status) like find_smems_bwa."""
+        back to back and int64[N+1] offsets, numpy or torch.  -> (offsets, smems[S, 4], status) like find_smems_bwa.
+        both_strands: 2N strand-reads as find_smems_both (2i read i, 2i + 1 its reverse complement).  split_breaks (mode
+        "bwa"): breaks cut the reads as find_smems_split; strings are then encoded with ExactMatch.encode_lenient."""
         ix = self.matcher.index(self.lut.lut_size)
         if isinstance(reads, tuple):
             bases, read_offsets = reads
-            return ix.find_smems_long(mode, bases, read_offsets, minimum_length)
-        enc = [self.matcher.encode(r) for r in reads]
+            return ix.find_smems_long(mode, bases, read_offsets, minimum_length, both_strands=both_strands,
+                                      split_breaks=split_breaks)
+        encode = self.matcher.encode_lenient if split_breaks else self.matcher.encode
+        enc = [encode(r) for r in reads]
         offs = np.zeros(len(enc) + 1, np.int64)
         offs[1:] = np.cumsum([len(e) for e in enc]) if enc else []
         bases = np.concatenate(enc).astype(np.uint8) if enc else np.zeros(0, np.uint8)
-        return ix.find_smems_long(mode, bases, offs, minimum_length)
+        return ix.find_smems_long(mode, bases, offs, minimum_length, both_strands=both_strands, split_breaks=split_breaks)
 
     def find_smems_lut(self, reads, lens=None):
         return self._find("lut", reads, lens, 1)

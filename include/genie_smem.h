@@ -314,6 +314,40 @@ int genie_find_smems_long(const genie_index *ix, int32_t mode, const uint8_t *d_
                           int64_t *d_offsets, int32_t *d_rows, int64_t out_cap_rows, int32_t *d_status,
                           void *d_workspace, int64_t workspace_bytes, void *stream);
 
+/* genie_find_smems_long with both strands and / or breaks.  Inputs as genie_find_smems_long (CSR reads of any length,
+ * total_bases / max_len as host-side bounds, the same offset check on the device); `flags` ORs
+ *   GENIE_READS_BOTH_STRANDS  the output covers 2N strand-reads, interleaved as genie_find_smems_both: strand-read 2i is
+ *                             read i, 2i + 1 is rc(read i) (reversed, code c -> 3 - c, a code > 3 stays what it is);
+ *                             d_offsets[2N+1], d_status[2N]; strand-1 rows keep positions in the reverse complement;
+ *   GENIE_READS_SPLIT_BREAKS  the semantics of genie_find_smems_split: a break is a position whose code is > 3 or whose
+ *                             base (on a reversed strand: its complement) never occurs in the reference; a strand-read's
+ *                             SMEMs are those of its segments, in its own order, each with the BWA traversal and min_len,
+ *                             start / end in the whole strand-read; every status GENIE_READ_OK; an empty or all-break
+ *                             strand-read has no rows.  Only with GENIE_MODE_BWA (GENIE_E_INVALID otherwise).
+ * Let S = 2 with BOTH_STRANDS, else 1.  Defining properties, each byte for byte:
+ *   flags == 0         genie_find_smems_long itself (the workspace function returns the same number);
+ *   BOTH_STRANDS       genie_find_smems_long on the explicit batch [r0, rc(r0), r1, rc(r1), ...], every mode, status per
+ *                      strand-read -- and so genie_find_smems_both on reads of at most GENIE_MAX_READ_LEN bases;
+ *   SPLIT_BREAKS       genie_find_smems_split on reads of at most GENIE_MAX_READ_LEN bases;
+ *   both               SPLIT_BREAKS alone on that explicit interleaved batch.
+ * Rows past out_cap_rows are dropped and d_offsets[S N] keeps the true total; N = 0 writes d_offsets[0] = 0.  Unknown flag
+ * bits, bad pointers / sizes / alignment give GENIE_E_INVALID and a small workspace GENIE_E_CAPACITY, all before the device
+ * check; bad offsets GENIE_E_INVALID, found on the device.  The reverse complement is never written to memory as bytes.
+ * d_workspace: 256-byte aligned, genie_find_smems_long_ex_workspace_bytes(N, total_bases, max_len, flags) bytes: the
+ * long-read pipeline for S total_bases positions and max(1, S N) units (a unit is one strand of one segment of one read),
+ * i.e. about 17.3 S bytes per base and 64 S per read; with SPLIT_BREAKS one more unit per 32 positions, the unit table
+ * and the segmentation's counts: about 20.1 S bytes per base and 92 S per read.
+ * Synchronisations of `stream`: without SPLIT_BREAKS one, after the offset check (as genie_find_smems_long).  With it one
+ * more to read the number of units, and one per extra pass when the units outnumber what the workspace holds (passes of
+ * consecutive units, each of at least S N). */
+#define GENIE_READS_BOTH_STRANDS 1
+#define GENIE_READS_SPLIT_BREAKS 2
+int64_t genie_find_smems_long_ex_workspace_bytes(int64_t N, int64_t total_bases, int64_t max_len, int32_t flags);
+int genie_find_smems_long_ex(const genie_index *ix, int32_t mode, int32_t flags, const uint8_t *d_bases,
+                             const int64_t *d_read_offsets, int64_t N, int64_t total_bases, int64_t max_len,
+                             int32_t min_len, int64_t *d_offsets, int32_t *d_rows, int64_t out_cap_rows,
+                             int32_t *d_status, void *d_workspace, int64_t workspace_bytes, void *stream);
+
 /* The same discovery for callers on the far side of a host link (SMEM.find_smems_* on host arrays): 2-bit packed reads in,
  * 8-byte rows out -- 40 instead of 150 bytes per 150-base read over PCIe, 8 instead of 16 per SMEM.  Reads of at most 255
  * bases.  Row r of d_reads2bit = stride_bytes bytes (a multiple of 4, >= 4 * ceil(max length / 16)): byte i holds bases
