@@ -17,6 +17,7 @@
 #include <cstdlib>
 #include <mutex>
 #include <string>
+#include <unordered_map>
 
 #include "genie_internal.h"
 
@@ -658,12 +659,11 @@ __global__ void __launch_bounds__(kScanBlock) compact_scatter(const int32_t *__r
     if (i < N) {
         offsets[i] = (long long)base;
         if (i == N - 1) offsets[N] = (long long)(base + v);
-        if (!out) {
-            /* offsets only */
-        } else if ((long long)(base + v) > out_cap_rows) {
-            /* rows beyond the capacity are dropped: the caller compares offsets[N] with it */
-        } else {
-            for (unsigned int t = 0; t < (unsigned int)v; t++) out[base + t] = slots[i * (long long)cap + t];
+        if (out) {
+            // rows beyond the capacity are dropped, row by row as in the CSR entry points: the caller compares offsets[N] with it
+            const long long room = out_cap_rows - (long long)base;
+            const unsigned int fit = room <= 0 ? 0u : (room < (long long)v ? (unsigned int)room : (unsigned int)v);
+            for (unsigned int t = 0; t < fit; t++) out[base + t] = slots[i * (long long)cap + t];
         }
     }
 }
@@ -832,11 +832,38 @@ struct FindRequest : FindBatch {
     explicit FindRequest(const FindBatch &b) : FindBatch(b) {}
 };
 
+// A kernel that asks for more dynamic LDS than the default limit has the limit raised before its launch.  The limit belongs
+// to the kernel, not to the launch: every stream and host thread shares it.  So it is always raised to the same value, the
+// most a block of that kernel can have (the LDS of a CU less the kernel's static LDS), never to the size of one launch --
+// two threads with reads of different lengths would otherwise lower each other's limit between the set and the launch.
+constexpr int kLdsBytes = 160 * 1024;
+std::mutex g_lds_mu;
+std::unordered_map<const void *, int> g_lds_limit;      // kernel -> that value, asked of the runtime once
+
+template <class Kernel>
+int allow_large_lds(Kernel k)
+{
+    const void *fn = reinterpret_cast<const void *>(k);
+    int limit;
+    {
+        std::lock_guard<std::mutex> lk(g_lds_mu);
+        auto it = g_lds_limit.find(fn);
+        if (it == g_lds_limit.end()) {
+            hipFuncAttributes attr;
+            HIP_TRY(hipFuncGetAttributes(&attr, fn));
+            it = g_lds_limit.emplace(fn, kLdsBytes - (int)attr.sharedSizeBytes).first;
+        }
+        limit = it->second;
+    }
+    HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, limit));
+    return GENIE_OK;
+}
+
 // K_A: every instance asks for more dynamic LDS than the default limit
 template <class Kernel, class... Args>
 int launch_match_table(Kernel km, const Geometry &g, hipStream_t s, Args... args)
 {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(km), hipFuncAttributeMaxDynamicSharedMemorySize, g.lds));
+    if (int rc = allow_large_lds(km)) return rc;
     LAUNCH(km, dim3(g.grid), dim3(g.block), g.lds, s, args...);
     return GENIE_OK;
 }
@@ -901,7 +928,7 @@ int launch_pipeline(const genie_index *ix, const Geometry &g, const FindRequest 
     } else {                                 // one lane per read, rows staged in LDS
         auto kb = traverse_kernel<MODE>;
         const int lds_b = tb * g.fwd_lds;
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kb), hipFuncAttributeMaxDynamicSharedMemorySize, lds_b));
+        if ((rc = allow_large_lds(kb))) return rc;
         LAUNCH(kb, dim3((unsigned)((N + tb - 1) / tb)), dim3(tb), lds_b, s, ix->dev, lens, N,
                r.fixed_len, r.min_len, ws.fwd, g.fwd_stride, g.fwd_lds, cnt, ws.kj, g.kj_row, head, head_stride,
                r.offsets ? g.kj_row : r.cap, st, bsums, r.counts8, r.status8);
@@ -1098,8 +1125,7 @@ int launch_sa_interval(const genie_index *ix, const uint8_t *d_pats, const int32
     const int lds = dir_bytes + waves * per_wave;
     const int cus = ix->num_cus > 0 ? ix->num_cus : 256;
     long long grid = std::min<long long>((N + waves - 1) / waves, (long long)cus * std::max(1, (160 * 1024) / lds));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(sa_interval_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    if (int rc = allow_large_lds(sa_interval_kernel)) return rc;
     LAUNCH(sa_interval_kernel, dim3((unsigned)grid), dim3(waves * kWave), lds, (hipStream_t)stream, ix->dev,
            d_pats, d_lens, (long long)N, stride, fixed_len, Lmax, reinterpret_cast<int2 *>(d_out));
     return GENIE_OK;

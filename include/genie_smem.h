@@ -357,8 +357,8 @@ int genie_find_smems_long_ex(const genie_index *ix, int32_t mode, int32_t flags,
  *                 rows start at the sum of the counts before it), 8 bytes each: byte 0 start, byte 1 end, bytes 2..3
  *                 span = hi - lo (little endian), bytes 4..7 lo.  span == 0xFFFF means "65535 or more": that row's
  *                 index and its hi are also appended to d_escapes (int64 pairs: row, hi; unordered);
- *   d_totals[0]   rows in all (rows beyond out_cap_rows were dropped);  d_totals[1] = escapes in all (compare with
- *                 cap_escapes and call again with a larger list if it is exceeded).
+ *   d_totals[0]   rows in all (rows beyond out_cap_rows were dropped);  d_totals[1] = escapes in all, of the rows that
+ *                 were not dropped (compare with cap_escapes and call again with a larger list if it is exceeded).
  * The reference has no counterpart (its API is in-process Python strings); genie-smem_amd/packing.py holds the host side:
  * pack_reads() and unpack_rows() give back exactly the int32 (start, end, lo, hi) rows of genie_find_smems_csr. */
 int genie_find_smems_packed(const genie_index *ix, int32_t mode, const uint8_t *d_reads2bit, const int32_t *d_lens, int64_t N,
@@ -369,14 +369,17 @@ int genie_find_smems_packed(const genie_index *ix, int32_t mode, const uint8_t *
 /* The same with 6-byte rows (another quarter off the bytes that travel back: 66 instead of 88 per 150-base read), for
  * references below 2^24 bases (GENIE_E_TOO_LONG otherwise): byte 0 start, byte 1 end, bytes 2..4 lo (24 bits, little endian),
  * byte 5 span = hi - lo, 0xFF meaning "255 or more" (that row's index and hi are on d_escapes).  d_rows6: 2-byte aligned.
- * Everything else as genie_find_smems_packed; packing.unpack_rows(..., row_bytes=6) is the host side. */
+ * Everything else as genie_find_smems_packed; packing.unpack_rows(..., row_bytes=6) is the host side.
+ * Alignment (GENIE_E_INVALID otherwise): d_reads2bit 4 bytes (rows of 32-bit words), d_rows8 8, d_totals 8. */
 int genie_find_smems_packed6(const genie_index *ix, int32_t mode, const uint8_t *d_reads2bit, const int32_t *d_lens, int64_t N,
                              int32_t stride_bytes, int32_t fixed_len, int32_t min_len, uint8_t *d_counts8, uint8_t *d_status8,
                              void *d_rows6, int64_t out_cap_rows, int64_t *d_totals, int64_t *d_escapes, int64_t cap_escapes,
                              void *d_workspace, int64_t workspace_bytes, void *stream);
 
 /* Compact the slotted output to CSR: d_offsets[N+1] (exclusive prefix sum of min(count,cap))
- * and d_out[total*4].  d_tmp: scratch of genie_compact_tmp_bytes(N) bytes. */
+ * and d_out[total*4].  d_out may be NULL (offsets only: the sizing call); rows beyond out_cap_rows are dropped
+ * (d_offsets[N] still holds the true total).  d_slots and d_out 16-byte aligned; d_tmp: 8-byte aligned scratch of
+ * genie_compact_tmp_bytes(N) bytes. */
 int64_t genie_compact_tmp_bytes(int64_t N);
 int genie_compact_smems(const int32_t *d_counts, const int32_t *d_slots, int64_t N, int32_t cap,
                         int64_t *d_offsets, int32_t *d_out, int64_t out_cap_rows, void *d_tmp, void *stream);
