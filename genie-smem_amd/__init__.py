@@ -12,7 +12,7 @@ from .lut import LUT
 from .rmi import RMI
 from .rmi_lut import RMI_LUT
 from .smem import SMEM, create_query_from_ref, create_random_query
-from . import packing, parallel
+from . import packing, parallel, text_reads
 
-__all__ = ["ExactMatch", "LUT", "RMI", "RMI_LUT", "SMEM", "GenieIndex", "parallel", "packing", "_native",
+__all__ = ["ExactMatch", "LUT", "RMI", "RMI_LUT", "SMEM", "GenieIndex", "parallel", "packing", "text_reads", "_native",
            "create_query_from_ref", "create_random_query"]

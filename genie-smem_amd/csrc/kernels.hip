@@ -1340,5 +1340,6 @@ int launch_locate(const genie_index *ix, const int32_t *d_lohi, int32_t stride, 
 #include "split_reads.inc"
 #include "long_reads.inc"
 #include "long_units.inc"
+#include "text_reads.inc"
 
 }  // namespace genie

@@ -86,6 +86,17 @@ class ExactMatch:
         codes = self._enc[np.frombuffer(seq.encode("latin-1", "replace"), np.uint8)]
         return np.where(codes == 255, np.uint8(4), codes).astype(np.uint8)
 
+    def byte_codes(self, fold_case=False):
+        """The 256-entry table behind encode_lenient, for text_reads.reads_from_text: the code of every byte of the
+        reference's alphabet, 4 for any other.  fold_case: a lower-case letter gets the code of its upper-case one."""
+        if self._codes is None:
+            self.load_ref_sequence()
+        table = np.where(self._enc == 255, np.uint8(4), self._enc).astype(np.uint8)
+        if fold_case:
+            lower = np.arange(ord("a"), ord("z") + 1)
+            table[lower] = np.where(table[lower] == 4, table[lower - 32], table[lower])
+        return table
+
     def decode(self, codes):
         return "".join(self.alphabet[int(c)] for c in codes)
 

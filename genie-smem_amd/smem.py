@@ -20,6 +20,7 @@ from . import _native as N
 from .exact_match import ExactMatch
 from .lut import LUT
 from .rmi_lut import RMI_LUT
+from .text_reads import reads_from_text
 
 
 class SMEM:
@@ -125,6 +126,44 @@ class SMEM:
         offs[1:] = np.cumsum([len(e) for e in enc]) if enc else []
         bases = np.concatenate(enc).astype(np.uint8) if enc else np.zeros(0, np.uint8)
         return ix.find_smems_long(mode, bases, offs, minimum_length, both_strands=both_strands, split_breaks=split_breaks)
+
+    def find_smems_text(self, data, fmt="lines", mode="bwa", minimum_length=1, both_strands=False, split_breaks=True,
+                        fold_case=False):
+        """SMEMs of the reads in a text: every line a read (fmt "lines") or four-line FASTQ records (fmt "fastq").  data:
+        bytes-like, numpy uint8 or torch uint8, on the host or the device.  The text is cut into reads and translated on the
+        device (text_reads.reads_from_text with ExactMatch.byte_codes(fold_case): the codes encode_lenient gives), then
+        searched as find_smems_long((bases, read_offsets), ...) with the same options.  -> (offsets, smems[S, 4], status)."""
+        return self._find_text(data, fmt, False, mode, minimum_length, both_strands, split_breaks, fold_case)[:3]
+
+    def _find_text(self, data, fmt, partial, mode, minimum_length, both_strands, split_breaks, fold_case):
+        """find_smems_text on one chunk -> (offsets, smems, status, reads, consumed bytes)."""
+        ix = self.matcher.index(self.lut.lut_size)
+        bases, read_offsets, consumed = reads_from_text(data, fmt, self.matcher.byte_codes(fold_case), partial, ix.device)
+        res = ix.find_smems_long(mode, bases, read_offsets, minimum_length, both_strands=both_strands, split_breaks=split_breaks)
+        return res + (read_offsets.numel() - 1, consumed)
+
+    def iter_fastq_smems(self, path, chunk_bytes=64 << 20, mode="bwa", minimum_length=1, both_strands=False, split_breaks=True,
+                         fold_case=False):
+        """find_smems_text over a FASTQ file of any size, a chunk at a time: yields (offsets, smems, status) of the records that
+        are complete in each chunk of about chunk_bytes bytes; the unfinished record at a chunk's end is carried into the next
+        one.  A chunk that holds no complete record grows by another chunk_bytes until it does (or the file ends).  The
+        concatenated reads are those of find_smems_text on the whole file."""
+        chunk_bytes = max(int(chunk_bytes), 1)
+        opts = (mode, minimum_length, both_strands, split_breaks, fold_case)
+        with open(path, "rb") as fh:
+            carry = b""
+            while True:
+                fresh = fh.read(chunk_bytes)
+                last = len(fresh) < chunk_bytes                     # a short read of a regular file: its end
+                buf = carry + fresh
+                if last:
+                    if buf:
+                        yield self._find_text(buf, "fastq", False, *opts)[:3]
+                    return
+                offsets, smems, status, n_reads, consumed = self._find_text(buf, "fastq", True, *opts)
+                carry = buf[consumed:]                              # no complete record: everything, and the chunk grows
+                if n_reads:
+                    yield offsets, smems, status
 
     def find_smems_lut(self, reads, lens=None):
         return self._find("lut", reads, lens, 1)

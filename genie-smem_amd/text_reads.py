@@ -1,0 +1,92 @@
+"""Reads from text on the device (genie_reads_from_text): the bytes of a file with one read per line, or of a FASTQ file
+with four-line records, become base codes back to back and int64 offsets -- the (bases, read_offsets) that
+GenieIndex.find_smems_long takes.  The text travels over the host link as it is, one byte per base; nothing is encoded on
+the host."""
+import ctypes as C
+import warnings
+
+import numpy as np
+import torch
+
+from . import _native as N
+
+
+class TextFormatError(ValueError):
+    """A malformed FASTQ record (GENIE_E_INVALID found on the device); `record` is the first one."""
+
+    def __init__(self, record, fmt):
+        self.record = int(record)
+        super().__init__(f"{fmt} text: record {self.record} is malformed (a header line must start with '@', a separator "
+                         "line with '+', and without partial=True the last record must be complete)")
+
+
+def _text_tensor(data, device):
+    """bytes-like | numpy uint8 | torch uint8 (host or device) -> flat uint8 tensor on `device`."""
+    if isinstance(data, torch.Tensor):
+        if data.dtype != torch.uint8:
+            raise TypeError("text tensor must be uint8")
+        return data.reshape(-1).to(device).contiguous()
+    if isinstance(data, np.ndarray):
+        if data.dtype != np.uint8:
+            raise TypeError("text array must be uint8")
+        a = np.ascontiguousarray(data).reshape(-1)
+    else:
+        a = np.frombuffer(data, np.uint8)                   # bytes, bytearray, memoryview, mmap
+    if a.size == 0:
+        return torch.zeros(0, dtype=torch.uint8, device=device)
+    with warnings.catch_warnings():                         # a read-only buffer (bytes): it is only read, by the upload
+        warnings.simplefilter("ignore", UserWarning)
+        return torch.from_numpy(a).to(device)
+
+
+def reads_from_text(data, fmt="lines", code_of_byte=None, partial=False, device="cuda"):
+    """-> (bases uint8[total_bases], read_offsets int64[N + 1], consumed): two tensors on `device` and a byte count.
+    data: bytes-like, numpy uint8 or torch uint8 (host or device).  fmt: "lines" (every line a read) or "fastq" (four-line
+    records).  code_of_byte: 256 uint8 entries (ExactMatch.byte_codes(); default A C G T -> 0 1 2 3, anything else 4).
+    partial: the text is a chunk of a longer stream -- the unfinished last line (record) is left alone and `consumed` says
+    where it starts.  Two native calls: one sizes the outputs, one fills them.  A malformed FASTQ raises TextFormatError."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("reads_from_text runs on an MI355X only (no CPU fallback); device is " + str(device))
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    if fmt not in N.TEXT_FORMATS:
+        raise ValueError(f"fmt must be one of {sorted(N.TEXT_FORMATS)}, got {fmt!r}")
+    if code_of_byte is None:
+        code_of_byte = default_byte_codes()
+    table = np.ascontiguousarray(code_of_byte, np.uint8)
+    if table.shape != (256,):
+        raise ValueError("code_of_byte needs 256 entries")
+    lib = N.lib()
+    text = _text_tensor(data, device)
+    nbytes = text.numel()
+    flags = N.TEXT_PARTIAL if partial else 0
+    out5 = (C.c_int64 * 5)()
+
+    def call(bases, offsets, cap_bases, cap_reads):
+        tmp_bytes = int(lib.genie_reads_from_text_tmp_bytes(nbytes, cap_reads))
+        tmp = torch.empty(max(tmp_bytes, 256), dtype=torch.uint8, device=device)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else C.c_void_p(0)
+        out5[4] = -1
+        with torch.cuda.device(device):
+            rc = lib.genie_reads_from_text(ptr(text), nbytes, N.TEXT_FORMATS[fmt], flags, table.ctypes.data_as(C.c_void_p),
+                                           ptr(bases), cap_bases, ptr(offsets), cap_reads, out5, ptr(tmp), tmp_bytes,
+                                           C.c_void_p(torch.cuda.current_stream(device).cuda_stream))
+        if rc == -1 and out5[4] >= 0:
+            raise TextFormatError(out5[4], fmt)
+        N.check(rc, "genie_reads_from_text")
+
+    call(None, None, 0, 0)
+    n_reads, total = int(out5[0]), int(out5[1])
+    bases = torch.empty(max(total, 1), dtype=torch.uint8, device=device)     # a pointer even for no bases
+    offsets = torch.empty(n_reads + 1, dtype=torch.int64, device=device)
+    call(bases, offsets, total, n_reads)
+    return bases[:total], offsets, int(out5[3])
+
+
+def default_byte_codes():
+    """A C G T -> 0 1 2 3, every other byte 4."""
+    table = np.full(256, 4, np.uint8)
+    for i, ch in enumerate(b"ACGT"):
+        table[ch] = i
+    return table

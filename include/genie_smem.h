@@ -348,6 +348,50 @@ int genie_find_smems_long_ex(const genie_index *ix, int32_t mode, int32_t flags,
                              int32_t min_len, int64_t *d_offsets, int32_t *d_rows, int64_t out_cap_rows,
                              int32_t *d_status, void *d_workspace, int64_t workspace_bytes, void *stream);
 
+/* Reads from TEXT, on the device: the bytes of a file of reads -> the d_bases / d_read_offsets that genie_find_smems_long_ex
+ * takes.  The reference has no counterpart (its reads are Python strings); this replaces encoding every string on the host.
+ * Lines.  A line ends at a '\n' (0x0A), which is not part of it; if the line is then not empty and its last byte is '\r',
+ *   that one byte is dropped too.  The bytes behind the last '\n' are the tail: without GENIE_TEXT_PARTIAL a non-empty tail
+ *   is one more line (no '\r' is dropped from it), with GENIE_TEXT_PARTIAL the tail is not a line.  An empty text has no
+ *   lines, "\n\n" two empty ones.
+ * format GENIE_TEXT_LINES: read r is line r, N = the number of lines; an empty line is a read of length 0.
+ * format GENIE_TEXT_FASTQ: record r is lines 4r .. 4r+3, read r is line 4r+1, N = floor(lines / 4).  Line 4r must be non-empty
+ *   and start with '@', line 4r+2 non-empty and start with '+': otherwise GENIE_E_INVALID (found on the device) and out5[4] =
+ *   the first such record.  Quality lines are not looked at (they may start with '@' and hold '+').  Without
+ *   GENIE_TEXT_PARTIAL a number of lines that is no multiple of 4 is GENIE_E_INVALID with out5[4] = N, the incomplete record;
+ *   with it the lines of an incomplete last record are not consumed.  Sequences wrapped over several lines, and FASTA, are
+ *   NOT handled: every record is exactly four lines.
+ * Translation: an output byte is code_of_byte[b] where that is 0..3, else 4 (a break for GENIE_READS_SPLIT_BREAKS,
+ *   GENIE_READ_BAD_BASE without it); never above 4.  Every byte value is legal inside a line except '\n'.  code_of_byte is a
+ *   host array of 256 entries, read before the call returns (it travels as a kernel argument).
+ * Output: d_bases = the reads' codes back to back, d_read_offsets[0 .. N] their int64 offsets, d_read_offsets[0] = 0;
+ *   out5 (host) = {N, total_bases, longest read, consumed_bytes, first bad record or -1}.  consumed_bytes is text_bytes
+ *   without GENIE_TEXT_PARTIAL; with it, where the first line that was not consumed starts (GENIE_TEXT_LINES: behind the last
+ *   '\n'; GENIE_TEXT_FASTQ: the start of line 4N), so that parsing text[consumed_bytes:] followed by the rest of the stream
+ *   continues exactly where this chunk stopped.
+ * Sizing: with d_bases and d_read_offsets both NULL only out5 is produced (the capacities are then not looked at).
+ *   Otherwise N > cap_reads or total_bases > cap_bases gives GENIE_E_CAPACITY: out5 holds the true values, d_bases is not
+ *   written and nothing is written outside d_bases[0 .. cap_bases) and d_read_offsets[0 .. cap_reads] (whose contents are then
+ *   undefined).  cap_bases = text_bytes and cap_reads = text_bytes always suffice.  A malformed record is reported before
+ *   a capacity.
+ * Checked before any device work: GENIE_E_INVALID for a null d_text with text_bytes > 0, a null code_of_byte or out5, a negative
+ *   size, an unknown format or flag bit, exactly one of d_bases / d_read_offsets null, d_read_offsets not 8-byte aligned;
+ *   then GENIE_E_CAPACITY for a d_tmp that is null, not 256-byte aligned or smaller than
+ *   genie_reads_from_text_tmp_bytes(text_bytes, cap_reads) (32 bytes per 4096 of text and 8 per 1024 reads of capacity;
+ *   GENIE_E_INVALID for a negative argument).  d_text and d_bases need no alignment.
+ * All launches go to `stream` on the current device; the call synchronises it exactly once, at the end (out5 has to reach
+ *   the host).  Three streaming passes over the text, nothing per read; the output is a function of the inputs alone. */
+#define GENIE_TEXT_LINES 0      /* every line is a read */
+#define GENIE_TEXT_FASTQ 1      /* records of four lines; line 2 of each is the read */
+#define GENIE_TEXT_PARTIAL 1    /* flags: the text is a chunk of a longer stream */
+int64_t genie_reads_from_text_tmp_bytes(int64_t text_bytes, int64_t cap_reads);
+int genie_reads_from_text(const uint8_t *d_text, int64_t text_bytes, int32_t format, int32_t flags,
+                          const uint8_t *code_of_byte /* host, 256 entries */,
+                          uint8_t *d_bases, int64_t cap_bases,
+                          int64_t *d_read_offsets, int64_t cap_reads,
+                          int64_t *out5 /* host */,
+                          void *d_tmp, int64_t tmp_bytes, void *stream);
+
 /* The same discovery for callers on the far side of a host link (SMEM.find_smems_* on host arrays): 2-bit packed reads in,
  * 8-byte rows out -- 40 instead of 150 bytes per 150-base read over PCIe, 8 instead of 16 per SMEM.  Reads of at most 255
  * bases.  Row r of d_reads2bit = stride_bytes bytes (a multiple of 4, >= 4 * ceil(max length / 16)): byte i holds bases
