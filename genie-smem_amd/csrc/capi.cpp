@@ -425,28 +425,18 @@ int genie_find_smems_split(const genie_index *ix, const uint8_t *d_reads, const 
                                    d_workspace, workspace_bytes, stream);
 }
 
+// the long call is the _ex call with no flags: its checks, in its order, and its launch
 int64_t genie_find_smems_long_workspace_bytes(int64_t N, int64_t total_bases, int64_t max_len)
 {
-    if (N < 0 || total_bases < 0 || max_len < 0 || max_len > 0x7fffffffll) return (int64_t)GENIE_E_INVALID;
-    return find_smems_long_workspace_bytes(N, total_bases);
+    return genie_find_smems_long_ex_workspace_bytes(N, total_bases, max_len, 0);
 }
 
 int genie_find_smems_long(const genie_index *ix, int32_t mode, const uint8_t *d_bases, const int64_t *d_read_offsets, int64_t N,
                           int64_t total_bases, int64_t max_len, int32_t min_len, int64_t *d_offsets, int32_t *d_rows,
                           int64_t out_cap_rows, int32_t *d_status, void *d_workspace, int64_t workspace_bytes, void *stream)
 {
-    // argument checks first: they need no device image
-    if (!ix) return GENIE_E_INVALID;
-    if (N < 0 || total_bases < 0 || max_len < 0 || max_len > 0x7fffffffll || out_cap_rows < 0 || !d_offsets ||
-        (N > 0 && (!d_read_offsets || !d_rows || !d_workspace)) || (total_bases > 0 && !d_bases))
-        return GENIE_E_INVALID;
-    if (mode < GENIE_MODE_BWA || mode > GENIE_MODE_RMI) return GENIE_E_INVALID;
-    if ((reinterpret_cast<uintptr_t>(d_rows) & 15) != 0 || (reinterpret_cast<uintptr_t>(d_workspace) & 255) != 0) return GENIE_E_INVALID;
-    if (N > 0 && workspace_bytes < find_smems_long_workspace_bytes(N, total_bases)) return GENIE_E_CAPACITY;
-    int rc = ready(ix);
-    if (rc || (rc = mode_tables(ix, mode))) return rc;
-    return launch_find_smems_long(ix, mode, d_bases, d_read_offsets, N, total_bases, max_len, min_len, d_offsets, d_rows, out_cap_rows,
-                                  d_status, d_workspace, workspace_bytes, stream);
+    return genie_find_smems_long_ex(ix, mode, 0, d_bases, d_read_offsets, N, total_bases, max_len, min_len, d_offsets, d_rows,
+                                    out_cap_rows, d_status, d_workspace, workspace_bytes, stream);
 }
 
 int64_t genie_find_smems_long_ex_workspace_bytes(int64_t N, int64_t total_bases, int64_t max_len, int32_t flags)

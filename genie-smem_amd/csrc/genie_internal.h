@@ -382,10 +382,7 @@ int64_t find_smems_split_workspace_bytes(int64_t N, int32_t max_len);
 int launch_find_smems_split(const genie_index *ix, const uint8_t *d_reads, const int32_t *d_lens, int64_t N, int32_t stride,
                             int32_t fixed_len, int32_t min_len, int64_t *d_offsets, int32_t *d_rows, int64_t out_cap_rows,
                             int32_t *d_status, void *d_ws, int64_t ws_bytes, void *stream);
-int64_t find_smems_long_workspace_bytes(int64_t N, int64_t total_bases);
-int launch_find_smems_long(const genie_index *ix, int32_t mode, const uint8_t *d_bases, const int64_t *d_read_offsets, int64_t N,
-                           int64_t total_bases, int64_t max_len, int32_t min_len, int64_t *d_offsets, int32_t *d_rows,
-                           int64_t out_cap_rows, int32_t *d_status, void *d_ws, int64_t ws_bytes, void *stream);
+// flags == 0: genie_find_smems_long
 int64_t find_smems_long_ex_workspace_bytes(int64_t N, int64_t total_bases, int32_t flags);
 int launch_find_smems_long_ex(const genie_index *ix, int32_t mode, int32_t flags, const uint8_t *d_bases, const int64_t *d_read_offsets,
                               int64_t N, int64_t total_bases, int64_t max_len, int32_t min_len, int64_t *d_offsets, int32_t *d_rows,

@@ -784,6 +784,19 @@ struct Carver {
     }
 };
 
+// Units per pass of a call that works through `total` units in passes: the largest count in [lo, total] whose pass layout
+// fits the workspace (fits(count); lo does, the caller sized the workspace for it), and no more than there are.
+template <class F>
+inline long long pass_size(long long lo, long long total, F fits)
+{
+    long long hi = std::max(lo, total);
+    while (lo < hi) {
+        const long long mid = lo + (hi - lo + 1) / 2;
+        if (fits(mid)) lo = mid; else hi = mid - 1;
+    }
+    return std::min(lo, total);
+}
+
 // block sums of the traversal kernels (CSR form): one 64-bit word per block; the smallest block holds 16 reads
 inline int64_t block_sums_bytes(int64_t N) { return (N / 16 + 3) * 8; }
 

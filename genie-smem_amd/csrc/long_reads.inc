@@ -1,20 +1,24 @@
-// long_reads.inc -- genie_find_smems_long: SMEMs of reads of any length, given as CSR (included by kernels.hip, inside
-// namespace genie; uses its launch plumbing and the match-statistics helpers of match_table_kernel.inc).
+// long_reads.inc -- the SMEM pipeline for reads of any length, over UNITS given as CSR (included by kernels.hip, inside
+// namespace genie; uses its launch plumbing and the match-statistics helpers of match_table_kernel.inc).  A unit is a run
+// of bases that is searched as one read: uoff[U + 1] are the units' offsets (prefix sums of their lengths), usrc[u] says
+// where unit u's bases come from, ushift[u] where it starts inside its read.  Without usrc unit u is the caller's bytes
+// [uoff[u], uoff[u + 1]) read forwards, without ushift it starts at 0: genie_find_smems_long's reads are such units.
+// long_units.inc makes the units and holds the entry point.
 //
-// The fixed-stride pipeline keeps a whole read in LDS and its positions in 16 bits.  Here nothing is per read except one
-// short serial pass: every stage is cut into WINDOWS of kLrWin positions (read-relative: window w of a read holds its
-// positions [w kLrWin, (w + 1) kLrWin)), handed out across all reads of the batch, so ten 10^6-base reads fill the chip
-// as well as 10^6 short ones.  Positions are 32-bit.
-//   LR0 lr_check_kernel   offsets non-decreasing, inside [0, total_bases], no read above max_len; the host reads the flag
-//                         (the one synchronisation of the call).  Too short for K in LUT / RMI mode: the read's status.
+// The fixed-stride pipeline keeps a whole read in LDS and its positions in 16 bits.  Here nothing is per unit except one
+// short serial pass: every stage is cut into WINDOWS of kLrWin positions (unit-relative: window w of a unit holds its
+// positions [w kLrWin, (w + 1) kLrWin)), handed out across all units of the batch, so ten 10^6-base reads fill the chip
+// as well as 10^6 short ones.  Positions are 32-bit.  lr_pipeline launches, over (uoff, U):
 //   LR1 lr_pack_kernel    one thread per 64-bit word of the packed stream (32 bases, plain big-endian words as QPlain
-//                         reads them); read r owns the words [Wd(r), Wd(r+1)), Wd(r) = off[r] / 32 + 3r, which leaves at
-//                         least two zero words behind every read (the padding every 32-base window relies on).  Bad base:
-//                         the read's status.
+//                         reads them); unit u owns the words [Wd(u), Wd(u+1)), Wd(u) = uoff[u] / 32 + 3u, which leaves at
+//                         least two zero words behind every unit (the padding every 32-base window relies on).  Only this
+//                         stage reads the caller's bases: a reversed unit is read backwards and complemented after the
+//                         bad-base test on the raw bytes (the reverse complement is never written as bytes).  Bad base:
+//                         the unit's status.
 //   LR2 lr_fwd_kernel     one wave per window: matching statistics fwd[a] (end of the longest match at a, 32-bit) from
 //                         one match-table lookup per position (mt_issue / mt_eval, as round 1 of K_A); positions the entry
 //                         cannot decide go to the slow list (mt_slow, the same code as K_A's), which compares the read with
-//                         the reference for as long as they agree -- past the window, to the end of the read.  Also:
+//                         the reference for as long as they agree -- past the window, to the end of the unit.  Also:
 //                         the window's maximum of fwd[a] - a (first position on ties), the mark "some position's match
 //                         ends here" at fwd[a], and the absent-base flag (fwd[a] = a).
 //   LR3 lr_walk_kernel    one block per window, its fwd and the previous window's in LDS.  The traversal step of K_B depends only on the current end i: the
@@ -24,11 +28,12 @@
 //                         that takes whole windows from their maxima (LR2) where fwd at the window's first position still
 //                         covers i.  Then pointer jumping in LDS (log2 kLrWin rounds) gives, for every marked position e,
 //                         the first end at or behind the window's end reached from e and the rows emitted on the way.
-//   LR4 lr_chain_kernel   one thread per read: the chain from 0, one step per window it enters (not per SMEM).  Writes the
-//                         window's entry end and the rows emitted before it in the read; the read's row count.
-//   launch_compact        the read counts to d_offsets (offsets only).
+//   LR4 lr_chain_kernel   one thread per unit: the chain from 0, one step per window it enters (not per SMEM).  Writes the
+//                         window's entry end and the rows emitted before it in the unit; the unit's row count.
+//   launch_compact        the unit counts to `offsets` (offsets only).
 //   LR5 lr_emit_kernel    one thread per window the chain enters: its SMEMs in order, the SA interval of each from
-//                         sa_interval over the packed read (any length), each row written once, non-temporal.
+//                         sa_interval over the packed unit (any length), each row written once, non-temporal, with the
+//                         unit's start inside its read added to start / end.
 namespace {
 
 constexpr int kLrWin = 256;               // positions per window (a multiple of 64: one per lane of LR3's block)
@@ -58,43 +63,37 @@ __device__ __forceinline__ unsigned long long lr_shfl_xor64(unsigned long long v
     return ((unsigned long long)hi << 32) | lo;
 }
 
-// also the status of every read: 0, or GENIE_READ_TOO_SHORT (LUT / RMI mode, fewer than K bases -- empty reads too, as in
-// K_A); LR1 overwrites it with GENIE_READ_BAD_BASE, which takes precedence
-__global__ void __launch_bounds__(256) lr_check_kernel(const long long *__restrict__ off, long long N, long long total,
-                                                       long long max_len, int mode, int K, int *__restrict__ flag,
-                                                       int32_t *__restrict__ st)
-{
-    const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r > N) return;
-    const long long o = off[r];
-    bool bad = o < 0 || o > total;
-    if (r < N) {
-        const long long o2 = off[r + 1];
-        bad = bad || o2 < o || o2 - o > max_len;
-        st[r] = (mode != GENIE_MODE_BWA && o2 - o < K) ? GENIE_READ_TOO_SHORT : GENIE_READ_OK;
-    }
-    if (bad) atomicOr(flag, 1);
-}
-
-__global__ void __launch_bounds__(256) lr_pack_kernel(const uint8_t *__restrict__ bases, const long long *__restrict__ off, long long N,
-                                                      long long nwords, uint64_t *__restrict__ packed, int32_t *__restrict__ st)
+// usrc[u]: (source byte of unit u's first base) * 2 + reversed; null: every unit is forward and starts at byte uoff[u]
+__global__ void __launch_bounds__(256) lr_pack_kernel(const uint8_t *__restrict__ bases, const long long *__restrict__ uoff, long long U,
+                                                      const long long *__restrict__ usrc, long long nwords,
+                                                      uint64_t *__restrict__ packed, int32_t *__restrict__ st)
 {
     const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= nwords) return;
-    const long long r = lr_find(N, g, [&](long long x) { return lr_wd(off, x); });
-    const long long k = g - lr_wd(off, r);
-    const long long o = off[r], L = off[r + 1] - o;
+    const long long u = lr_find(U, g, [&](long long x) { return lr_wd(uoff, x); });
+    const long long k = g - lr_wd(uoff, u);
+    const long long L = uoff[u + 1] - uoff[u];
     uint64_t w = 0;
     if (k >= 0 && 32 * k < L) {
-        const uint8_t *src = bases + o + 32 * k;
+        const long long key = usrc ? usrc[u] : 2 * uoff[u];
         const int cnt = L - 32 * k < 32 ? (int)(L - 32 * k) : 32;
         uint32_t bad = 0;
-        for (int j = 0; j < cnt; j++) {
-            const uint32_t c = src[j];
-            bad |= c;
-            w |= (uint64_t)(c & 3u) << (62 - 2 * j);
+        if (key & 1) {                                           // reversed: base j of the word is source byte -j, complemented
+            const uint8_t *src = bases + (key >> 1) - 32 * k;
+            for (int j = 0; j < cnt; j++) {
+                const uint32_t c = src[-j];
+                bad |= c;
+                w |= (uint64_t)((c & 3u) ^ 3u) << (62 - 2 * j);
+            }
+        } else {
+            const uint8_t *src = bases + (key >> 1) + 32 * k;
+            for (int j = 0; j < cnt; j++) {
+                const uint32_t c = src[j];
+                bad |= c;
+                w |= (uint64_t)(c & 3u) << (62 - 2 * j);
+            }
         }
-        if (bad > 3u) st[r] = GENIE_READ_BAD_BASE;            // every writer stores the same value
+        if (bad > 3u) st[u] = GENIE_READ_BAD_BASE;            // every writer stores the same value
     }
     packed[g] = w;
 }
@@ -268,29 +267,31 @@ __global__ void __launch_bounds__(256) lr_chain_kernel(const long long *__restri
     cnt[r] = total;
 }
 
+// ushift[u]: the unit's start inside its read, added to start / end of its rows; null: 0
 __global__ void __launch_bounds__(256) lr_emit_kernel(DevIndex ix, int mode, int min_len, const long long *__restrict__ off, long long N,
                                                       long long nwin, const uint64_t *__restrict__ packed, const int32_t *__restrict__ fwd,
                                                       const int32_t *__restrict__ bst, const int32_t *__restrict__ entry,
                                                       const int32_t *__restrict__ base, const long long *__restrict__ offsets,
-                                                      int4 *__restrict__ rows, long long cap)
+                                                      const int32_t *__restrict__ ushift, int4 *__restrict__ rows, long long cap)
 {
     const long long gw = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (gw >= nwin) return;
     const int e = entry[gw];
-    if (e < 0) return;                                           // a window the chain jumps over (or of a flagged read)
+    if (e < 0) return;                                           // a window the chain jumps over (or of a flagged unit)
     const long long r = lr_find(N, gw, [&](long long x) { return lr_wb(off, x); });
     const long long o = off[r];
     const int L = (int)(off[r + 1] - o);
     const int w0 = (int)((gw - lr_wb(off, r)) * kLrWin);
     const int lim = L - w0 < kLrWin ? L : w0 + kLrWin;
     const QPlain Q{packed + lr_wd(off, r)};
+    const uint32_t sh = ushift ? (uint32_t)ushift[r] : 0u;
     long long k = offsets[r] + base[gw];
     for (int i = e; i < lim;) {
         const int b = bst[o + i], end = fwd[o + b];
         if (mode != GENIE_MODE_BWA || end - b >= min_len) {
             if (k < cap) {
                 const int2 iv = sa_interval(ix, ix.dir, Q, b, end - b);
-                store_nt(rows + k, make_uint4((uint32_t)b, (uint32_t)end, (uint32_t)iv.x, (uint32_t)iv.y));
+                store_nt(rows + k, make_uint4((uint32_t)b + sh, (uint32_t)end + sh, (uint32_t)iv.x, (uint32_t)iv.y));
             }
             k++;
         }
@@ -307,11 +308,12 @@ struct LongArea {
     int2 *jc, *wmax;
     uint8_t *mark;
     int32_t *entry, *base;
-    long long nwords, nwin;
+    long long total, nwords, nwin;
 };
 
 inline int64_t long_layout(uint8_t *p, int64_t N, int64_t total, LongArea *a)
 {
+    a->total = total;
     a->nwords = total / 32 + 3 * N + 4;
     a->nwin = total / kLrWin + N + 1;
     Carver c{p};
@@ -330,55 +332,29 @@ inline int64_t long_layout(uint8_t *p, int64_t N, int64_t total, LongArea *a)
     return c.at;
 }
 
-}  // namespace
-
-int64_t find_smems_long_workspace_bytes(int64_t N, int64_t total_bases)
+// LR1 .. LR5 over the U units of `uoff`, the row counts to `offsets`: the one launch sequence of the long calls
+int lr_pipeline(const genie_index *ix, int mode, int min_len, const uint8_t *d_bases, const LongArea &a, const long long *uoff,
+                long long U, const long long *usrc, const int32_t *ushift, int64_t *offsets, int32_t *d_rows, long long cap,
+                hipStream_t s)
 {
-    LongArea a;
-    return long_layout(nullptr, N, total_bases, &a);
-}
-
-int launch_find_smems_long(const genie_index *ix, int32_t mode, const uint8_t *d_bases, const int64_t *d_read_offsets, int64_t N,
-                           int64_t total_bases, int64_t max_len, int32_t min_len, int64_t *d_offsets, int32_t *d_rows,
-                           int64_t out_cap_rows, int32_t *d_status, void *d_ws, int64_t ws_bytes, void *stream)
-{
-    (void)ws_bytes;
-    hipStream_t s = (hipStream_t)stream;
-    if (N == 0) {
-        HIP_TRY(hipMemsetAsync(d_offsets, 0, 8, s));
-        return GENIE_OK;
-    }
-    LongArea a;
-    long_layout(static_cast<uint8_t *>(d_ws), N, total_bases, &a);
-    const long long *off = reinterpret_cast<const long long *>(d_read_offsets);
-    HIP_TRY(hipMemsetAsync(a.flag, 0, 4, s));
     HIP_TRY(hipMemsetAsync(a.entry, 0xFF, a.nwin * 4, s));
-    if (total_bases > 0) HIP_TRY(hipMemsetAsync(a.mark, 0, total_bases, s));
-    LAUNCH(lr_check_kernel, dim3((unsigned)((N + 1 + 255) / 256)), dim3(256), 0, s, off, (long long)N, (long long)total_bases,
-           (long long)max_len, mode, ix->dev.K, a.flag, a.st);
-    int bad = 0;
-    HIP_TRY(hipMemcpyAsync(&bad, a.flag, 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (bad) return GENIE_E_INVALID;
-
-    LAUNCH(lr_pack_kernel, dim3((unsigned)((a.nwords + 255) / 256)), dim3(256), 0, s, d_bases, off, (long long)N, a.nwords,
-           a.packed, a.st);
+    if (a.total > 0) HIP_TRY(hipMemsetAsync(a.mark, 0, a.total, s));
+    LAUNCH(lr_pack_kernel, dim3((unsigned)((a.nwords + 255) / 256)), dim3(256), 0, s, d_bases, uoff, U, usrc, a.nwords, a.packed, a.st);
     const dim3 fgrid((unsigned)((a.nwin + kLrFwdWaves - 1) / kLrFwdWaves)), fblock(kLrFwdWaves * 64);
     if (ix->dev.flags & kFlagCompactTable)
-        LAUNCH(lr_fwd_kernel<true>, fgrid, fblock, 0, s, ix->dev, mode, off, (long long)N, a.nwin, a.packed, a.st, a.fwd, a.wmax,
-               a.mark, table_bytes(ix));
+        LAUNCH(lr_fwd_kernel<true>, fgrid, fblock, 0, s, ix->dev, mode, uoff, U, a.nwin, a.packed, a.st, a.fwd, a.wmax, a.mark,
+               table_bytes(ix));
     else
-        LAUNCH(lr_fwd_kernel<false>, fgrid, fblock, 0, s, ix->dev, mode, off, (long long)N, a.nwin, a.packed, a.st, a.fwd,
-               a.wmax, a.mark, table_bytes(ix));
-    LAUNCH(lr_walk_kernel, dim3((unsigned)a.nwin), dim3(kLrWin), 0, s, mode, min_len, off, (long long)N, a.st, a.fwd, a.wmax,
-           a.mark, a.bst, a.jc);
-    LAUNCH(lr_chain_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, off, (long long)N, a.st, a.jc, a.entry, a.base,
-           a.cnt);
-    int rc = launch_compact(a.cnt, nullptr, N, 0x7fffffff, d_offsets, nullptr, 0, a.sums, stream);
+        LAUNCH(lr_fwd_kernel<false>, fgrid, fblock, 0, s, ix->dev, mode, uoff, U, a.nwin, a.packed, a.st, a.fwd, a.wmax, a.mark,
+               table_bytes(ix));
+    LAUNCH(lr_walk_kernel, dim3((unsigned)a.nwin), dim3(kLrWin), 0, s, mode, min_len, uoff, U, a.st, a.fwd, a.wmax, a.mark, a.bst,
+           a.jc);
+    LAUNCH(lr_chain_kernel, dim3((unsigned)((U + 255) / 256)), dim3(256), 0, s, uoff, U, a.st, a.jc, a.entry, a.base, a.cnt);
+    int rc = launch_compact(a.cnt, nullptr, U, 0x7fffffff, offsets, nullptr, 0, a.sums, s);
     if (rc) return rc;
-    LAUNCH(lr_emit_kernel, dim3((unsigned)((a.nwin + 255) / 256)), dim3(256), 0, s, ix->dev, mode, min_len, off, (long long)N,
-           a.nwin, a.packed, a.fwd, a.bst, a.entry, a.base, reinterpret_cast<const long long *>(d_offsets),
-           reinterpret_cast<int4 *>(d_rows), (long long)out_cap_rows);
-    if (d_status) HIP_TRY(hipMemcpyAsync(d_status, a.st, N * 4, hipMemcpyDeviceToDevice, s));
+    LAUNCH(lr_emit_kernel, dim3((unsigned)((a.nwin + 255) / 256)), dim3(256), 0, s, ix->dev, mode, min_len, uoff, U, a.nwin, a.packed,
+           a.fwd, a.bst, a.entry, a.base, reinterpret_cast<const long long *>(offsets), ushift, reinterpret_cast<int4 *>(d_rows), cap);
     return GENIE_OK;
 }
+
+}  // namespace

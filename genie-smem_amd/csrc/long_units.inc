@@ -1,34 +1,32 @@
-// long_units.inc -- genie_find_smems_long_ex: both strands and breaks for reads of any length (included by kernels.hip
-// behind long_reads.inc, inside namespace genie; uses its kernels and layout).
+// long_units.inc -- genie_find_smems_long and genie_find_smems_long_ex: how the units of long_reads.inc's pipeline are made
+// from reads, strands and breaks, and the entry point (included by kernels.hip behind long_reads.inc, inside namespace genie).
 //
-// Of the long-read pipeline only the pack stage reads the caller's bases; LR2 .. LR5 work on the packed stream and on
-// workspace rows addressed through the offsets array they are handed.  So the pipeline is handed UNITS instead of reads:
-// a unit is one strand of one segment of one read, and uoff[U + 1] (prefix sums of the unit lengths) takes the place of
-// the read offsets.  Strands and breaks are then a property of the pack stage and of where the rows land.
+// A unit is one strand of one segment of one read.  Strands and breaks are a property of the pack stage (usrc) and of
+// where the rows land (ushift, the caller's offsets); everything between works on units alone.
 //   strand-read q = S i + s   read i on strand s (S = 2 with GENIE_READS_BOTH_STRANDS, else 1); position p of a reversed
 //                             strand-read is the read's position L - 1 - p, complemented (a code > 3 stays what it is)
 //   virtual position          S off[i] + s L_i + p: the strand-reads back to back, [0, S total_bases)
-//   LU0 lu_check_kernel       LR0's offset check (the host reads the flag: the first synchronisation).  Without breaks it
-//                             also writes the unit table -- the units are the strand-reads, empty ones included -- with
-//                             no pass over the bases.
-//   with GENIE_READS_SPLIT_BREAKS, parallel over positions (blocks of kLuChunk virtual positions across all strand-reads):
+//   LU0 lu_check_kernel       offsets non-decreasing, inside [0, total_bases], no read above max_len; the host reads the
+//                             flag (the first synchronisation).  Also the status of every strand-read (too short for K in
+//                             LUT / RMI mode) and, for two strands, the unit table of the strand-reads, empty ones
+//                             included, with no pass over the bases.
+//   The units are the strand-reads without GENIE_READS_SPLIT_BREAKS, or when its scan finds no break: lr_pipeline over
+//   them, whose launch_compact writes the caller's offsets.  On one strand the caller's read offsets are the unit offsets
+//   and there is no table, so nothing is copied; genie_find_smems_long is this case.
+//   With GENIE_READS_SPLIT_BREAKS, parallel over positions (blocks of kLuChunk virtual positions across all strand-reads):
 //   LU1 lu_seg_kernel<false>  good = code < 4 and present in the reference (split_present_bases); a segment starts where
 //                             good and (previous not good or first of its strand-read).  A block stages one flag byte per
 //                             position in LDS, a thread then takes kLuPer consecutive ones.  Starts per block, for every
 //                             strand-read the starts of its block in front of its first position, and "a break exists".
 //   scan_block_sums_kernel    over the block counts; the host reads the total and the break flag (the second
-//                             synchronisation).  No break anywhere: the units are the strand-reads, as without the flag.
+//                             synchronisation).
 //   per pass of at most C consecutive units (C from the workspace, at least S N):
 //   LU2 lu_seg_kernel<true>   the k-th start and the k-th end belong to the same segment: begin / end by rank
 //   LU3 lu_units_kernel       length, first source byte, direction and start inside the strand-read of every unit
 //   launch_compact            the unit lengths to uoff[]
-//   LU4 lu_pack_kernel        LR1 for units: one thread per 64-bit word; a reversed unit is read backwards and complemented
-//                             after the bad-base test on the raw bytes.  The reverse complement is never written as bytes.
-//   LR2 .. LR4, launch_compact   unchanged, over (uoff, U)
-//   LU5 lu_emit_kernel        LR5 with the unit's start added where the row is written (every row written once)
-//   LU6 lu_offsets_kernel     a strand-read's offset is its first unit's (units of a strand-read are consecutive)
+//   lr_pipeline               over (uoff, C) with usrc and ushift, its rows behind those of the passes before
+//   LU4 lu_offsets_kernel     a strand-read's offset is its first unit's (units of a strand-read are consecutive)
 //   Between passes the host reads the pass's row total (one synchronisation per extra pass).
-// Without breaks LR5 itself emits and launch_compact writes the caller's offsets: one synchronisation, as the long call.
 namespace {
 
 constexpr int kLuChunk = 16384;           // virtual positions per block of LU1 / LU2 ...
@@ -61,8 +59,11 @@ __device__ __forceinline__ long long lu_src_key(long long o, long long o2, bool 
     return rev ? (o2 - 1 - p) * 2 + 1 : (o + p) * 2;
 }
 
+// Every argument check that needs the offsets.  Given st: the status of every strand-read, 0 or GENIE_READ_TOO_SHORT (LUT /
+// RMI mode, fewer than K bases -- empty reads too, as in K_A); LR1 overwrites it with GENIE_READ_BAD_BASE, which takes
+// precedence.  Given uoff: the unit table (usrc, uoff) whose units are the strand-reads.
 __global__ void __launch_bounds__(256) lu_check_kernel(const long long *__restrict__ off, long long N, long long total,
-                                                       long long max_len, int mode, int K, int S, bool table, int *__restrict__ flag,
+                                                       long long max_len, int mode, int K, int S, int *__restrict__ flag,
                                                        int32_t *__restrict__ st, long long *__restrict__ usrc,
                                                        long long *__restrict__ uoff)
 {
@@ -73,16 +74,16 @@ __global__ void __launch_bounds__(256) lu_check_kernel(const long long *__restri
     if (r < N) {
         const long long o2 = off[r + 1];
         bad = bad || o2 < o || o2 - o > max_len;
-        if (table) {
-            const int32_t status = (mode != GENIE_MODE_BWA && o2 - o < K) ? GENIE_READ_TOO_SHORT : GENIE_READ_OK;
-            for (int s = 0; s < S; s++) {
-                const long long u = S * r + s;
-                st[u] = status;
+        const int32_t status = (mode != GENIE_MODE_BWA && o2 - o < K) ? GENIE_READ_TOO_SHORT : GENIE_READ_OK;
+        for (int s = 0; s < S; s++) {
+            const long long u = S * r + s;
+            if (st) st[u] = status;
+            if (uoff) {
                 usrc[u] = lu_src_key(o, o2, s == 1, 0);
                 uoff[u] = S == 1 ? o : (s ? o + o2 : 2 * o);
             }
         }
-    } else if (table) {
+    } else if (uoff) {
         uoff[S * N] = S * o;
     }
     if (bad) atomicOr(flag, 1);
@@ -242,72 +243,6 @@ __global__ void __launch_bounds__(256) lu_units_kernel(LuReads R, long long C, c
     ub[j] = lu_src_key(R.off[i], R.off[i + 1], R.S == 2 && (q & 1), p);
 }
 
-__global__ void __launch_bounds__(256) lu_pack_kernel(const uint8_t *__restrict__ bases, const long long *__restrict__ uoff, long long U,
-                                                      const long long *__restrict__ usrc, long long nwords,
-                                                      uint64_t *__restrict__ packed, int32_t *__restrict__ st)
-{
-    const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= nwords) return;
-    const long long u = lr_find(U, g, [&](long long x) { return lr_wd(uoff, x); });
-    const long long k = g - lr_wd(uoff, u);
-    const long long L = uoff[u + 1] - uoff[u];
-    uint64_t w = 0;
-    if (k >= 0 && 32 * k < L) {
-        const long long key = usrc[u];
-        const int cnt = L - 32 * k < 32 ? (int)(L - 32 * k) : 32;
-        uint32_t bad = 0;
-        if (key & 1) {                                           // reversed: base j of the word is source byte -j, complemented
-            const uint8_t *src = bases + (key >> 1) - 32 * k;
-            for (int j = 0; j < cnt; j++) {
-                const uint32_t c = src[-j];
-                bad |= c;
-                w |= (uint64_t)((c & 3u) ^ 3u) << (62 - 2 * j);
-            }
-        } else {
-            const uint8_t *src = bases + (key >> 1) + 32 * k;
-            for (int j = 0; j < cnt; j++) {
-                const uint32_t c = src[j];
-                bad |= c;
-                w |= (uint64_t)(c & 3u) << (62 - 2 * j);
-            }
-        }
-        if (bad > 3u) st[u] = GENIE_READ_BAD_BASE;            // every writer stores the same value
-    }
-    packed[g] = w;
-}
-
-// LR5 with the unit's start inside its strand-read added to start / end
-__global__ void __launch_bounds__(256) lu_emit_kernel(DevIndex ix, int mode, int min_len, const long long *__restrict__ off, long long N,
-                                                      long long nwin, const uint64_t *__restrict__ packed, const int32_t *__restrict__ fwd,
-                                                      const int32_t *__restrict__ bst, const int32_t *__restrict__ entry,
-                                                      const int32_t *__restrict__ base, const long long *__restrict__ offsets,
-                                                      const int32_t *__restrict__ ushift, int4 *__restrict__ rows, long long cap)
-{
-    const long long gw = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (gw >= nwin) return;
-    const int e = entry[gw];
-    if (e < 0) return;
-    const long long r = lr_find(N, gw, [&](long long x) { return lr_wb(off, x); });
-    const long long o = off[r];
-    const int L = (int)(off[r + 1] - o);
-    const int w0 = (int)((gw - lr_wb(off, r)) * kLrWin);
-    const int lim = L - w0 < kLrWin ? L : w0 + kLrWin;
-    const QPlain Q{packed + lr_wd(off, r)};
-    const uint32_t sh = (uint32_t)ushift[r];
-    long long k = offsets[r] + base[gw];
-    for (int i = e; i < lim;) {
-        const int b = bst[o + i], end = fwd[o + b];
-        if (mode != GENIE_MODE_BWA || end - b >= min_len) {
-            if (k < cap) {
-                const int2 iv = sa_interval(ix, ix.dir, Q, b, end - b);
-                store_nt(rows + k, make_uint4((uint32_t)b + sh, (uint32_t)end + sh, (uint32_t)iv.x, (uint32_t)iv.y));
-            }
-            k++;
-        }
-        i = end;
-    }
-}
-
 // strand-reads whose first unit is in the pass (or, in the last pass, that have none left) get their offset
 __global__ void __launch_bounds__(256) lu_offsets_kernel(LuReads R, const unsigned long long *__restrict__ bsum,
                                                          const int32_t *__restrict__ qloc, long long units, long long p0,
@@ -326,10 +261,11 @@ __global__ void __launch_bounds__(256) lu_offsets_kernel(LuReads R, const unsign
     if (f >= p0 && (f < p1 || (last && f == p1))) offsets[q] = row0 + local_off[f - p0];
 }
 
-// Workspace of the call: the check flag, the segmentation's block counts and per-strand-read counts, then a pass area
-// for C units: the unit table and the long-read pipeline for C units and S total_bases positions.
+// Workspace of the call.  With breaks first the segmentation's block counts and per-strand-read counts.  Then the area of C
+// units: the pipeline's for C units and S total_bases positions -- it begins with the flag block (check flag, break flag),
+// whose address therefore does not depend on C -- and behind it the pieces of the unit table that the units need: none
+// for whole reads on one strand, source and offsets for strand-reads, all of them for segments.
 struct LongExFixed {
-    int *flag;
     unsigned long long *bsum;        // blocks + 2 words
     int32_t *qloc;                   // S N + 1
     long long nblk;
@@ -339,86 +275,54 @@ inline int64_t long_ex_fixed_layout(uint8_t *p, int64_t N, int64_t total, int S,
 {
     f->nblk = split ? (S * total + kLuChunk - 1) / kLuChunk : 0;
     Carver c{p};
-    c.take(f->flag, 256);
     c.take(f->bsum, split ? 8 * (f->nblk + 2) : 0);
     c.take(f->qloc, split ? 4 * (S * N + 1) : 0);
     return c.at;
 }
 
 struct LongExPass {
+    LongArea lr;                     // long_layout(C, S total)
     long long *ua, *ub;              // C each: virtual begin, virtual end / source key
     int32_t *ulen, *ushift;
     long long *uoff, *loff;          // C + 1 each: unit offsets, the pass's row offsets
-    uint8_t *lr;                     // long_layout(C, S total)
 };
 
-inline int64_t long_ex_pass_layout(uint8_t *p, int64_t C, int64_t vtotal, bool split, LongExPass *a)
+inline int64_t long_ex_pass_layout(uint8_t *p, int64_t C, int64_t total, int S, bool split, LongExPass *a)
 {
-    Carver c{p};
+    const bool table = S == 2 || split;
+    Carver c{p, long_layout(p, C, S * total, &a->lr)};
     c.take(a->ua, split ? 8 * C : 0);
-    c.take(a->ub, 8 * C);
+    c.take(a->ub, table ? 8 * C : 0);
     c.take(a->ulen, split ? 4 * C : 0);
     c.take(a->ushift, split ? 4 * C : 0);
-    c.take(a->uoff, 8 * (C + 1));
+    c.take(a->uoff, table ? 8 * (C + 1) : 0);
     c.take(a->loff, split ? 8 * (C + 1) : 0);
-    c.take(a->lr, 0);
-    LongArea la;
-    return c.at + long_layout(nullptr, C, vtotal, &la);
+    return c.at;
 }
 
-// LU4, LR2 .. LR4 and the row counts to `offsets`, then LR5 (ushift null) or LU5
-int lu_pipeline(const genie_index *ix, int mode, int min_len, const uint8_t *d_bases, const LongArea &a, const long long *uoff,
-                long long U, const long long *usrc, const int32_t *ushift, int64_t *offsets, int32_t *d_rows, long long cap,
-                hipStream_t s)
-{
-    LAUNCH(lu_pack_kernel, dim3((unsigned)((a.nwords + 255) / 256)), dim3(256), 0, s, d_bases, uoff, U, usrc, a.nwords, a.packed, a.st);
-    const dim3 fgrid((unsigned)((a.nwin + kLrFwdWaves - 1) / kLrFwdWaves)), fblock(kLrFwdWaves * 64);
-    if (ix->dev.flags & kFlagCompactTable)
-        LAUNCH(lr_fwd_kernel<true>, fgrid, fblock, 0, s, ix->dev, mode, uoff, U, a.nwin, a.packed, a.st, a.fwd, a.wmax, a.mark,
-               table_bytes(ix));
-    else
-        LAUNCH(lr_fwd_kernel<false>, fgrid, fblock, 0, s, ix->dev, mode, uoff, U, a.nwin, a.packed, a.st, a.fwd, a.wmax, a.mark,
-               table_bytes(ix));
-    LAUNCH(lr_walk_kernel, dim3((unsigned)a.nwin), dim3(kLrWin), 0, s, mode, min_len, uoff, U, a.st, a.fwd, a.wmax, a.mark, a.bst,
-           a.jc);
-    LAUNCH(lr_chain_kernel, dim3((unsigned)((U + 255) / 256)), dim3(256), 0, s, uoff, U, a.st, a.jc, a.entry, a.base, a.cnt);
-    int rc = launch_compact(a.cnt, nullptr, U, 0x7fffffff, offsets, nullptr, 0, a.sums, s);
-    if (rc) return rc;
-    const dim3 egrid((unsigned)((a.nwin + 255) / 256));
-    if (ushift)
-        LAUNCH(lu_emit_kernel, egrid, dim3(256), 0, s, ix->dev, mode, min_len, uoff, U, a.nwin, a.packed, a.fwd, a.bst, a.entry, a.base,
-               reinterpret_cast<const long long *>(offsets), ushift, reinterpret_cast<int4 *>(d_rows), cap);
-    else
-        LAUNCH(lr_emit_kernel, egrid, dim3(256), 0, s, ix->dev, mode, min_len, uoff, U, a.nwin, a.packed, a.fwd, a.bst, a.entry, a.base,
-               reinterpret_cast<const long long *>(offsets), reinterpret_cast<int4 *>(d_rows), cap);
-    return GENIE_OK;
-}
-
+// units the caller's workspace holds: the strand-reads (a table is laid out for one at least), with breaks one more per
+// kLuSpare positions
 inline int64_t long_ex_units(int64_t N, int64_t total, int S, bool split)
 {
-    return std::max<int64_t>(1, S * N) + (split ? S * total / kLuSpare : 0);
+    return (S == 2 || split ? std::max<int64_t>(1, S * N) : N) + (split ? S * total / kLuSpare : 0);
 }
 
 }  // namespace
 
 int64_t find_smems_long_ex_workspace_bytes(int64_t N, int64_t total_bases, int32_t flags)
 {
-    if (flags == 0) return find_smems_long_workspace_bytes(N, total_bases);
     const int S = (flags & GENIE_READS_BOTH_STRANDS) ? 2 : 1;
     const bool split = (flags & GENIE_READS_SPLIT_BREAKS) != 0;
     LongExFixed f;
     LongExPass a;
     return long_ex_fixed_layout(nullptr, N, total_bases, S, split, &f) +
-           long_ex_pass_layout(nullptr, long_ex_units(N, total_bases, S, split), S * total_bases, split, &a);
+           long_ex_pass_layout(nullptr, long_ex_units(N, total_bases, S, split), total_bases, S, split, &a);
 }
 
 int launch_find_smems_long_ex(const genie_index *ix, int32_t mode, int32_t flags, const uint8_t *d_bases, const int64_t *d_read_offsets,
                               int64_t N, int64_t total_bases, int64_t max_len, int32_t min_len, int64_t *d_offsets, int32_t *d_rows,
                               int64_t out_cap_rows, int32_t *d_status, void *d_ws, int64_t ws_bytes, void *stream)
 {
-    if (flags == 0)
-        return launch_find_smems_long(ix, mode, d_bases, d_read_offsets, N, total_bases, max_len, min_len, d_offsets, d_rows,
-                                      out_cap_rows, d_status, d_ws, ws_bytes, stream);
     hipStream_t s = (hipStream_t)stream;
     if (N == 0) {
         HIP_TRY(hipMemsetAsync(d_offsets, 0, 8, s));
@@ -426,37 +330,33 @@ int launch_find_smems_long_ex(const genie_index *ix, int32_t mode, int32_t flags
     }
     const int S = (flags & GENIE_READS_BOTH_STRANDS) ? 2 : 1;
     const bool split = (flags & GENIE_READS_SPLIT_BREAKS) != 0;
-    const long long SN = (long long)S * N, vtotal = (long long)S * total_bases;
+    const long long SN = (long long)S * N;
     const long long *off = reinterpret_cast<const long long *>(d_read_offsets);
     LongExFixed f;
     const int64_t fixed = long_ex_fixed_layout(static_cast<uint8_t *>(d_ws), N, total_bases, S, split, &f);
     uint8_t *pass = static_cast<uint8_t *>(d_ws) + fixed;
-    LongExPass a;
-    LongArea la;
-    if (!split) {
-        long_ex_pass_layout(pass, SN, vtotal, false, &a);
-        long_layout(a.lr, SN, vtotal, &la);
-    }
-    HIP_TRY(hipMemsetAsync(f.flag, 0, 8, s));
+    // The strand-reads as units.  On one strand the caller's offsets are the unit offsets and there is no table.
+    LongExPass whole;
+    long_ex_pass_layout(pass, SN, total_bases, S, false, &whole);
+    int *const flag = whole.lr.flag;
+    long long *const tsrc = S == 2 ? whole.ub : nullptr, *const toff = S == 2 ? whole.uoff : nullptr;
+    auto strand_reads = [&]() -> int {
+        int rc = lr_pipeline(ix, mode, min_len, d_bases, whole.lr, toff ? toff : off, SN, tsrc, nullptr, d_offsets, d_rows, out_cap_rows, s);
+        if (rc) return rc;
+        if (d_status) HIP_TRY(hipMemcpyAsync(d_status, whole.lr.st, SN * 4, hipMemcpyDeviceToDevice, s));
+        return GENIE_OK;
+    };
+    HIP_TRY(hipMemsetAsync(flag, 0, 8, s));
     LAUNCH(lu_check_kernel, dim3((unsigned)((N + 1 + 255) / 256)), dim3(256), 0, s, off, (long long)N, (long long)total_bases,
-           (long long)max_len, mode, ix->dev.K, S, !split, f.flag, split ? nullptr : la.st, split ? nullptr : a.ub,
-           split ? nullptr : a.uoff);
+           (long long)max_len, mode, ix->dev.K, S, flag, whole.lr.st, tsrc, toff);
     int bad = 0;
-    HIP_TRY(hipMemcpyAsync(&bad, f.flag, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&bad, flag, 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     if (bad) return GENIE_E_INVALID;
-
-    if (!split) {                                                // the units are the strand-reads
-        HIP_TRY(hipMemsetAsync(la.entry, 0xFF, la.nwin * 4, s));
-        if (vtotal > 0) HIP_TRY(hipMemsetAsync(la.mark, 0, vtotal, s));
-        int rc = lu_pipeline(ix, mode, min_len, d_bases, la, a.uoff, SN, a.ub, nullptr, d_offsets, d_rows, out_cap_rows, s);
-        if (rc) return rc;
-        if (d_status) HIP_TRY(hipMemcpyAsync(d_status, la.st, SN * 4, hipMemcpyDeviceToDevice, s));
-        return GENIE_OK;
-    }
+    if (!split) return strand_reads();
 
     const LuReads R{d_bases, off, (long long)N, S};
-    int *anybreak = f.flag + 1;
+    int *anybreak = flag + 1;
     HIP_TRY(hipMemsetAsync(f.qloc, 0xFF, (SN + 1) * 4, s));
     if (f.nblk > 0)
         LAUNCH(lu_seg_kernel<false>, dim3((unsigned)f.nblk), dim3(256), 0, s, ix->dev, R, f.bsum, f.qloc, anybreak, 0ll, 0ll,
@@ -467,47 +367,31 @@ int launch_find_smems_long_ex(const genie_index *ix, int32_t mode, int32_t flags
     HIP_TRY(hipMemcpyAsync(&units, f.bsum + f.nblk, 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(&breaks, anybreak, 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
+    if (!breaks) return strand_reads();                          // every status is GENIE_READ_OK: BWA mode, no bad or absent base
     if (d_status) HIP_TRY(hipMemsetAsync(d_status, 0, SN * 4, s));
-    if (!breaks) {                                               // no break anywhere: the units are the strand-reads
-        long_ex_pass_layout(pass, SN, vtotal, false, &a);
-        long_layout(a.lr, SN, vtotal, &la);
-        LAUNCH(lu_check_kernel, dim3((unsigned)((N + 1 + 255) / 256)), dim3(256), 0, s, off, (long long)N, (long long)total_bases,
-               (long long)max_len, mode, ix->dev.K, S, true, f.flag, la.st, a.ub, a.uoff);
-        HIP_TRY(hipMemsetAsync(la.entry, 0xFF, la.nwin * 4, s));
-        if (vtotal > 0) HIP_TRY(hipMemsetAsync(la.mark, 0, vtotal, s));
-        return lu_pipeline(ix, mode, min_len, d_bases, la, a.uoff, SN, a.ub, nullptr, d_offsets, d_rows, out_cap_rows, s);
-    }
     const long long U = (long long)units;
     if (U == 0) {
         HIP_TRY(hipMemsetAsync(d_offsets, 0, (SN + 1) * 8, s));
         return GENIE_OK;
     }
+    LongExPass a;
     // units per pass: as many as the workspace holds (at least S N: the caller sized it for that many)
-    long long C = std::max<long long>(SN, 1);
-    {
-        long long lo = C, hi = std::max(C, U);
-        while (lo < hi) {
-            const long long mid = lo + (hi - lo + 1) / 2;
-            if (long_ex_pass_layout(nullptr, mid, vtotal, true, &a) <= ws_bytes - fixed) lo = mid; else hi = mid - 1;
-        }
-        C = std::min(lo, U);
-    }
-    long_ex_pass_layout(pass, C, vtotal, true, &a);
-    long_layout(a.lr, C, vtotal, &la);
+    const long long C = pass_size(std::max<long long>(SN, 1), U, [&](long long c) {
+        return long_ex_pass_layout(nullptr, c, total_bases, S, true, &a) <= ws_bytes - fixed;
+    });
+    long_ex_pass_layout(pass, C, total_bases, S, true, &a);
     long long row0 = 0;
     for (long long p0 = 0; p0 < U; p0 += C) {
         const long long p1 = std::min(U, p0 + C), Cp = p1 - p0;
         const bool last = p1 == U;
-        HIP_TRY(hipMemsetAsync(la.st, 0, Cp * 4, s));             // GENIE_READ_OK: a unit holds no break
-        HIP_TRY(hipMemsetAsync(la.entry, 0xFF, la.nwin * 4, s));
-        HIP_TRY(hipMemsetAsync(la.mark, 0, vtotal, s));
+        HIP_TRY(hipMemsetAsync(a.lr.st, 0, Cp * 4, s));           // GENIE_READ_OK: a unit holds no break
         LAUNCH(lu_seg_kernel<true>, dim3((unsigned)f.nblk), dim3(256), 0, s, ix->dev, R, f.bsum, f.qloc, anybreak, p0, p1, a.ua, a.ub);
         LAUNCH(lu_units_kernel, dim3((unsigned)((Cp + 255) / 256)), dim3(256), 0, s, R, Cp, static_cast<const long long *>(a.ua), a.ub,
                a.ulen, a.ushift);
-        int rc = launch_compact(a.ulen, nullptr, Cp, 0x7fffffff, reinterpret_cast<int64_t *>(a.uoff), nullptr, 0, la.sums, stream);
+        int rc = launch_compact(a.ulen, nullptr, Cp, 0x7fffffff, reinterpret_cast<int64_t *>(a.uoff), nullptr, 0, a.lr.sums, stream);
         if (rc) return rc;
         const long long cap_left = std::max(0ll, (long long)out_cap_rows - row0);
-        rc = lu_pipeline(ix, mode, min_len, d_bases, la, a.uoff, Cp, a.ub, a.ushift, reinterpret_cast<int64_t *>(a.loff),
+        rc = lr_pipeline(ix, mode, min_len, d_bases, a.lr, a.uoff, Cp, a.ub, a.ushift, reinterpret_cast<int64_t *>(a.loff),
                          cap_left > 0 ? d_rows + 4 * row0 : d_rows, cap_left, s);
         if (rc) return rc;
         LAUNCH(lu_offsets_kernel, dim3((unsigned)((SN + 1 + 255) / 256)), dim3(256), 0, s, R, static_cast<const unsigned long long *>(f.bsum),

@@ -395,15 +395,7 @@ int launch_find_smems_split(const genie_index *ix, const uint8_t *d_reads, const
     // segments per pass: as many as the workspace holds at this longest segment (at least N: the caller sized it for N reads
     // of fixed_len >= M bases)
     SplitPassArea a;
-    long long C = std::max<long long>(N, 1);
-    {
-        long long lo = C, hi = S;
-        while (lo < hi) {
-            const long long mid = lo + (hi - lo + 1) / 2;
-            if (split_pass_layout(nullptr, mid, M, &a) <= pass_avail) lo = mid; else hi = mid - 1;
-        }
-        C = std::min(lo, S);
-    }
+    const long long C = pass_size(std::max<long long>(N, 1), S, [&](long long c) { return split_pass_layout(nullptr, c, M, &a) <= pass_avail; });
     LAUNCH(scan_block_sums_kernel, dim3(1), dim3(kScanBlock), 0, s, f.gsum, groups);
     LAUNCH(split_offsets_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, f.nseg, f.gsum, (long long)N, f.segoff);
 

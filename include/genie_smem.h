@@ -307,7 +307,8 @@ int genie_find_smems_split(const genie_index *ix, const uint8_t *d_reads, const 
  * NULL) the same GENIE_READ_* codes.  For every read that genie_find_smems_csr accepts, rows and status are the same bytes.
  * d_rows 16-byte aligned; d_workspace 256-byte aligned, genie_find_smems_long_workspace_bytes(N, total_bases, max_len)
  * bytes (GENIE_E_CAPACITY when smaller): about 17.3 bytes per base plus 48 per read.  Argument checks come before the
- * device check.  This call synchronizes `stream` once, after the offset check and before any other kernel runs. */
+ * device check.  This call synchronizes `stream` once, after the offset check and before any other kernel runs.
+ * Both functions are genie_find_smems_long_ex (below) with flags == 0: the same checks, workspace and launches. */
 int64_t genie_find_smems_long_workspace_bytes(int64_t N, int64_t total_bases, int64_t max_len);
 int genie_find_smems_long(const genie_index *ix, int32_t mode, const uint8_t *d_bases, const int64_t *d_read_offsets,
                           int64_t N, int64_t total_bases, int64_t max_len, int32_t min_len,
@@ -325,7 +326,8 @@ int genie_find_smems_long(const genie_index *ix, int32_t mode, const uint8_t *d_
  *                             start / end in the whole strand-read; every status GENIE_READ_OK; an empty or all-break
  *                             strand-read has no rows.  Only with GENIE_MODE_BWA (GENIE_E_INVALID otherwise).
  * Let S = 2 with BOTH_STRANDS, else 1.  Defining properties, each byte for byte:
- *   flags == 0         genie_find_smems_long itself (the workspace function returns the same number);
+ *   flags == 0         what genie_find_smems_long documents: that call is this one with no flags, and so is its
+ *                      workspace function;
  *   BOTH_STRANDS       genie_find_smems_long on the explicit batch [r0, rc(r0), r1, rc(r1), ...], every mode, status per
  *                      strand-read -- and so genie_find_smems_both on reads of at most GENIE_MAX_READ_LEN bases;
  *   SPLIT_BREAKS       genie_find_smems_split on reads of at most GENIE_MAX_READ_LEN bases;
@@ -334,9 +336,9 @@ int genie_find_smems_long(const genie_index *ix, int32_t mode, const uint8_t *d_
  * bits, bad pointers / sizes / alignment give GENIE_E_INVALID and a small workspace GENIE_E_CAPACITY, all before the device
  * check; bad offsets GENIE_E_INVALID, found on the device.  The reverse complement is never written to memory as bytes.
  * d_workspace: 256-byte aligned, genie_find_smems_long_ex_workspace_bytes(N, total_bases, max_len, flags) bytes: the
- * long-read pipeline for S total_bases positions and max(1, S N) units (a unit is one strand of one segment of one read),
- * i.e. about 17.3 S bytes per base and 64 S per read; with SPLIT_BREAKS one more unit per 32 positions, the unit table
- * and the segmentation's counts: about 20.1 S bytes per base and 92 S per read.
+ * long-read pipeline for S total_bases positions and S N units (one at least with any flag; a unit is one strand of one
+ * segment of one read), i.e. about 17.3 S bytes per base and 64 S per read; with SPLIT_BREAKS one more unit per 32
+ * positions, the unit table and the segmentation's counts: about 20.1 S bytes per base and 92 S per read.
  * Synchronisations of `stream`: without SPLIT_BREAKS one, after the offset check (as genie_find_smems_long).  With it one
  * more to read the number of units, and one per extra pass when the units outnumber what the workspace holds (passes of
  * consecutive units, each of at least S N). */

@@ -399,6 +399,21 @@ def test_nonzero_first_offset(pkg, oracle_mod):
         _same((off, rows[:cap], st), want)
 
 
+def test_nonzero_first_offset_whole_reads_on_one_strand(pkg, oracle_mod):
+    """Where the units are whole reads on one strand -- no flags, and SPLIT_BREAKS on reads without a break -- the caller's
+    offsets serve as the unit offsets: a lead that is no multiple of 32 must not show in offsets, rows or status."""
+    codes, ix, o = LR._ref(pkg, oracle_mod, 100_000)
+    reads = [LR._from_ref(codes, L, 50 + i) if L else np.zeros(0, np.uint8) for i, L in enumerate((0, 1, 31, 32, 33, 300, 5000))]
+    lead = np.full(1234, 4, np.uint8)
+    offs = 1234 + LR._csr(reads)[1]
+    got = {}
+    for mode, flags in (("bwa", 0), ("lut", 0), ("bwa", SPLIT)):
+        off, rows, st, cap = _ex_raw(pkg, ix, mode, flags, [np.concatenate([lead, reads[0]])] + reads[1:], offs=offs)
+        got[mode, flags] = (off, rows[:cap], st)
+        _same(got[mode, flags], LR._long(ix, mode, reads))
+    _same(got["bwa", SPLIT], got["bwa", 0])
+
+
 # ------------------------------------------------------------------ drop-in
 def test_dropin_strings_with_n_on_both_strands(pkg, oracle_mod):
     from genie_smem_amd import synth
