@@ -215,6 +215,8 @@ int genie_sa_interval(const genie_index *ix, const uint8_t *d_pats, const int32_
  * mode RMI: RMI_LUT.get_suffix_rmi = predict + last-mile search (SMEM/RMI_LUT.py:67-184),
  * contract behaviour = the true interval; an absent K-mer is reported the reference's way,
  * lower > upper (lower = the row it would be inserted at).  LUT output as genie_sa_interval.
+ * A reference of fewer than K bases holds no K-mer: every K-mer is absent, in each mode's own way
+ * (genie_index_train_rmi refuses such a handle with GENIE_E_INVALID; genie_index_set_rmi does not).
  * d_pred (may be NULL,
  * RMI only) receives the float64 prediction of RMI_LUT.rmi_predict (SMEM/RMI_LUT.py:53-63). */
 int genie_seed_lookup(const genie_index *ix, int32_t mode, const uint8_t *d_kmers, int64_t N,
