@@ -343,17 +343,28 @@ def test_second_level_range_table(pkg):
     assert _parse(pkg.GenieIndex.build(ref[:5000], 8, table_bits=9).serialize().numpy())["P2"] == 9
 
 
+# the references of the two match-table tests, with the default knobs and with (dir_bits, table_bits) = (5, 7)
+MATCH_TABLE_CASES = ["syn10k", "tail_A", "tiny", "repeat"] + [c + "-P5-bits7" for c in ("syn10k", "tail_A", "tiny", "repeat")]
+
+
+def _match_table_knobs(case):
+    """case id -> (reference name, keyword arguments of GenieIndex.build, the P2 they must give or None)."""
+    case, _, knobs = case.partition("-")
+    return (case, dict(dir_bits=5, table_bits=7), 7) if knobs else (case, {}, None)
+
+
 def _match_table(img, h):
     return np.frombuffer(bytes(img[h["off_mtab"]:h["off_mtab"] + 32 * h["mtab_entries"]]),
                          np.dtype([("meta", "<u4"), ("lb", "<u4"), ("key", "<u4", (6,))]))
 
 
-@pytest.mark.parametrize("case", ["syn10k", "tail_A", "tiny", "repeat"])
+@pytest.mark.parametrize("case", MATCH_TABLE_CASES)
 def test_match_table_against_brute_force(pkg, case):
     """MatchRec per P2-mer (genie_internal.h): base / lmask / flags / row count / first row and the 16-base
     continuations of its suffixes -- in the entry, or chained through overflow entries -- against a direct
     enumeration of the reference's substrings."""
     rng = np.random.default_rng(77)
+    case, knobs, want_p2 = _match_table_knobs(case)
     if case == "syn10k":
         ref = rng.integers(0, 4, 10_000).astype(np.uint8)
     elif case == "tail_A":                       # the reference ends in A's: cut-short suffixes look like padding
@@ -364,10 +375,11 @@ def test_match_table_against_brute_force(pkg, case):
         ref = np.concatenate([np.tile([0, 1, 2, 3, 3, 1], 60), rng.integers(0, 4, 1000), np.tile([2, 2, 0, 1, 3, 0, 1, 1, 2, 3], 11),
                               rng.integers(0, 4, 1000)]).astype(np.uint8)
     n = len(ref)
-    ix = pkg.GenieIndex.build(ref, 6, table_format="wide")
+    ix = pkg.GenieIndex.build(ref, 6, table_format="wide", **knobs)
     img = ix.serialize().numpy()
     h = _parse(img)
     P2 = h["P2"]
+    assert P2 == (want_p2 or P2) and h["P"] == knobs.get("dir_bits", 7)
     assert h["dir2_entries"] == 4 ** P2 <= h["mtab_entries"] and h["flags"] & 2 == 0 and h["ov_entries"] == 0
     mt = _match_table(img, h)
     raw = np.frombuffer(bytes(img[h["off_mtab"]:h["off_mtab"] + 32 * h["mtab_entries"]]), "<u4").reshape(-1, 8)
@@ -425,13 +437,14 @@ def test_match_table_against_brute_force(pkg, case):
             assert (int(mt["lb"][c]), int(mt["key"][c][0])) == (want[0], want[-1]) and len(want) == want[-1] - want[0] + 1, mer
 
 
-@pytest.mark.parametrize("case", ["syn10k", "tail_A", "tiny", "repeat"])
+@pytest.mark.parametrize("case", MATCH_TABLE_CASES)
 def test_compact_match_table_against_brute_force(pkg, case):
     """MatchRec16 per P2-mer + its overflow blocks (genie_internal.h, the form for tables that do not fit an XCD's L2):
     first row, suffix count, the 8-base continuations (inline up to six; 7 .. 13: five inline + a block of eight), the
     rows-decide flag (a cut-short suffix, or more than 13) and, for an absent P2-mer, its longest occurring prefix and that
     prefix's rows -- against a direct enumeration."""
     rng = np.random.default_rng(77)
+    case, knobs, want_p2 = _match_table_knobs(case)
     if case == "syn10k":
         ref = rng.integers(0, 4, 10_000).astype(np.uint8)
     elif case == "tail_A":
@@ -442,10 +455,11 @@ def test_compact_match_table_against_brute_force(pkg, case):
         ref = np.concatenate([np.tile([0, 1, 2, 3, 3, 1], 60), rng.integers(0, 4, 1000), np.tile([2, 2, 0, 1, 3, 0, 1, 1, 2, 3], 11),
                               rng.integers(0, 4, 1000)]).astype(np.uint8)
     n = len(ref)
-    ix = pkg.GenieIndex.build(ref, 6, table_format="compact")
+    ix = pkg.GenieIndex.build(ref, 6, table_format="compact", **knobs)
     img = ix.serialize().numpy()
     h = _parse(img)
     P2 = h["P2"]
+    assert P2 == (want_p2 or P2) and h["P"] == knobs.get("dir_bits", 7)
     assert h["flags"] & 2 and h["mtab_entries"] == h["dir2_entries"] == 4 ** P2 and 1 <= h["ov_entries"] <= 65536
     raw = np.frombuffer(bytes(img[h["off_mtab"]:h["off_mtab"] + 16 * h["mtab_entries"]]), np.dtype([("w0", "<u4"), ("key", "<u2", (6,))]))
     ov = np.frombuffer(bytes(img[h["off_ov"]:h["off_ov"] + 16 * h["ov_entries"]]), "<u2").reshape(-1, 8)
