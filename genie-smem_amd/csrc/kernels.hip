@@ -950,12 +950,6 @@ int launch_pipeline(const genie_index *ix, const Geometry &g, const FindRequest 
     while ((1 << block_shift) < reads_per_block) block_shift++;
     if (r.offsets)                           // scan of the traversal blocks' sums; K_C adds the in-block part
         LAUNCH(scan_block_sums_kernel, dim3(1), dim3(kScanBlock), 0, s, bsums, (N + reads_per_block - 1) / reads_per_block);
-    // K_C: intervals + final rows, 16 lanes per read (4 reads per wave pass), persistent blocks
-    // (half the blocks help on the 1 Mb reference, 1.50 -> 1.40 ms per 4 x 10^6 reads, but cost at 300 kb, 0.215 -> 0.250 ms
-    // per 10^6, with the same 8 MB table: not worth a rule)
-    long long grid_c = (long long)cus * (32 / kIvWaves);
-    const long long need_c = (N + kIvWaves * 4 * kIvUnroll - 1) / (kIvWaves * 4 * kIvUnroll);
-    if (grid_c > need_c) grid_c = need_c;
     RowEscapes esc{nullptr, nullptr, 0};
     const int sched_c = ((ix->opt_scheduling >> 2) & 1) | cus << 8;  // bit 0: no priority rotation; bits 8..: CUs (blocks per round)
     if (r.packed) {
@@ -964,9 +958,31 @@ int launch_pipeline(const genie_index *ix, const Geometry &g, const FindRequest 
         esc.cap = r.cap_escapes;
         HIP_TRY(hipMemsetAsync(r.offsets, 0, 16, s));
     }
-    auto kc = r.packed ? (r.row_bytes == 6 ? (c16 ? interval_kernel<true, false, true, 2> : interval_kernel<true, false, false, 2>)
-                                           : (c16 ? interval_kernel<true, false, true, 1> : interval_kernel<true, false, false, 1>))
-            : r.offsets ? (c16 ? interval_kernel<true, WIDE, true> : interval_kernel<true, WIDE, false>)
+    if (!WIDE && r.offsets) {
+        // K_C, short reads, CSR rows: one lane per row over tiles of reads staged in LDS, persistent blocks -- as many per CU as
+        // their LDS allows, four (eight waves per SIMD) up to 150 bases
+        const int lds_c = kIvTile * g.qp_stride * 16;
+        auto kr = r.packed ? (r.row_bytes == 6 ? (c16 ? interval_rows_kernel<true, 2> : interval_rows_kernel<false, 2>)
+                                               : (c16 ? interval_rows_kernel<true, 1> : interval_rows_kernel<false, 1>))
+                           : (c16 ? interval_rows_kernel<true, 0> : interval_rows_kernel<false, 0>);
+        const int bpc = std::max(1, std::min(32 / kIvWaves, kLdsBytes / (lds_c + kIvRowsStaticLds)));
+        const long long grid_r = std::min((long long)cus * bpc, (N + kIvTile - 1) / kIvTile);
+        // tiles of equal size, the same number for every block (10^6 reads in tiles of 256 are 3.8 per block: a last round
+        // in which a fifth of the blocks have nothing to do)
+        const long long rounds = (N + grid_r * kIvTile - 1) / (grid_r * kIvTile);
+        const int tile_reads = (int)((N + grid_r * rounds - 1) / (grid_r * rounds));
+        LAUNCH(kr, dim3((unsigned)grid_r), dim3(kIvWaves * kWave), lds_c, s, ix->dev, N, reinterpret_cast<const uint16_t *>(ws.kj),
+               g.kj_row, ws.qp, g.qp_stride, g.qp_recs, reinterpret_cast<void *>(r.rows), reinterpret_cast<long long *>(r.offsets),
+               (long long)r.cap_rows, bsums, cnt, block_shift, esc, sched_c, tile_reads);
+        return GENIE_OK;
+    }
+    // K_C, long reads and the slot form: intervals + final rows, 16 lanes per read (4 reads per wave pass), persistent blocks
+    // (half the blocks help on the 1 Mb reference, 1.50 -> 1.40 ms per 4 x 10^6 reads, but cost at 300 kb, 0.215 -> 0.250 ms
+    // per 10^6, with the same 8 MB table: not worth a rule)
+    long long grid_c = (long long)cus * (32 / kIvWaves);
+    const long long need_c = (N + kIvWaves * 4 * kIvUnroll - 1) / (kIvWaves * 4 * kIvUnroll);
+    if (grid_c > need_c) grid_c = need_c;
+    auto kc = r.offsets ? (c16 ? interval_kernel<true, true, true> : interval_kernel<true, true, false>)
                         : (c16 ? interval_kernel<false, WIDE, true> : interval_kernel<false, WIDE, false>);
     // CSR rows: through the scanned block sums and the counts; slots: `cap` per read
     LAUNCH(kc, dim3((unsigned)grid_c), dim3(kIvWaves * kWave), 0, s, ix->dev, N, ws.kj, g.kj_row, head, head_stride, ws.qp,

@@ -21,11 +21,13 @@
 //        positions that still cover the current one G x V at a time -- 16 x 1 straight from global memory (small
 //        batches), 2 x 8 from LDS windows of the row (batches of 32 768 reads or more).
 //
-//   K_C  interval_kernel                ONE LANE PER EMITTED SMEM (16 lanes per read).  Fills in the
+//   K_C  interval_rows_kernel / interval_kernel   ONE LANE PER EMITTED SMEM.  Fills in the
 //        SA interval [lo, hi] of every emitted substring: from ONE match-table entry where that decides
 //        (patterns of P2 .. P2 + 16 bases; longer ones that single out one key; the longest occurring prefix
-//        of an absent P2-mer), else the general bounded search over suffix-array rows, 64 at a time from a
-//        per-wave list; packed read from K_A's output.  Persistent 512-thread blocks.
+//        of an absent P2-mer; interval_from_entry), else the general bounded search over suffix-array rows, 64 at a
+//        time from a per-wave list; packed read from K_A's output.  Persistent 512-thread blocks.  Short reads in CSR
+//        form: interval_rows_kernel, the rows of a tile of 256 reads densely over the lanes, the tile's slots staged in
+//        LDS; long reads and the slot form: interval_kernel, 16 lanes per read.
 
 template <bool WIDE>
 struct ReadTraits {
@@ -461,7 +463,77 @@ __device__ __forceinline__ void emit_row(void *out, long long idx, int k, int j,
     }
 }
 
-template <bool CSR, bool WIDE, bool C16, int COUT = 0>
+// What ONE match-table entry (`ra`, and `rb` of the 32-byte form) says about the pattern of `len` bases whose window is `w`:
+// true and its rows in `iv` where the entry decides, false where the general search must.
+template <bool C16>
+__device__ __forceinline__ bool interval_from_entry(const int4 ra, const int4 rb, uint64_t w, int len, int P2,
+                                                    const __amdgpu_buffer_rsrc_t ov, bool act, int2 &iv)
+{
+    const uint32_t meta = (uint32_t)ra.x;
+    // every pattern here is an emitted SMEM, so it OCCURS: (a) an absent P2-mer whose longest occurring
+    // prefix is the pattern -> that prefix's rows, kept in the entry; (b) P2 .. P2 + 16 bases -> the keys
+    // that agree that far; (c) longer, with ONE key agreeing in all 16 bases -> that row.
+    bool fast = false;
+    iv = make_int2(-1, -1);
+    if (C16) {
+        // compact entry (genie_internal.h): the same three cases with 8-base keys; an entry of more than
+        // six suffixes continues in the per-row key array
+        const uint32_t cnt4 = (meta >> 24) & 15u, nib = meta >> 28, lb = meta & 0xFFFFFFu;
+        if (act && cnt4 == 0) {
+            if (len == (int)nib) { fast = true; iv = make_int2((int)lb, ra.y); }
+        } else if (act && (nib & kM16Wide) && cnt4 <= 3u && len >= P2) {          // three 16-base keys
+            const uint32_t xk = (uint32_t)((w << (2 * P2)) >> 32);
+            const int cl = len - P2 < 16 ? len - P2 : 16;
+            const uint32_t km = cl == 0 ? 0u : ~0u << (32 - 2 * cl);
+            const uint32_t bits = (((((uint32_t)ra.y ^ xk) & km) == 0 ? 1u : 0u) | ((((uint32_t)ra.z ^ xk) & km) == 0 ? 2u : 0u) |
+                                   ((((uint32_t)ra.w ^ xk) & km) == 0 ? 4u : 0u)) & ((1u << cnt4) - 1u);
+            fast = len <= P2 + 16 || __popc(bits) == 1;
+            if (bits) {
+                const int first = (int)lb + __ffs((int)bits) - 1;
+                iv = make_int2(first, first + __popc(bits) - 1);
+            }
+        } else if (act && (cnt4 == kM16More || !(nib & kM16General)) && len >= P2) {
+            const uint32_t total = cnt4 == kM16More ? 7u + nib : cnt4;
+            const uint32_t xk16 = (uint32_t)((w << (2 * P2)) >> 48);
+            const int cl = len - P2 < 8 ? len - P2 : 8;
+            const uint32_t km16 = cl == 0 ? 0u : (0xFFFFu << (16 - 2 * cl)) & 0xFFFFu;
+            const uint32_t k16[6] = {(uint32_t)ra.y & 0xFFFFu, (uint32_t)ra.y >> 16, (uint32_t)ra.z & 0xFFFFu,
+                                     (uint32_t)ra.z >> 16, (uint32_t)ra.w & 0xFFFFu, (uint32_t)ra.w >> 16};
+            const uint32_t ninl = cnt4 == kM16More ? (uint32_t)kM16Keys - 1u : cnt4;
+            uint32_t bits = 0, xm = 0xFFFFu;
+#pragma unroll
+            for (int i = 0; i < kM16Keys; i++) bits |= (((k16[i] ^ xk16) & km16) == 0 && (uint32_t)i < ninl) ? 1u << i : 0u;
+            if (cnt4 == kM16More) mt_ov_scan(ov, k16[5], (int)total - (kM16Keys - 1), xk16, km16, xm, bits);
+            fast = len <= P2 + 8 || __popc(bits) == 1;
+            if (bits) {                                  // adjacent rows: the keys ascend
+                const int first = (int)lb + __ffs((int)bits) - 1;
+                iv = make_int2(first, first + __popc(bits) - 1);
+            }
+        }
+    } else if (act && !(meta & kMatchSlow)) {
+        const uint32_t rows = meta >> 24;
+        if (rows == 0) {
+            if (len == (int)(meta & 0xFFu)) { fast = true; iv = make_int2(ra.y, ra.z); }
+        } else if (len >= P2) {
+            const uint32_t xk = (uint32_t)((w << (2 * P2)) >> 32);
+            const int cl = len - P2 < 16 ? len - P2 : 16;
+            const uint32_t km = cl == 0 ? 0u : ~0u << (32 - 2 * cl);
+            uint32_t bits = ((((uint32_t)ra.z ^ xk) & km) == 0 ? 1u : 0u) | ((((uint32_t)ra.w ^ xk) & km) == 0 ? 2u : 0u) |
+                            ((((uint32_t)rb.x ^ xk) & km) == 0 ? 4u : 0u) | ((((uint32_t)rb.y ^ xk) & km) == 0 ? 8u : 0u) |
+                            ((((uint32_t)rb.z ^ xk) & km) == 0 ? 16u : 0u) | ((((uint32_t)rb.w ^ xk) & km) == 0 ? 32u : 0u);
+            bits &= (1u << rows) - 1u;                   // rows <= kMatchKeys: the entry is not slow
+            fast = len <= P2 + 16 || __popc(bits) == 1;
+            if (bits) {                                  // adjacent rows: the keys ascend
+                const int first = (int)ra.y + __ffs((int)bits) - 1;
+                iv = make_int2(first, first + __popc(bits) - 1);
+            }
+        }
+    }
+    return fast;
+}
+
+// Long reads (WIDE) and the slot form; the CSR forms of short reads run interval_rows_kernel (below).
+template <bool CSR, bool WIDE, bool C16>
 __global__ void __launch_bounds__(kIvWaves * 64, 8) interval_kernel(DevIndex ix, long long N,
                                                                     const void *__restrict__ kj_in, int kj_stride,
                                                                     const uint8_t *__restrict__ head_in, int head_stride,
@@ -472,6 +544,8 @@ __global__ void __launch_bounds__(kIvWaves * 64, 8) interval_kernel(DevIndex ix,
                                                                     const int32_t *__restrict__ before_in_block, int block_shift,
                                                                     RowEscapes esc, int sched)
 {
+    static_assert(WIDE || !CSR, "short reads, CSR rows: interval_rows_kernel");
+    constexpr int COUT = 0;
     __shared__ int4 lists[kIvWaves][kIvList];            // {row index lo, hi, read, start | end << 16}
     typedef typename std::conditional<WIDE, uint32_t, uint16_t>::type kj_t;
     typedef typename std::conditional<WIDE, QRecs, QPlain>::type QIn;      // how K_A left the packed read (kernels.hip)
@@ -524,10 +598,6 @@ __global__ void __launch_bounds__(kIvWaves * 64, 8) interval_kernel(DevIndex ix,
             if (!CSR) c[u] = c[u] < cap ? c[u] : cap;
             more |= c[u] > 0;
         }
-        // the NEXT iteration's hand-off lines (four consecutive slots: packed-read records + head of the pairs row; the counts
-        // before each read in its block), asked for through the scalar cache behind this iteration's first loads: they come
-        // from HBM / the Infinity Cache (K_A and K_B wrote them a kernel ago) and would each hold a vector-miss slot nine
-        // times as long as a table entry does (scalar_touch_lines, kernels.hip)
         for (int t0 = 0; __any(more); t0 += 16) {
             const int t = t0 + sub;
             uint32_t e[U];
@@ -561,66 +631,8 @@ __global__ void __launch_bounds__(kIvWaves * 64, 8) interval_kernel(DevIndex ix,
             for (int u = 0; u < U; u++) {
                 const int k = (int)(e[u] & ((1u << ReadTraits<WIDE>::kj_shift) - 1)), j = (int)(e[u] >> ReadTraits<WIDE>::kj_shift);
                 const int len = j - k;
-                const uint32_t meta = (uint32_t)ra[u].x;
-                // every pattern here is an emitted SMEM, so it OCCURS: (a) an absent P2-mer whose longest occurring
-                // prefix is the pattern -> that prefix's rows, kept in the entry; (b) P2 .. P2 + 16 bases -> the keys
-                // that agree that far; (c) longer, with ONE key agreeing in all 16 bases -> that row.
-                bool fast = false;
-                int2 iv = make_int2(-1, -1);
-                if (C16) {
-                    // compact entry (genie_internal.h): the same three cases with 8-base keys; an entry of more than
-                    // six suffixes continues in the per-row key array
-                    const uint32_t cnt4 = (meta >> 24) & 15u, nib = meta >> 28, lb = meta & 0xFFFFFFu;
-                    if (act[u] && cnt4 == 0) {
-                        if (len == (int)nib) { fast = true; iv = make_int2((int)lb, ra[u].y); }
-                    } else if (act[u] && (nib & kM16Wide) && cnt4 <= 3u && len >= P2) {          // three 16-base keys
-                        const uint32_t xk = (uint32_t)((w[u] << (2 * P2)) >> 32);
-                        const int cl = len - P2 < 16 ? len - P2 : 16;
-                        const uint32_t km = cl == 0 ? 0u : ~0u << (32 - 2 * cl);
-                        const uint32_t bits = (((((uint32_t)ra[u].y ^ xk) & km) == 0 ? 1u : 0u) | ((((uint32_t)ra[u].z ^ xk) & km) == 0 ? 2u : 0u) |
-                                               ((((uint32_t)ra[u].w ^ xk) & km) == 0 ? 4u : 0u)) & ((1u << cnt4) - 1u);
-                        fast = len <= P2 + 16 || __popc(bits) == 1;
-                        if (bits) {
-                            const int first = (int)lb + __ffs((int)bits) - 1;
-                            iv = make_int2(first, first + __popc(bits) - 1);
-                        }
-                    } else if (act[u] && (cnt4 == kM16More || !(nib & kM16General)) && len >= P2) {
-                        const uint32_t total = cnt4 == kM16More ? 7u + nib : cnt4;
-                        const uint32_t xk16 = (uint32_t)((w[u] << (2 * P2)) >> 48);
-                        const int cl = len - P2 < 8 ? len - P2 : 8;
-                        const uint32_t km16 = cl == 0 ? 0u : (0xFFFFu << (16 - 2 * cl)) & 0xFFFFu;
-                        const uint32_t k16[6] = {(uint32_t)ra[u].y & 0xFFFFu, (uint32_t)ra[u].y >> 16, (uint32_t)ra[u].z & 0xFFFFu,
-                                                 (uint32_t)ra[u].z >> 16, (uint32_t)ra[u].w & 0xFFFFu, (uint32_t)ra[u].w >> 16};
-                        const uint32_t ninl = cnt4 == kM16More ? (uint32_t)kM16Keys - 1u : cnt4;
-                        uint32_t bits = 0, xm = 0xFFFFu;
-#pragma unroll
-                        for (int i = 0; i < kM16Keys; i++) bits |= (((k16[i] ^ xk16) & km16) == 0 && (uint32_t)i < ninl) ? 1u << i : 0u;
-                        if (cnt4 == kM16More) mt_ov_scan(ov, k16[5], (int)total - (kM16Keys - 1), xk16, km16, xm, bits);
-                        fast = len <= P2 + 8 || __popc(bits) == 1;
-                        if (bits) {                                  // adjacent rows: the keys ascend
-                            const int first = (int)lb + __ffs((int)bits) - 1;
-                            iv = make_int2(first, first + __popc(bits) - 1);
-                        }
-                    }
-                } else if (act[u] && !(meta & kMatchSlow)) {
-                    const uint32_t rows = meta >> 24;
-                    if (rows == 0) {
-                        if (len == (int)(meta & 0xFFu)) { fast = true; iv = make_int2(ra[u].y, ra[u].z); }
-                    } else if (len >= P2) {
-                        const uint32_t xk = (uint32_t)((w[u] << (2 * P2)) >> 32);
-                        const int cl = len - P2 < 16 ? len - P2 : 16;
-                        const uint32_t km = cl == 0 ? 0u : ~0u << (32 - 2 * cl);
-                        uint32_t bits = ((((uint32_t)ra[u].z ^ xk) & km) == 0 ? 1u : 0u) | ((((uint32_t)ra[u].w ^ xk) & km) == 0 ? 2u : 0u) |
-                                        ((((uint32_t)rb[u].x ^ xk) & km) == 0 ? 4u : 0u) | ((((uint32_t)rb[u].y ^ xk) & km) == 0 ? 8u : 0u) |
-                                        ((((uint32_t)rb[u].z ^ xk) & km) == 0 ? 16u : 0u) | ((((uint32_t)rb[u].w ^ xk) & km) == 0 ? 32u : 0u);
-                        bits &= (1u << rows) - 1u;                   // rows <= kMatchKeys: the entry is not slow
-                        fast = len <= P2 + 16 || __popc(bits) == 1;
-                        if (bits) {                                  // adjacent rows: the keys ascend
-                            const int first = (int)ra[u].y + __ffs((int)bits) - 1;
-                            iv = make_int2(first, first + __popc(bits) - 1);
-                        }
-                    }
-                }
+                int2 iv;
+                const bool fast = interval_from_entry<C16>(ra[u], rb[u], w[u], len, P2, ov, act[u], iv);
                 if (fast) emit_row<COUT>(out, base[u] + t, k, j, iv.x, iv.y, esc);
                 const bool general = act[u] && !fast;
                 const unsigned long long gb = __ballot(general);
@@ -639,6 +651,160 @@ __global__ void __launch_bounds__(kIvWaves * 64, 8) interval_kernel(DevIndex ix,
                 }
             }
         }
+    }
+    if (nlist) search_list(0, nlist);
+}
+
+// ------------------------------------------------------------------ K_C, short reads, CSR rows
+// ONE LANE PER ROW over staged read tiles.  The kernel above gives every read 16 lanes whatever its count, repeats the
+// addressing of slot, head and offsets every four reads, and reaches its table entry through two loads that come from HBM
+// (head, window).  Here a persistent block takes TILES of `tile_reads` (at most kIvTile) consecutive reads -- the host cuts
+// the batch so that every block gets the same number of tiles:
+//   1. it copies the tile's slots (packed read + head of the pairs row: contiguous, 16-byte aligned) into LDS, 16 bytes per
+//      lane and all loads in flight together, with the tile's counts-before-the-read;
+//   2. one lane per read writes offsets[] and leaves in LDS the read's first row, relative to the tile's, and its own index
+//      for every 64th row of the tile that is one of its rows (chunk_read);
+//   3. the tile's rows are worked through in chunks of 64 per wave: a row finds its read by bisecting the starts between
+//      the reads of its chunk's first row and of the next chunk's (a handful: three steps, not eight), takes its pair and
+//      its window from LDS, loads ONE table entry, and stores at tile base + row -- a wave's stores are consecutive rows.
+// What the entry cannot decide goes to the wave's list and the general search, as above (the list outlives a tile, so the
+// search reads the packed read from global memory).  Rows, offsets, totals and escapes are those of interval_kernel.
+constexpr int kIvTile = 256;         // most reads per tile (tiles need not be traversal blocks)
+constexpr int kIvChunks = kIvTile * 255 / kWave + 2;                               // 64-row chunks of a tile's rows, and one
+constexpr int kIvRowsStaticLds = kIvWaves * kIvList * 16 + 2 * kIvTile * 4 + ((kIvChunks + 15) & ~15) + 16;   // lists, starts, chunk_read, row count
+
+template <bool C16, int COUT>
+__global__ void __launch_bounds__(kIvWaves * 64, 8) interval_rows_kernel(DevIndex ix, long long N,
+                                                                         const uint16_t *__restrict__ kj_in, int kj_stride,
+                                                                         const RefRec *__restrict__ qp_in, int qp_stride, int qp_recs,
+                                                                         void *__restrict__ out,
+                                                                         long long *__restrict__ offsets, long long out_cap,
+                                                                         const unsigned long long *__restrict__ block_base,
+                                                                         const int32_t *__restrict__ before_in_block, int block_shift,
+                                                                         RowEscapes esc, int sched, int tile_reads)
+{
+    extern __shared__ __align__(16) uint8_t smem[];      // the tile's slots: kIvTile x qp_stride x 16 bytes
+    __shared__ int4 lists[kIvWaves][kIvList];            // {row index lo, hi, read, start | end << 16}
+    __shared__ int starts[2 * kIvTile];                  // first row of every read of the tile, relative to the tile's first;
+                                                         // beyond the tile's reads: INT_MAX (a bisection may look that far)
+    __shared__ uint8_t chunk_read[kIvChunks];            // the read that row 64 c of the tile belongs to
+    __shared__ int tile_rows;
+    constexpr int kHeadEntries = kPairHeadWords * 8 / 2;
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = rfl((int)(threadIdx.x >> 6));
+    const int P2 = ix.P2;
+    const int slot_bytes = qp_stride * 16, head_off = qp_recs * 16;
+    const __amdgpu_buffer_rsrc_t ov =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<MatchOv16 *>(ix.ov), 0, ix.ov_entries * (int)sizeof(MatchOv16), 0x00020000);
+    int4 *list = lists[wave];
+    int nlist = 0;
+    // the general search of list[o .. o + n), n <= 64
+    auto search_list = [&](int o, int n) {
+        if (lane < n) {
+            const int4 en = list[o + lane];
+            const int k = en.w & 0xFFFF, j = (int)((uint32_t)en.w >> 16);
+            const QPlain qp{reinterpret_cast<const uint64_t *>(qp_in + (long long)en.z * qp_stride)};
+            const int2 iv = sa_interval(ix, ix.dir, qp, k, j - k);
+            emit_row<COUT>(out, ((long long)en.y << 32) | (uint32_t)en.x, k, j, iv.x, iv.y, esc);
+        }
+    };
+    // (issue priority rotated per tile, as in the match-statistics kernel: the CU serves its oldest waves first)
+    const bool rotate = !(sched & 1);
+    int it = (int)(blockIdx.x / (uint32_t)(sched >> 8));
+    const long long tiles = (N + tile_reads - 1) / tile_reads;
+    if ((int)threadIdx.x < kIvTile) starts[kIvTile + threadIdx.x] = 0x7FFFFFFF;      // (the barriers of the first tile order this)
+    for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x, it++) {
+        if (rotate) set_wave_priority(it);
+        const long long r0 = tile * tile_reads;
+        const int reads = (int)(N - r0 < (long long)tile_reads ? N - r0 : (long long)tile_reads);
+        // the tile's first row (block-uniform) and, one lane per read, the read's own
+        const long long tile_base = (long long)block_base[r0 >> block_shift] + before_in_block[r0];
+        const bool have = (int)threadIdx.x < reads;
+        const long long r = r0 + (have ? (int)threadIdx.x : 0);
+        const long long base = have ? (long long)block_base[r >> block_shift] + before_in_block[r] : 0;
+        {
+            const uint4 *src = reinterpret_cast<const uint4 *>(qp_in + r0 * (long long)qp_stride);
+            uint4 *dst = reinterpret_cast<uint4 *>(smem);
+            const int units = reads * qp_stride;
+            constexpr int kInFlight = 4;
+            for (int e0 = threadIdx.x; e0 < units; e0 += kInFlight * kIvWaves * kWave) {
+                uint4 v[kInFlight];
+#pragma unroll
+                for (int u = 0; u < kInFlight; u++) {
+                    const int e = e0 + u * kIvWaves * kWave;
+                    v[u] = e < units ? src[e] : make_uint4(0, 0, 0, 0);
+                }
+#pragma unroll
+                for (int u = 0; u < kInFlight; u++) {
+                    const int e = e0 + u * kIvWaves * kWave;
+                    if (e < units) dst[e] = v[u];
+                }
+            }
+        }
+        __syncthreads();
+        if ((int)threadIdx.x < kIvTile) {
+            // entry 0 of the head is the count; offsets[N] (the packed forms: word 0 of the totals) by whoever holds the last read
+            const int c = have ? (int)*reinterpret_cast<const uint16_t *>(smem + threadIdx.x * slot_bytes + head_off) : 0;
+            if (have) {
+                if (!COUT) offsets[r] = base;
+                if (r == N - 1) offsets[COUT ? 0 : N] = base + c;
+            }
+            const int first = have ? (int)(base - tile_base) : 0x7FFFFFFF;
+            starts[threadIdx.x] = first;
+            // every 64th row of the tile belongs to one read with rows; the last read also answers for the first such row
+            // behind the tile's rows, which bounds the last chunk
+            if (have)
+                for (int ch = (first + kWave - 1) >> 6; (ch << 6) < first + c; ch++) chunk_read[ch] = (uint8_t)threadIdx.x;
+            if (have && (int)threadIdx.x == reads - 1) {
+                tile_rows = first + c;
+                chunk_read[(first + c + kWave - 1) >> 6] = (uint8_t)threadIdx.x;
+            }
+        }
+        __syncthreads();
+        const int total = tile_rows;
+        for (int q0 = wave * kWave; q0 < total && tile_base + q0 < out_cap; q0 += kIvWaves * kWave) {
+            const int q = q0 + lane;
+            const bool act = q < total && tile_base + q < out_cap;
+            // the read of row q: the last one that starts at or before it (reads without rows share their successor's start),
+            // which lies between the read of the chunk's first row and that of the next chunk's: every later read starts
+            // behind this chunk, so the bisection needs no upper bound
+            const int lo = rfl((int)chunk_read[q0 >> 6]), span = rfl((int)chunk_read[(q0 >> 6) + 1]) - lo;
+            int i = lo;
+            for (int s = span > 0 ? 1 << (31 - __builtin_clz(span)) : 0; s > 0; s >>= 1) i += starts[i + s] <= q ? s : 0;
+            const int t = act ? q - starts[i] : 0;
+            const uint8_t *slot = smem + i * slot_bytes;
+            uint32_t e = 0;
+            if (act) e = t + 1 < kHeadEntries ? (uint32_t)reinterpret_cast<const uint16_t *>(slot + head_off)[t + 1]
+                                              : (uint32_t)kj_in[(r0 + i) * (long long)kj_stride + t + 1];
+            const int k = (int)(e & 0xFFu), j = (int)(e >> 8);
+            // the window QPlain::win returns: words k / 32 and k / 32 + 1 of the slot
+            const uint64_t *wp = reinterpret_cast<const uint64_t *>(slot) + (k >> 5);
+            const uint64_t w = act ? funnel(wp[0], wp[1], (k & 31) * 2) : 0ull;
+            const uint32_t c = (uint32_t)(w >> (64 - 2 * P2));
+            const int4 *en = C16 ? reinterpret_cast<const int4 *>(reinterpret_cast<const MatchRec16 *>(ix.mtab) + c)
+                                 : reinterpret_cast<const int4 *>(ix.mtab + c);
+            int4 ra = make_int4(0, 0, 0, 0), rb = make_int4(0, 0, 0, 0);
+            if (act) { ra = en[0]; if (!C16) rb = en[1]; }
+            int2 iv;
+            const bool fast = interval_from_entry<C16>(ra, rb, w, j - k, P2, ov, act, iv);
+            if (fast) emit_row<COUT>(out, tile_base + q, k, j, iv.x, iv.y, esc);
+            const bool general = act && !fast;
+            const unsigned long long gb = __ballot(general);
+            if (gb) {
+                if (general) {
+                    const long long row = tile_base + q;
+                    list[nlist + __popcll(gb & ((1ull << lane) - 1ull))] = make_int4((int)(uint32_t)row, (int)(row >> 32), (int)(r0 + i), k | (j << 16));
+                }
+                nlist += __popcll(gb);
+                wave_lds_fence();
+                if (nlist >= 64) {
+                    nlist -= 64;
+                    search_list(nlist, 64);
+                    wave_lds_fence();
+                }
+            }
+        }
+        __syncthreads();                                  // the next tile overwrites the slots and the starts
     }
     if (nlist) search_list(0, nlist);
 }
