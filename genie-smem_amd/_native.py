@@ -47,6 +47,7 @@ SYMBOLS = [
     "genie_find_smems_long_ex", "genie_find_smems_long_ex_workspace_bytes",
     "genie_find_smems_both", "genie_find_smems_both_workspace_bytes",
     "genie_reads_from_text", "genie_reads_from_text_tmp_bytes",
+    "genie_reads_from_fasta", "genie_reads_from_fasta_tmp_bytes",
     "genie_compact_tmp_bytes",
     "genie_compact_smems", "genie_locate_tmp_bytes", "genie_locate", "genie_index_train_rmi", "genie_index_rmi_models", "genie_launch_info", "genie_search_kernel_name", "genie_index_set_option", "genie_index_set_stage_events", "genie_strerror", "genie_last_hip_error",
 ]
@@ -69,7 +70,7 @@ class GenieError(RuntimeError):
 
 def build(force=False):
     """Compile libgenie_smem.so for gfx950 with hipcc (csrc/Makefile), in-tree."""
-    srcs = [os.path.join(CSRC, f) for f in ("kernels.hip", "index_build.hip", "short_read_kernel.inc", "match_table_kernel.inc", "match_table_body.inc", "match_table_long_body.inc", "split_reads.inc", "long_reads.inc", "long_units.inc", "text_reads.inc", "capi.cpp", "index_host.cpp", "genie_internal.h", "Makefile")]
+    srcs = [os.path.join(CSRC, f) for f in ("kernels.hip", "index_build.hip", "short_read_kernel.inc", "match_table_kernel.inc", "match_table_body.inc", "match_table_long_body.inc", "split_reads.inc", "long_reads.inc", "long_units.inc", "text_reads.inc", "fasta_reads.inc", "capi.cpp", "index_host.cpp", "genie_internal.h", "Makefile")]
     srcs.append(os.path.join(os.path.dirname(_PKG), "include", "genie_smem.h"))
     newest = max(os.path.getmtime(s) for s in srcs)
     if force or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < newest:
@@ -132,6 +133,8 @@ def lib():
         "genie_find_smems_both_workspace_bytes": (i64, [i64, i32]),
         "genie_reads_from_text_tmp_bytes": (i64, [i64, i64]),
         "genie_reads_from_text": (C.c_int, [vp, i64, i32, i32, vp, vp, i64, vp, i64, vp, vp, i64, vp]),
+        "genie_reads_from_fasta_tmp_bytes": (i64, [i64, i64]),
+        "genie_reads_from_fasta": (C.c_int, [vp, i64, i32, vp, vp, i64, vp, vp, i64, vp, vp, i64, vp]),
         "genie_compact_tmp_bytes": (i64, [i64]),
         "genie_compact_smems": (C.c_int, [vp, vp, i64, i32, vp, vp, i64, vp, vp]),
         "genie_index_train_rmi": (C.c_int, [vp, i32, vp, vp, vp]),

@@ -488,6 +488,28 @@ int genie_reads_from_text(const uint8_t *d_text, int64_t text_bytes, int32_t for
                                   d_tmp, stream);
 }
 
+int64_t genie_reads_from_fasta_tmp_bytes(int64_t text_bytes, int64_t cap_reads)
+{
+    if (text_bytes < 0 || cap_reads < 0) return (int64_t)GENIE_E_INVALID;
+    return reads_from_fasta_tmp_bytes(text_bytes, cap_reads);
+}
+
+int genie_reads_from_fasta(const uint8_t *d_text, int64_t text_bytes, int32_t flags, const uint8_t *code_of_byte, uint8_t *d_bases,
+                           int64_t cap_bases, int64_t *d_read_offsets, int64_t *d_record_starts, int64_t cap_reads, int64_t *out5,
+                           void *d_tmp, int64_t tmp_bytes, void *stream)
+{
+    // argument checks first: they need no device
+    if (text_bytes < 0 || cap_bases < 0 || cap_reads < 0 || tmp_bytes < 0 || !code_of_byte || !out5 || (text_bytes > 0 && !d_text))
+        return GENIE_E_INVALID;
+    if (flags & ~GENIE_TEXT_PARTIAL) return GENIE_E_INVALID;
+    if ((d_bases == nullptr) != (d_read_offsets == nullptr) || (!d_read_offsets && d_record_starts)) return GENIE_E_INVALID;
+    if (((reinterpret_cast<uintptr_t>(d_read_offsets) | reinterpret_cast<uintptr_t>(d_record_starts)) & 7) != 0) return GENIE_E_INVALID;
+    if (!d_tmp || (reinterpret_cast<uintptr_t>(d_tmp) & 255) != 0 || tmp_bytes < reads_from_fasta_tmp_bytes(text_bytes, cap_reads))
+        return GENIE_E_CAPACITY;
+    return launch_reads_from_fasta(d_text, text_bytes, flags, code_of_byte, d_bases, cap_bases, d_read_offsets, d_record_starts, cap_reads,
+                                   out5, d_tmp, stream);
+}
+
 static int find_smems_packed_any(const genie_index *ix, int32_t mode, const uint8_t *d_reads2bit, const int32_t *d_lens, int64_t N,
                                  int32_t stride_bytes, int32_t fixed_len, int32_t min_len, uint8_t *d_counts8, uint8_t *d_status8,
                                  void *d_rows, int64_t out_cap_rows, int64_t *d_totals, int64_t *d_escapes, int64_t cap_escapes,

@@ -391,6 +391,10 @@ int64_t reads_from_text_tmp_bytes(int64_t text_bytes, int64_t cap_reads);
 int launch_reads_from_text(const uint8_t *d_text, int64_t text_bytes, int32_t format, int32_t flags, const uint8_t *code_of_byte,
                            uint8_t *d_bases, int64_t cap_bases, int64_t *d_read_offsets, int64_t cap_reads, int64_t *out5,
                            void *d_tmp, void *stream);
+int64_t reads_from_fasta_tmp_bytes(int64_t text_bytes, int64_t cap_reads);
+int launch_reads_from_fasta(const uint8_t *d_text, int64_t text_bytes, int32_t flags, const uint8_t *code_of_byte, uint8_t *d_bases,
+                            int64_t cap_bases, int64_t *d_read_offsets, int64_t *d_record_starts, int64_t cap_reads, int64_t *out5,
+                            void *d_tmp, void *stream);
 int launch_find_smems_packed(const genie_index *ix, int32_t mode, const FindBatch &b, uint8_t *d_counts8, uint8_t *d_status8,
                              void *d_rows8, int64_t out_cap_rows, int64_t *d_totals, int64_t *d_escapes, int64_t cap_escapes,
                              void *stream, int row_bytes = 8);

@@ -1370,5 +1370,6 @@ int launch_locate(const genie_index *ix, const int32_t *d_lohi, int32_t stride, 
 #include "long_reads.inc"
 #include "long_units.inc"
 #include "text_reads.inc"
+#include "fasta_reads.inc"
 
 }  // namespace genie

@@ -340,6 +340,24 @@ __global__ void __launch_bounds__(kScanBlock) tr_offsets_apply(long long *__rest
     if (i == 0) offs[0] = 0;
 }
 
+// The block's run of codes, staged in LDS on the 16-byte grid of its destination: stage bytes [olead, olead + total) go to
+// bases[d0 .. d0 + total), 16 bytes per lane, byte by byte only at the run's two ends.  Every thread of the block calls it,
+// behind the barrier that follows the staging.
+__device__ __forceinline__ void tr_store_run(const uint4 *stage, int olead, int total, uint8_t *__restrict__ bases, long long d0)
+{
+    const uint8_t *st = reinterpret_cast<const uint8_t *>(stage);
+    const int end = olead + total;
+    for (int ch = threadIdx.x; 16 * ch < end; ch += kTrBlock) {
+        const int lo = 16 * ch;
+        if (lo >= olead && lo + 16 <= end) {
+            *reinterpret_cast<uint4 *>(bases + (d0 + (lo - olead))) = stage[ch];
+        } else {
+            for (int k = 0; k < 16; k++)
+                if (lo + k >= olead && lo + k < end) bases[d0 + (lo + k - olead)] = st[lo + k];
+        }
+    }
+}
+
 __global__ void __launch_bounds__(kTrBlock) tr_translate_kernel(const uint8_t *__restrict__ text, long long T, int lead, int format,
                                                                 const TrTable table, const unsigned long long *__restrict__ cnt,
                                                                 const long long *__restrict__ last, const long long *__restrict__ state,
@@ -414,16 +432,7 @@ __global__ void __launch_bounds__(kTrBlock) tr_translate_kernel(const uint8_t *_
         keep &= keep - 1;
     }
     __syncthreads();
-    const int end = olead + (int)total;                             // stage[olead .. end) goes to bases[d0 .. d0 + total)
-    for (int ch = t; 16 * ch < end; ch += kTrBlock) {
-        const int lo = 16 * ch;
-        if (lo >= olead && lo + 16 <= end) {
-            *reinterpret_cast<uint4 *>(bases + (d0 + (lo - olead))) = stage[ch];
-        } else {
-            for (int k = 0; k < 16; k++)
-                if (lo + k >= olead && lo + k < end) bases[d0 + (lo + k - olead)] = st[lo + k];
-        }
-    }
+    tr_store_run(stage, olead, (int)total, bases, d0);
 }
 
 inline long long tr_tiles(int64_t text_bytes, int lead) { return (text_bytes + lead + kTrTile - 1) / kTrTile; }
@@ -431,6 +440,21 @@ inline int64_t tr_scan_blocks(int64_t text_bytes, int64_t cap_reads)
 {
     const int64_t most = cap_reads < text_bytes ? cap_reads : text_bytes;   // a text of T bytes has at most T lines
     return most < 1 ? 1 : (most + kScanBlock - 1) / kScanBlock;
+}
+
+// code_of_byte as it travels to the kernels: clamped to 0..4
+inline TrTable tr_table(const uint8_t *code_of_byte)
+{
+    TrTable table;
+    for (int i = 0; i < 64; i++) {
+        uint32_t w = 0;
+        for (int k = 0; k < 4; k++) {
+            const uint8_t c = code_of_byte[4 * i + k];
+            w |= (uint32_t)(c <= 3 ? c : 4) << (8 * k);
+        }
+        table.w[i] = w;
+    }
+    return table;
 }
 
 struct TextArea {
@@ -481,15 +505,7 @@ int launch_reads_from_text(const uint8_t *d_text, int64_t text_bytes, int32_t fo
     if (ntiles > 0x7fffffffll || tr_scan_blocks(text_bytes, cap_reads) > 0x7fffffffll) return GENIE_E_INVALID;   // one block each
     TextArea a;
     text_layout(static_cast<uint8_t *>(d_tmp), text_bytes, cap_reads, &a);
-    TrTable table;
-    for (int i = 0; i < 64; i++) {
-        uint32_t w = 0;
-        for (int k = 0; k < 4; k++) {
-            const uint8_t c = code_of_byte[4 * i + k];
-            w |= (uint32_t)(c <= 3 ? c : 4) << (8 * k);
-        }
-        table.w[i] = w;
-    }
+    const TrTable table = tr_table(code_of_byte);
     const dim3 tgrid((unsigned)ntiles), tblock(kTrBlock);
     LAUNCH(tr_count_kernel, tgrid, tblock, 0, s, d_text, (long long)text_bytes, lead, a.cnt, a.last);
     LAUNCH(tr_scan_kernel, dim3(1), dim3(kScanBlock), 0, s, a.cnt, a.last, ntiles, (long long)text_bytes, (int)format, partial, a.state);

@@ -129,10 +129,11 @@ class SMEM:
 
     def find_smems_text(self, data, fmt="lines", mode="bwa", minimum_length=1, both_strands=False, split_breaks=True,
                         fold_case=False):
-        """SMEMs of the reads in a text: every line a read (fmt "lines") or four-line FASTQ records (fmt "fastq").  data:
-        bytes-like, numpy uint8 or torch uint8, on the host or the device.  The text is cut into reads and translated on the
-        device (text_reads.reads_from_text with ExactMatch.byte_codes(fold_case): the codes encode_lenient gives), then
-        searched as find_smems_long((bases, read_offsets), ...) with the same options.  -> (offsets, smems[S, 4], status)."""
+        """SMEMs of the reads in a text: every line a read (fmt "lines"), four-line FASTQ records (fmt "fastq") or FASTA
+        records with wrapped sequences (fmt "fasta").  data: bytes-like, numpy uint8 or torch uint8, on the host or the
+        device.  The text is cut into reads and translated on the device (text_reads.reads_from_text with
+        ExactMatch.byte_codes(fold_case): the codes encode_lenient gives), then searched as
+        find_smems_long((bases, read_offsets), ...) with the same options.  -> (offsets, smems[S, 4], status)."""
         return self._find_text(data, fmt, False, mode, minimum_length, both_strands, split_breaks, fold_case)[:3]
 
     def _find_text(self, data, fmt, partial, mode, minimum_length, both_strands, split_breaks, fold_case):
@@ -142,12 +143,14 @@ class SMEM:
         res = ix.find_smems_long(mode, bases, read_offsets, minimum_length, both_strands=both_strands, split_breaks=split_breaks)
         return res + (read_offsets.numel() - 1, consumed)
 
-    def iter_fastq_smems(self, path, chunk_bytes=64 << 20, mode="bwa", minimum_length=1, both_strands=False, split_breaks=True,
-                         fold_case=False):
-        """find_smems_text over a FASTQ file of any size, a chunk at a time: yields (offsets, smems, status) of the records that
-        are complete in each chunk of about chunk_bytes bytes; the unfinished record at a chunk's end is carried into the next
-        one.  A chunk that holds no complete record grows by another chunk_bytes until it does (or the file ends).  The
-        concatenated reads are those of find_smems_text on the whole file."""
+    def iter_text_smems(self, path, fmt, chunk_bytes=64 << 20, mode="bwa", minimum_length=1, both_strands=False, split_breaks=True,
+                        fold_case=False):
+        """find_smems_text over a file of any size, a chunk at a time: yields (offsets, smems, status) of the reads (records)
+        that are complete in each chunk of about chunk_bytes bytes; the unfinished one at a chunk's end is carried into the
+        next chunk.  A chunk that holds no complete read grows by another chunk_bytes until it does (or the file ends), and
+        is parsed again from its start each time it grows: one record much larger than chunk_bytes (a chromosome in a
+        FASTA file) is re-parsed once per growth step, so choose chunk_bytes above the largest record.  The concatenated
+        reads are those of find_smems_text on the whole file."""
         chunk_bytes = max(int(chunk_bytes), 1)
         opts = (mode, minimum_length, both_strands, split_breaks, fold_case)
         with open(path, "rb") as fh:
@@ -158,12 +161,22 @@ class SMEM:
                 buf = carry + fresh
                 if last:
                     if buf:
-                        yield self._find_text(buf, "fastq", False, *opts)[:3]
+                        yield self._find_text(buf, fmt, False, *opts)[:3]
                     return
-                offsets, smems, status, n_reads, consumed = self._find_text(buf, "fastq", True, *opts)
+                offsets, smems, status, n_reads, consumed = self._find_text(buf, fmt, True, *opts)
                 carry = buf[consumed:]                              # no complete record: everything, and the chunk grows
                 if n_reads:
                     yield offsets, smems, status
+
+    def iter_fastq_smems(self, path, chunk_bytes=64 << 20, mode="bwa", minimum_length=1, both_strands=False, split_breaks=True,
+                         fold_case=False):
+        """iter_text_smems over a FASTQ file (four-line records)."""
+        return self.iter_text_smems(path, "fastq", chunk_bytes, mode, minimum_length, both_strands, split_breaks, fold_case)
+
+    def iter_fasta_smems(self, path, chunk_bytes=64 << 20, mode="bwa", minimum_length=1, both_strands=False, split_breaks=True,
+                         fold_case=False):
+        """iter_text_smems over a FASTA file ('>' header lines, sequences wrapped over any number of lines)."""
+        return self.iter_text_smems(path, "fasta", chunk_bytes, mode, minimum_length, both_strands, split_breaks, fold_case)
 
     def find_smems_lut(self, reads, lens=None):
         return self._find("lut", reads, lens, 1)

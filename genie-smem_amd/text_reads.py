@@ -1,8 +1,9 @@
-"""Reads from text on the device (genie_reads_from_text): the bytes of a file with one read per line, or of a FASTQ file
-with four-line records, become base codes back to back and int64 offsets -- the (bases, read_offsets) that
-GenieIndex.find_smems_long takes.  The text travels over the host link as it is, one byte per base; nothing is encoded on
-the host."""
+"""Reads from text on the device (genie_reads_from_text, genie_reads_from_fasta): the bytes of a file with one read per
+line, of a FASTQ file with four-line records, or of a FASTA file whose sequences are wrapped over any number of lines,
+become base codes back to back and int64 offsets -- the (bases, read_offsets) that GenieIndex.find_smems_long takes.  The
+text travels over the host link as it is, one byte per base; nothing is encoded on the host."""
 import ctypes as C
+import re
 import warnings
 
 import numpy as np
@@ -12,12 +13,17 @@ from . import _native as N
 
 
 class TextFormatError(ValueError):
-    """A malformed FASTQ record (GENIE_E_INVALID found on the device); `record` is the first one."""
+    """A malformed FASTQ record or FASTA text (GENIE_E_INVALID found on the device); `record` is the first bad record
+    (FASTA: 0, the text does not begin with a header line)."""
 
     def __init__(self, record, fmt):
         self.record = int(record)
-        super().__init__(f"{fmt} text: record {self.record} is malformed (a header line must start with '@', a separator "
-                         "line with '+', and without partial=True the last record must be complete)")
+        if fmt == "fasta":
+            why = "a non-empty line stands in front of the first '>' header line"
+        else:
+            why = ("a header line must start with '@', a separator line with '+', and without partial=True the last record "
+                   "must be complete")
+        super().__init__(f"{fmt} text: record {self.record} is malformed ({why})")
 
 
 def _text_tensor(data, device):
@@ -39,19 +45,28 @@ def _text_tensor(data, device):
         return torch.from_numpy(a).to(device)
 
 
-def reads_from_text(data, fmt="lines", code_of_byte=None, partial=False, device="cuda"):
+FORMATS = tuple(N.TEXT_FORMATS) + ("fasta",)
+_NAME = re.compile(rb"[^ \t\r\n]*")
+
+
+def reads_from_text(data, fmt="lines", code_of_byte=None, partial=False, device="cuda", return_starts=False):
     """-> (bases uint8[total_bases], read_offsets int64[N + 1], consumed): two tensors on `device` and a byte count.
-    data: bytes-like, numpy uint8 or torch uint8 (host or device).  fmt: "lines" (every line a read) or "fastq" (four-line
-    records).  code_of_byte: 256 uint8 entries (ExactMatch.byte_codes(); default A C G T -> 0 1 2 3, anything else 4).
-    partial: the text is a chunk of a longer stream -- the unfinished last line (record) is left alone and `consumed` says
-    where it starts.  Two native calls: one sizes the outputs, one fills them.  A malformed FASTQ raises TextFormatError."""
+    data: bytes-like, numpy uint8 or torch uint8 (host or device).  fmt: "lines" (every line a read), "fastq" (four-line
+    records) or "fasta" ('>' header lines, sequences wrapped over any number of lines).  code_of_byte: 256 uint8 entries
+    (ExactMatch.byte_codes(); default A C G T -> 0 1 2 3, anything else 4).  partial: the text is a chunk of a longer stream
+    -- the unfinished last line (record) is left alone and `consumed` says where it starts.  return_starts ("fasta" only):
+    a fourth value, record_starts int64[N] on `device`, the text position of every record's '>' (see record_names).  Two
+    native calls: one sizes the outputs, one fills them.  A malformed FASTQ or FASTA raises TextFormatError."""
     device = torch.device(device)
     if device.type != "cuda":
         raise RuntimeError("reads_from_text runs on an MI355X only (no CPU fallback); device is " + str(device))
     if device.index is None:
         device = torch.device("cuda", torch.cuda.current_device())
-    if fmt not in N.TEXT_FORMATS:
-        raise ValueError(f"fmt must be one of {sorted(N.TEXT_FORMATS)}, got {fmt!r}")
+    if fmt not in FORMATS:
+        raise ValueError(f"fmt must be one of {sorted(FORMATS)}, got {fmt!r}")
+    fasta = fmt == "fasta"
+    if return_starts and not fasta:
+        raise ValueError("return_starts needs fmt='fasta'")
     if code_of_byte is None:
         code_of_byte = default_byte_codes()
     table = np.ascontiguousarray(code_of_byte, np.uint8)
@@ -62,26 +77,52 @@ def reads_from_text(data, fmt="lines", code_of_byte=None, partial=False, device=
     nbytes = text.numel()
     flags = N.TEXT_PARTIAL if partial else 0
     out5 = (C.c_int64 * 5)()
+    name = "genie_reads_from_fasta" if fasta else "genie_reads_from_text"
+    size_of = getattr(lib, name + "_tmp_bytes")
 
-    def call(bases, offsets, cap_bases, cap_reads):
-        tmp_bytes = int(lib.genie_reads_from_text_tmp_bytes(nbytes, cap_reads))
+    def call(bases, offsets, starts, cap_bases, cap_reads):
+        tmp_bytes = int(size_of(nbytes, cap_reads))
         tmp = torch.empty(max(tmp_bytes, 256), dtype=torch.uint8, device=device)
         ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else C.c_void_p(0)
         out5[4] = -1
+        tab = table.ctypes.data_as(C.c_void_p)
+        stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
         with torch.cuda.device(device):
-            rc = lib.genie_reads_from_text(ptr(text), nbytes, N.TEXT_FORMATS[fmt], flags, table.ctypes.data_as(C.c_void_p),
-                                           ptr(bases), cap_bases, ptr(offsets), cap_reads, out5, ptr(tmp), tmp_bytes,
-                                           C.c_void_p(torch.cuda.current_stream(device).cuda_stream))
+            if fasta:
+                rc = lib.genie_reads_from_fasta(ptr(text), nbytes, flags, tab, ptr(bases), cap_bases, ptr(offsets), ptr(starts),
+                                                cap_reads, out5, ptr(tmp), tmp_bytes, stream)
+            else:
+                rc = lib.genie_reads_from_text(ptr(text), nbytes, N.TEXT_FORMATS[fmt], flags, tab, ptr(bases), cap_bases,
+                                               ptr(offsets), cap_reads, out5, ptr(tmp), tmp_bytes, stream)
         if rc == -1 and out5[4] >= 0:
             raise TextFormatError(out5[4], fmt)
-        N.check(rc, "genie_reads_from_text")
+        N.check(rc, name)
 
-    call(None, None, 0, 0)
+    call(None, None, None, 0, 0)
     n_reads, total = int(out5[0]), int(out5[1])
     bases = torch.empty(max(total, 1), dtype=torch.uint8, device=device)     # a pointer even for no bases
     offsets = torch.empty(n_reads + 1, dtype=torch.int64, device=device)
-    call(bases, offsets, total, n_reads)
+    starts = torch.empty(n_reads, dtype=torch.int64, device=device) if return_starts else None
+    call(bases, offsets, starts, total, n_reads)
+    if return_starts:
+        return bases[:total], offsets, int(out5[3]), starts
     return bases[:total], offsets, int(out5[3])
+
+
+def record_names(data, record_starts):
+    """The names of FASTA records, on the host: for each text position in record_starts (of a record's '>', as
+    reads_from_text(..., "fasta", return_starts=True) gives them) the bytes behind the '>' up to the first space, tab, '\\r'
+    or '\\n' (or the text's end).  data: the bytes-like text those positions refer to.  -> list[bytes]."""
+    text = data if isinstance(data, (bytes, bytearray)) else memoryview(data).cast("B")
+    if isinstance(record_starts, torch.Tensor):
+        record_starts = record_starts.cpu().tolist()
+    names = []
+    for at in record_starts:
+        at = int(at)
+        if not 0 <= at < len(text) or text[at] != 0x3E:
+            raise ValueError(f"no '>' at text position {at}")
+        names.append(bytes(_NAME.match(text, at + 1).group()))
+    return names
 
 
 def default_byte_codes():

@@ -363,8 +363,8 @@ int genie_find_smems_long_ex(const genie_index *ix, int32_t mode, int32_t flags,
  *   and start with '@', line 4r+2 non-empty and start with '+': otherwise GENIE_E_INVALID (found on the device) and out5[4] =
  *   the first such record.  Quality lines are not looked at (they may start with '@' and hold '+').  Without
  *   GENIE_TEXT_PARTIAL a number of lines that is no multiple of 4 is GENIE_E_INVALID with out5[4] = N, the incomplete record;
- *   with it the lines of an incomplete last record are not consumed.  Sequences wrapped over several lines, and FASTA, are
- *   NOT handled: every record is exactly four lines.
+ *   with it the lines of an incomplete last record are not consumed.  Sequences wrapped over several lines are NOT handled:
+ *   every record is exactly four lines (FASTA has an entry point of its own, genie_reads_from_fasta below).
  * Translation: an output byte is code_of_byte[b] where that is 0..3, else 4 (a break for GENIE_READS_SPLIT_BREAKS,
  *   GENIE_READ_BAD_BASE without it); never above 4.  Every byte value is legal inside a line except '\n'.  code_of_byte is a
  *   host array of 256 entries, read before the call returns (it travels as a kernel argument).
@@ -395,6 +395,37 @@ int genie_reads_from_text(const uint8_t *d_text, int64_t text_bytes, int32_t for
                           int64_t *d_read_offsets, int64_t cap_reads,
                           int64_t *out5 /* host */,
                           void *d_tmp, int64_t tmp_bytes, void *stream);
+
+/* Reads from FASTA text, on the device: '>' header lines, each followed by a sequence wrapped over any number of lines.
+ * Lines, the tail, GENIE_TEXT_PARTIAL and the translation through code_of_byte are those of genie_reads_from_text.
+ * A header line is a non-empty line whose first byte is '>'; every other line is a sequence line (there is no comment
+ *   syntax: a line that starts with ';' is a sequence line).  A '>' elsewhere in a line is an ordinary byte.
+ * Record r starts at the r-th header line and runs to just before the next header line or the end of the text.  Read r is
+ *   the bytes of its sequence lines, concatenated in order (each without its '\n' and the dropped '\r'; empty lines
+ *   contribute nothing); a record without sequence bytes is a read of length 0.
+ * With H header lines: without GENIE_TEXT_PARTIAL N = H and consumed_bytes = text_bytes.  With it the last record may go on
+ *   in the next chunk: N = max(H - 1, 0) and consumed_bytes = the text position of the last header line's '>' (0 when
+ *   H = 0); the bytes from there on are left alone, so that parsing text[consumed_bytes:] followed by the rest of the stream
+ *   continues exactly where this chunk stopped.
+ * Malformed: a non-empty line in front of the first header line (without GENIE_TEXT_PARTIAL the tail counts).  Then
+ *   GENIE_E_INVALID, found on the device, with out5[4] = 0; the outputs' contents are undefined, nothing outside the
+ *   capacities is written, and it is reported before a capacity.  Leading empty lines are fine; a text without any
+ *   non-empty line is N = 0 and GENIE_OK.
+ * Output: d_bases = the reads' codes back to back; d_read_offsets[0 .. N] their int64 offsets, [0] = 0;
+ *   d_record_starts[0 .. N) (may be NULL) the text position of every record's '>', for a caller that kept the text and
+ *   wants the names; out5 (host) = {N, total_bases, longest read, consumed_bytes, 0 when malformed else -1}.
+ * Sizing, capacities, argument checks and synchronisation are word for word those of genie_reads_from_text (the sizing call
+ *   has d_bases, d_read_offsets and d_record_starts all NULL; d_record_starts is 8-byte aligned like d_read_offsets and
+ *   holds cap_reads entries); the scratch is genie_reads_from_fasta_tmp_bytes(text_bytes, cap_reads), 48 bytes per 4096 of
+ *   text.  Three streaming passes over the text, nothing per record and nothing per line, no atomics: the output is a
+ *   function of the inputs alone. */
+int64_t genie_reads_from_fasta_tmp_bytes(int64_t text_bytes, int64_t cap_reads);
+int genie_reads_from_fasta(const uint8_t *d_text, int64_t text_bytes, int32_t flags,
+                           const uint8_t *code_of_byte /* host, 256 entries */,
+                           uint8_t *d_bases, int64_t cap_bases,
+                           int64_t *d_read_offsets, int64_t *d_record_starts /* may be NULL */, int64_t cap_reads,
+                           int64_t *out5 /* host */,
+                           void *d_tmp, int64_t tmp_bytes, void *stream);
 
 /* The same discovery for callers on the far side of a host link (SMEM.find_smems_* on host arrays): 2-bit packed reads in,
  * 8-byte rows out -- 40 instead of 150 bytes per 150-base read over PCIe, 8 instead of 16 per SMEM.  Reads of at most 255
