@@ -466,6 +466,33 @@ int genie_find_smems_long_ex(const genie_index *ix, int32_t mode, int32_t flags,
                                      out_cap_rows, d_status, d_workspace, workspace_bytes, stream);
 }
 
+int64_t genie_match_stats_workspace_bytes(int64_t N, int64_t total_bases, int64_t max_len, int32_t flags)
+{
+    if (N < 0 || total_bases < 0 || max_len < 0 || max_len > 0x7fffffffll) return (int64_t)GENIE_E_INVALID;
+    if (flags & ~(GENIE_READS_BOTH_STRANDS | GENIE_READS_SPLIT_BREAKS)) return (int64_t)GENIE_E_INVALID;
+    return match_stats_workspace_bytes(N, total_bases, flags);
+}
+
+int genie_match_stats(const genie_index *ix, int32_t flags, const uint8_t *d_bases, const int64_t *d_read_offsets, int64_t N,
+                      int64_t total_bases, int64_t max_len, int32_t *d_ms, int32_t *d_lohi, int32_t *d_status, void *d_workspace,
+                      int64_t workspace_bytes, void *stream)
+{
+    // argument checks first: they need no device image
+    if (!ix) return GENIE_E_INVALID;
+    if (N < 0 || total_bases < 0 || max_len < 0 || max_len > 0x7fffffffll || workspace_bytes < 0 || (N > 0 && !d_read_offsets) ||
+        (total_bases > 0 && (!d_bases || !d_ms)))
+        return GENIE_E_INVALID;
+    if (flags & ~(GENIE_READS_BOTH_STRANDS | GENIE_READS_SPLIT_BREAKS)) return GENIE_E_INVALID;
+    if ((reinterpret_cast<uintptr_t>(d_ms) & 3) != 0 || (reinterpret_cast<uintptr_t>(d_lohi) & 7) != 0) return GENIE_E_INVALID;
+    if (N > 0 && (!d_workspace || (reinterpret_cast<uintptr_t>(d_workspace) & 255) != 0 ||
+                  workspace_bytes < match_stats_workspace_bytes(N, total_bases, flags)))
+        return GENIE_E_CAPACITY;
+    int rc = ready(ix);
+    if (rc) return rc;
+    return launch_match_stats(ix, flags, d_bases, d_read_offsets, N, total_bases, max_len, d_ms, d_lohi, d_status, d_workspace,
+                              workspace_bytes, stream);
+}
+
 int64_t genie_reads_from_text_tmp_bytes(int64_t text_bytes, int64_t cap_reads)
 {
     if (text_bytes < 0 || cap_reads < 0) return (int64_t)GENIE_E_INVALID;

@@ -34,6 +34,12 @@
 //   LR5 lr_emit_kernel    one thread per window the chain enters: its SMEMs in order, the SA interval of each from
 //                         sa_interval over the packed unit (any length), each row written once, non-temporal, with the
 //                         unit's start inside its read added to start / end.
+// lr_match_stats launches LR1 and LR2 alone (lr_fwd_kernel<C16, true>: no maxima, no marks, and a window goes on where
+// another one has flagged its unit's absent base), then
+//   LRM lr_ms_kernel      one block per window, one lane per position: fwd[a] - a to the position's place in the caller's
+//                         array, and the SA interval of [a, fwd[a]) from the match-table entry of the position's P2-mer where
+//                         that decides (interval_from_entry, as K_C), else from sa_interval over the packed unit -- those
+//                         positions are gathered per block so that the search runs on full waves.
 namespace {
 
 constexpr int kLrWin = 256;               // positions per window (a multiple of 64: one per lane of LR3's block)
@@ -98,7 +104,9 @@ __global__ void __launch_bounds__(256) lr_pack_kernel(const uint8_t *__restrict_
     packed[g] = w;
 }
 
-template <bool C16>
+// MS (the match-statistics tail): fwd[] alone -- wmax and mark are not touched -- and only a bad base stops a window: fwd[]
+// of a unit with an absent base is still wanted, and another window of the unit may have flagged it already.
+template <bool C16, bool MS = false>
 __global__ void __launch_bounds__(kLrFwdWaves * 64) lr_fwd_kernel(DevIndex ix, int mode, const long long *__restrict__ off, long long N,
                                                                   long long nwin, const uint64_t *__restrict__ packed,
                                                                   int32_t *__restrict__ st, int32_t *__restrict__ fwd,
@@ -116,7 +124,7 @@ __global__ void __launch_bounds__(kLrFwdWaves * 64) lr_fwd_kernel(DevIndex ix, i
     const long long o = off[r], Ll = off[r + 1] - o;
     if (w < 0 || w * kLrWin >= Ll) return;                     // a window past the read's end (at most one per read)
     const int L = (int)Ll, w0 = (int)(w * kLrWin);
-    if (st[r] != GENIE_READ_OK) return;                         // bad base or too short (LR0 / LR1)
+    if (MS ? st[r] == GENIE_READ_BAD_BASE : st[r] != GENIE_READ_OK) return;      // bad base or too short (LR0 / LR1)
     const __amdgpu_buffer_rsrc_t mtab =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<MatchRec *>(ix.mtab), 0, (int)mtab_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t ov =
@@ -161,17 +169,19 @@ __global__ void __launch_bounds__(kLrFwdWaves * 64) lr_fwd_kernel(DevIndex ix, i
             const unsigned long long key = ((unsigned long long)(uint32_t)(v - a) << kLrWinShift) | (unsigned)(kLrWin - 1 - t);
             best = key > best ? key : best;
             absent = absent || v == a;
-            if (v < L) mark[o + v] = 1;                          // every writer stores the same value
+            if (!MS && v < L) mark[o + v] = 1;                   // every writer stores the same value
         }
     }
+    if (!MS) {
 #pragma unroll
-    for (int m = 32; m > 0; m >>= 1) {
-        const unsigned long long x = lr_shfl_xor64(best, m);
-        best = x > best ? x : best;
+        for (int m = 32; m > 0; m >>= 1) {
+            const unsigned long long x = lr_shfl_xor64(best, m);
+            best = x > best ? x : best;
+        }
     }
     const bool any_absent = __any(absent);
     if (lane == 0) {
-        wmax[gw] = make_int2((int)(best >> kLrWinShift), w0 + kLrWin - 1 - (int)(best & (kLrWin - 1)));
+        if (!MS) wmax[gw] = make_int2((int)(best >> kLrWinShift), w0 + kLrWin - 1 - (int)(best & (kLrWin - 1)));
         if (any_absent) st[r] = GENIE_READ_ABSENT_BASE;
     }
 }
@@ -299,6 +309,88 @@ __global__ void __launch_bounds__(256) lr_emit_kernel(DevIndex ix, int mode, int
     }
 }
 
+typedef int lr_i2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void lr_store_lohi(int2 *dst, int2 iv)
+{
+    __builtin_nontemporal_store(lr_i2{iv.x, iv.y}, reinterpret_cast<lr_i2 *>(dst));
+}
+
+// LRM.  uvirt[u]: the virtual position (long_units.inc) of unit u's first base, where the unit's values go in ms / lohi; null:
+// off[u].  lohi null: lengths only.  A unit with a bad base gets -1 and (-1, -1) everywhere.
+template <bool C16>
+__global__ void __launch_bounds__(kLrWin) lr_ms_kernel(DevIndex ix, const long long *__restrict__ off, long long N,
+                                                       const uint64_t *__restrict__ packed, const int32_t *__restrict__ st,
+                                                       const int32_t *__restrict__ fwd, const long long *__restrict__ uvirt,
+                                                       int32_t *__restrict__ ms, int2 *__restrict__ lohi)
+{
+    __shared__ int32_t slen[kLrWin];
+    __shared__ uint16_t slist[kLrWin];                           // the positions the entry does not decide
+    __shared__ int nlist;
+    const long long gw = blockIdx.x;
+    const long long r = lr_find(N, gw, [&](long long x) { return lr_wb(off, x); });
+    const long long w = gw - lr_wb(off, r);
+    const long long o = off[r], Ll = off[r + 1] - o;
+    if (w < 0 || w * kLrWin >= Ll) return;                     // block-uniform, as everything up to the first barrier
+    const int L = (int)Ll, w0 = (int)(w * kLrWin);
+    const int t = threadIdx.x, a = w0 + t, lane = t & (kWave - 1);
+    const bool in = a < L;
+    const long long v0 = (uvirt ? uvirt[r] : o) + w0;            // where the window's first position goes
+    const bool bad = st[r] == GENIE_READ_BAD_BASE;
+    const int len = in && !bad ? fwd[o + a] - a : -1;
+    if (in) __builtin_nontemporal_store(len, ms + v0 + t);
+    if (!lohi) return;
+    if (bad) {
+        if (in) lr_store_lohi(lohi + v0 + t, make_int2(-1, -1));
+        return;
+    }
+    if (t == 0) nlist = 0;
+    slen[t] = len;
+    __syncthreads();
+    const QPlain Q{packed + lr_wd(off, r)};
+    const int P2 = ix.P2;
+    const __amdgpu_buffer_rsrc_t ov =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<MatchOv16 *>(ix.ov), 0, ix.ov_entries * (int)sizeof(MatchOv16), 0x00020000);
+    const bool act = len > 0;
+    const uint64_t x = act ? Q.win(a) : 0ull;
+    const uint32_t c = (uint32_t)(x >> (64 - 2 * P2));
+    const int4 *en = C16 ? reinterpret_cast<const int4 *>(reinterpret_cast<const MatchRec16 *>(ix.mtab) + c)
+                         : reinterpret_cast<const int4 *>(ix.mtab + c);
+    int4 ra = make_int4(0, 0, 0, 0), rb = make_int4(0, 0, 0, 0);
+    if (act) { ra = en[0]; if (!C16) rb = en[1]; }
+    int2 iv;                                                     // (-1, -1) where the match is empty
+    const bool fast = interval_from_entry<C16>(ra, rb, x, len, P2, ov, act, iv);
+    if (in && (fast || !act)) lr_store_lohi(lohi + v0 + t, iv);
+    const bool general = act && !fast;
+    const unsigned long long gb = __ballot(general);
+    if (gb) {
+        const int first = __ffsll((long long)gb) - 1;
+        int at = 0;
+        if (lane == first) at = atomicAdd(&nlist, __popcll(gb));
+        at = __shfl(at, first, kWave);
+        if (general) slist[at + __popcll(gb & ((1ull << lane) - 1ull))] = (uint16_t)t;
+    }
+    __syncthreads();
+    if (t < nlist) {
+        const int g = slist[t];
+        const int2 v = sa_interval(ix, ix.dir, Q, w0 + g, slen[g]);
+        lr_store_lohi(lohi + v0 + g, v);
+    }
+}
+
+// The positions of the caller's arrays in front of the first read and behind the last one (the offsets need not begin at 0
+// nor end at total_bases): no match.
+__global__ void __launch_bounds__(256) lr_ms_edges_kernel(const long long *__restrict__ off, long long N, int S, long long positions,
+                                                          int32_t *__restrict__ ms, int2 *__restrict__ lohi)
+{
+    const long long lead = S * off[0], tail = S * off[N];
+    const long long n = lead + (positions - tail);
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const long long v = i < lead ? i : tail + (i - lead);
+        ms[v] = 0;
+        if (lohi) lohi[v] = make_int2(-1, -1);
+    }
+}
+
 struct LongArea {
     int *flag;
     int32_t *st, *cnt;
@@ -311,7 +403,8 @@ struct LongArea {
     long long total, nwords, nwin;
 };
 
-inline int64_t long_layout(uint8_t *p, int64_t N, int64_t total, LongArea *a)
+// smems false: the pieces LR1 and LR2 use (the match-statistics tail), the others empty
+inline int64_t long_layout(uint8_t *p, int64_t N, int64_t total, LongArea *a, bool smems = true)
 {
     a->total = total;
     a->nwords = total / 32 + 3 * N + 4;
@@ -319,16 +412,16 @@ inline int64_t long_layout(uint8_t *p, int64_t N, int64_t total, LongArea *a)
     Carver c{p};
     c.take(a->flag, 256);
     c.take(a->st, 4 * N);
-    c.take(a->cnt, 4 * N);
+    c.take(a->cnt, smems ? 4 * N : 0);
     c.take(a->sums, 8 * ((N + kScanBlock - 1) / kScanBlock + 1));
     c.take(a->packed, 8 * a->nwords);
     c.take(a->fwd, 4 * total);
-    c.take(a->bst, 4 * total);
-    c.take(a->jc, 8 * total);
-    c.take(a->mark, total);
-    c.take(a->wmax, 8 * a->nwin);
-    c.take(a->entry, 4 * a->nwin);
-    c.take(a->base, 4 * a->nwin);
+    c.take(a->bst, smems ? 4 * total : 0);
+    c.take(a->jc, smems ? 8 * total : 0);
+    c.take(a->mark, smems ? total : 0);
+    c.take(a->wmax, smems ? 8 * a->nwin : 0);
+    c.take(a->entry, smems ? 4 * a->nwin : 0);
+    c.take(a->base, smems ? 4 * a->nwin : 0);
     return c.at;
 }
 
@@ -354,6 +447,23 @@ int lr_pipeline(const genie_index *ix, int mode, int min_len, const uint8_t *d_b
     if (rc) return rc;
     LAUNCH(lr_emit_kernel, dim3((unsigned)((a.nwin + 255) / 256)), dim3(256), 0, s, ix->dev, mode, min_len, uoff, U, a.nwin, a.packed,
            a.fwd, a.bst, a.entry, a.base, reinterpret_cast<const long long *>(offsets), ushift, reinterpret_cast<int4 *>(d_rows), cap);
+    return GENIE_OK;
+}
+
+// LR1, LR2 and LRM over the U units of `uoff`: the matching statistics of every position of every unit to its place in
+// ms / lohi (lohi may be null), the units' statuses to a.st
+int lr_match_stats(const genie_index *ix, const uint8_t *d_bases, const LongArea &a, const long long *uoff, long long U,
+                   const long long *usrc, const long long *uvirt, int32_t *d_ms, int32_t *d_lohi, hipStream_t s)
+{
+    LAUNCH(lr_pack_kernel, dim3((unsigned)((a.nwords + 255) / 256)), dim3(256), 0, s, d_bases, uoff, U, usrc, a.nwords, a.packed, a.st);
+    const bool c16 = (ix->dev.flags & kFlagCompactTable) != 0;
+    const auto fwd_kernel = c16 ? lr_fwd_kernel<true, true> : lr_fwd_kernel<false, true>;
+    LAUNCH(fwd_kernel, dim3((unsigned)((a.nwin + kLrFwdWaves - 1) / kLrFwdWaves)), dim3(kLrFwdWaves * 64), 0, s, ix->dev,
+           (int)GENIE_MODE_BWA, uoff, U, a.nwin, static_cast<const uint64_t *>(a.packed), a.st, a.fwd, static_cast<int2 *>(nullptr),
+           static_cast<uint8_t *>(nullptr), table_bytes(ix));
+    const auto ms_kernel = c16 ? lr_ms_kernel<true> : lr_ms_kernel<false>;
+    LAUNCH(ms_kernel, dim3((unsigned)a.nwin), dim3(kLrWin), 0, s, ix->dev, uoff, U, static_cast<const uint64_t *>(a.packed),
+           static_cast<const int32_t *>(a.st), static_cast<const int32_t *>(a.fwd), uvirt, d_ms, reinterpret_cast<int2 *>(d_lohi));
     return GENIE_OK;
 }
 

@@ -1,5 +1,6 @@
-// long_units.inc -- genie_find_smems_long and genie_find_smems_long_ex: how the units of long_reads.inc's pipeline are made
-// from reads, strands and breaks, and the entry point (included by kernels.hip behind long_reads.inc, inside namespace genie).
+// long_units.inc -- genie_find_smems_long, genie_find_smems_long_ex and genie_match_stats: how the units of long_reads.inc's
+// pipelines are made from reads, strands and breaks, and the entry points (included by kernels.hip behind long_reads.inc,
+// inside namespace genie).
 //
 // A unit is one strand of one segment of one read.  Strands and breaks are a property of the pack stage (usrc) and of
 // where the rows land (ushift, the caller's offsets); everything between works on units alone.
@@ -27,6 +28,8 @@
 //   lr_pipeline               over (uoff, C) with usrc and ushift, its rows behind those of the passes before
 //   LU4 lu_offsets_kernel     a strand-read's offset is its first unit's (units of a strand-read are consecutive)
 //   Between passes the host reads the pass's row total (one synchronisation per extra pass).
+// genie_match_stats shares all of this up to the units of a pass (lu_run); in place of lr_pipeline and LU4 it runs
+// lr_match_stats, which writes every position's values at its virtual position: ua[] of a segment, the offset of a strand-read.
 namespace {
 
 constexpr int kLuChunk = 16384;           // virtual positions per block of LU1 / LU2 ...
@@ -287,16 +290,17 @@ struct LongExPass {
     long long *uoff, *loff;          // C + 1 each: unit offsets, the pass's row offsets
 };
 
-inline int64_t long_ex_pass_layout(uint8_t *p, int64_t C, int64_t total, int S, bool split, LongExPass *a)
+// smems false: the layout of the match-statistics tail (no rows: the pieces of LR3 .. LR5 and the row offsets are empty)
+inline int64_t long_ex_pass_layout(uint8_t *p, int64_t C, int64_t total, int S, bool split, LongExPass *a, bool smems = true)
 {
     const bool table = S == 2 || split;
-    Carver c{p, long_layout(p, C, S * total, &a->lr)};
+    Carver c{p, long_layout(p, C, S * total, &a->lr, smems)};
     c.take(a->ua, split ? 8 * C : 0);
     c.take(a->ub, table ? 8 * C : 0);
     c.take(a->ulen, split ? 4 * C : 0);
     c.take(a->ushift, split ? 4 * C : 0);
     c.take(a->uoff, table ? 8 * (C + 1) : 0);
-    c.take(a->loff, split ? 8 * (C + 1) : 0);
+    c.take(a->loff, split && smems ? 8 * (C + 1) : 0);
     return c.at;
 }
 
@@ -307,27 +311,37 @@ inline int64_t long_ex_units(int64_t N, int64_t total, int S, bool split)
     return (S == 2 || split ? std::max<int64_t>(1, S * N) : N) + (split ? S * total / kLuSpare : 0);
 }
 
-}  // namespace
-
-int64_t find_smems_long_ex_workspace_bytes(int64_t N, int64_t total_bases, int32_t flags)
+inline int64_t long_ex_bytes(int64_t N, int64_t total_bases, int32_t flags, bool smems)
 {
     const int S = (flags & GENIE_READS_BOTH_STRANDS) ? 2 : 1;
     const bool split = (flags & GENIE_READS_SPLIT_BREAKS) != 0;
     LongExFixed f;
     LongExPass a;
     return long_ex_fixed_layout(nullptr, N, total_bases, S, split, &f) +
-           long_ex_pass_layout(nullptr, long_ex_units(N, total_bases, S, split), total_bases, S, split, &a);
+           long_ex_pass_layout(nullptr, long_ex_units(N, total_bases, S, split), total_bases, S, split, &a, smems);
 }
 
-int launch_find_smems_long_ex(const genie_index *ix, int32_t mode, int32_t flags, const uint8_t *d_bases, const int64_t *d_read_offsets,
-                              int64_t N, int64_t total_bases, int64_t max_len, int32_t min_len, int64_t *d_offsets, int32_t *d_rows,
-                              int64_t out_cap_rows, int32_t *d_status, void *d_ws, int64_t ws_bytes, void *stream)
+// One pass of at most C units, as the front hands it to a tail
+struct LuPass {
+    const LuReads &R;
+    const LongExFixed &f;
+    const LongExPass &a;
+    long long U, p0, p1;             // units of the call; the pass holds the units [p0, p1)
+};
+
+// The front that genie_find_smems_long_ex and genie_match_stats share: everything up to "the units of this pass exist" (LU0,
+// the strand-read table, LU1 .. LU3, the passes).  What is done with the units is the TAIL's:
+//   tail.kSmems                      which workspace layout the call has
+//   tail.empty()                     N == 0
+//   tail.whole(lr, uoff, usrc)       the units are the S N strand-reads (no SPLIT_BREAKS, or no break found); their statuses
+//                                    are in lr.st
+//   tail.broken(U)                   breaks exist and cut the strand-reads into U units (U may be 0): once, before the passes
+//   tail.pass(p)                     the units [p0, p1): table in p.a (ua virtual begin, ub source key, ushift, uoff), p.a.lr.st zeroed
+template <class Tail>
+int lu_run(const genie_index *ix, int32_t mode, int32_t flags, const uint8_t *d_bases, const int64_t *d_read_offsets, int64_t N,
+           int64_t total_bases, int64_t max_len, void *d_ws, int64_t ws_bytes, hipStream_t s, Tail &tail)
 {
-    hipStream_t s = (hipStream_t)stream;
-    if (N == 0) {
-        HIP_TRY(hipMemsetAsync(d_offsets, 0, 8, s));
-        return GENIE_OK;
-    }
+    if (N == 0) return tail.empty();
     const int S = (flags & GENIE_READS_BOTH_STRANDS) ? 2 : 1;
     const bool split = (flags & GENIE_READS_SPLIT_BREAKS) != 0;
     const long long SN = (long long)S * N;
@@ -337,15 +351,9 @@ int launch_find_smems_long_ex(const genie_index *ix, int32_t mode, int32_t flags
     uint8_t *pass = static_cast<uint8_t *>(d_ws) + fixed;
     // The strand-reads as units.  On one strand the caller's offsets are the unit offsets and there is no table.
     LongExPass whole;
-    long_ex_pass_layout(pass, SN, total_bases, S, false, &whole);
+    long_ex_pass_layout(pass, SN, total_bases, S, false, &whole, Tail::kSmems);
     int *const flag = whole.lr.flag;
     long long *const tsrc = S == 2 ? whole.ub : nullptr, *const toff = S == 2 ? whole.uoff : nullptr;
-    auto strand_reads = [&]() -> int {
-        int rc = lr_pipeline(ix, mode, min_len, d_bases, whole.lr, toff ? toff : off, SN, tsrc, nullptr, d_offsets, d_rows, out_cap_rows, s);
-        if (rc) return rc;
-        if (d_status) HIP_TRY(hipMemcpyAsync(d_status, whole.lr.st, SN * 4, hipMemcpyDeviceToDevice, s));
-        return GENIE_OK;
-    };
     HIP_TRY(hipMemsetAsync(flag, 0, 8, s));
     LAUNCH(lu_check_kernel, dim3((unsigned)((N + 1 + 255) / 256)), dim3(256), 0, s, off, (long long)N, (long long)total_bases,
            (long long)max_len, mode, ix->dev.K, S, flag, whole.lr.st, tsrc, toff);
@@ -353,7 +361,7 @@ int launch_find_smems_long_ex(const genie_index *ix, int32_t mode, int32_t flags
     HIP_TRY(hipMemcpyAsync(&bad, flag, 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     if (bad) return GENIE_E_INVALID;
-    if (!split) return strand_reads();
+    if (!split) return tail.whole(whole.lr, toff ? toff : off, tsrc);
 
     const LuReads R{d_bases, off, (long long)N, S};
     int *anybreak = flag + 1;
@@ -367,35 +375,72 @@ int launch_find_smems_long_ex(const genie_index *ix, int32_t mode, int32_t flags
     HIP_TRY(hipMemcpyAsync(&units, f.bsum + f.nblk, 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(&breaks, anybreak, 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    if (!breaks) return strand_reads();                          // every status is GENIE_READ_OK: BWA mode, no bad or absent base
-    if (d_status) HIP_TRY(hipMemsetAsync(d_status, 0, SN * 4, s));
+    if (!breaks) return tail.whole(whole.lr, toff ? toff : off, tsrc);      // every status is GENIE_READ_OK: BWA mode, no bad or absent base
     const long long U = (long long)units;
-    if (U == 0) {
-        HIP_TRY(hipMemsetAsync(d_offsets, 0, (SN + 1) * 8, s));
-        return GENIE_OK;
-    }
+    int rc = tail.broken(U);
+    if (rc || U == 0) return rc;
     LongExPass a;
     // units per pass: as many as the workspace holds (at least S N: the caller sized it for that many)
     const long long C = pass_size(std::max<long long>(SN, 1), U, [&](long long c) {
-        return long_ex_pass_layout(nullptr, c, total_bases, S, true, &a) <= ws_bytes - fixed;
+        return long_ex_pass_layout(nullptr, c, total_bases, S, true, &a, Tail::kSmems) <= ws_bytes - fixed;
     });
-    long_ex_pass_layout(pass, C, total_bases, S, true, &a);
-    long long row0 = 0;
+    long_ex_pass_layout(pass, C, total_bases, S, true, &a, Tail::kSmems);
     for (long long p0 = 0; p0 < U; p0 += C) {
         const long long p1 = std::min(U, p0 + C), Cp = p1 - p0;
-        const bool last = p1 == U;
         HIP_TRY(hipMemsetAsync(a.lr.st, 0, Cp * 4, s));           // GENIE_READ_OK: a unit holds no break
         LAUNCH(lu_seg_kernel<true>, dim3((unsigned)f.nblk), dim3(256), 0, s, ix->dev, R, f.bsum, f.qloc, anybreak, p0, p1, a.ua, a.ub);
         LAUNCH(lu_units_kernel, dim3((unsigned)((Cp + 255) / 256)), dim3(256), 0, s, R, Cp, static_cast<const long long *>(a.ua), a.ub,
                a.ulen, a.ushift);
-        int rc = launch_compact(a.ulen, nullptr, Cp, 0x7fffffff, reinterpret_cast<int64_t *>(a.uoff), nullptr, 0, a.lr.sums, stream);
+        rc = launch_compact(a.ulen, nullptr, Cp, 0x7fffffff, reinterpret_cast<int64_t *>(a.uoff), nullptr, 0, a.lr.sums, s);
         if (rc) return rc;
+        if ((rc = tail.pass(LuPass{R, f, a, U, p0, p1}))) return rc;
+    }
+    return GENIE_OK;
+}
+
+// The SMEM tail: lr_pipeline over the units, then LU4.  Between passes the host reads the pass's row total.
+struct LuSmemTail {
+    static constexpr bool kSmems = true;
+    const genie_index *ix;
+    int32_t mode, min_len;
+    const uint8_t *d_bases;
+    long long SN;
+    int64_t *d_offsets;
+    int32_t *d_rows;
+    int64_t out_cap_rows;
+    int32_t *d_status;
+    hipStream_t s;
+    long long row0 = 0;              // rows of the passes before
+
+    int empty()
+    {
+        HIP_TRY(hipMemsetAsync(d_offsets, 0, 8, s));
+        return GENIE_OK;
+    }
+    int whole(const LongArea &lr, const long long *uoff, const long long *usrc)
+    {
+        int rc = lr_pipeline(ix, mode, min_len, d_bases, lr, uoff, SN, usrc, nullptr, d_offsets, d_rows, out_cap_rows, s);
+        if (rc) return rc;
+        if (d_status) HIP_TRY(hipMemcpyAsync(d_status, lr.st, SN * 4, hipMemcpyDeviceToDevice, s));
+        return GENIE_OK;
+    }
+    int broken(long long U)
+    {
+        if (d_status) HIP_TRY(hipMemsetAsync(d_status, 0, SN * 4, s));
+        if (U == 0) HIP_TRY(hipMemsetAsync(d_offsets, 0, (SN + 1) * 8, s));
+        return GENIE_OK;
+    }
+    int pass(const LuPass &p)
+    {
+        const LongExPass &a = p.a;
+        const long long Cp = p.p1 - p.p0;
+        const bool last = p.p1 == p.U;
         const long long cap_left = std::max(0ll, (long long)out_cap_rows - row0);
-        rc = lr_pipeline(ix, mode, min_len, d_bases, a.lr, a.uoff, Cp, a.ub, a.ushift, reinterpret_cast<int64_t *>(a.loff),
-                         cap_left > 0 ? d_rows + 4 * row0 : d_rows, cap_left, s);
+        int rc = lr_pipeline(ix, mode, min_len, d_bases, a.lr, a.uoff, Cp, a.ub, a.ushift, reinterpret_cast<int64_t *>(a.loff),
+                             cap_left > 0 ? d_rows + 4 * row0 : d_rows, cap_left, s);
         if (rc) return rc;
-        LAUNCH(lu_offsets_kernel, dim3((unsigned)((SN + 1 + 255) / 256)), dim3(256), 0, s, R, static_cast<const unsigned long long *>(f.bsum),
-               static_cast<const int32_t *>(f.qloc), U, p0, p1, last, static_cast<const long long *>(a.loff), row0,
+        LAUNCH(lu_offsets_kernel, dim3((unsigned)((SN + 1 + 255) / 256)), dim3(256), 0, s, p.R, static_cast<const unsigned long long *>(p.f.bsum),
+               static_cast<const int32_t *>(p.f.qloc), p.U, p.p0, p.p1, last, static_cast<const long long *>(a.loff), row0,
                reinterpret_cast<long long *>(d_offsets));
         if (!last) {
             long long pass_rows = 0;
@@ -403,6 +448,75 @@ int launch_find_smems_long_ex(const genie_index *ix, int32_t mode, int32_t flags
             HIP_TRY(hipStreamSynchronize(s));
             row0 += pass_rows;
         }
+        return GENIE_OK;
     }
-    return GENIE_OK;
+};
+
+// The match-statistics tail: lr_match_stats over the units.  Positions that no unit covers (breaks; what lies in front of the
+// first read and behind the last) are filled beforehand; nothing is read back between passes.
+struct LuMsTail {
+    static constexpr bool kSmems = false;
+    const genie_index *ix;
+    const uint8_t *d_bases;
+    const long long *off;
+    long long N;
+    int S;
+    long long positions;             // S total_bases
+    int32_t *d_ms, *d_lohi, *d_status;
+    hipStream_t s;
+
+    int fill()                       // no match anywhere
+    {
+        if (positions > 0) HIP_TRY(hipMemsetAsync(d_ms, 0, positions * 4, s));
+        if (positions > 0 && d_lohi) HIP_TRY(hipMemsetAsync(d_lohi, 0xFF, positions * 8, s));
+        return GENIE_OK;
+    }
+    int empty() { return fill(); }
+    int whole(const LongArea &lr, const long long *uoff, const long long *usrc)
+    {
+        LAUNCH(lr_ms_edges_kernel, dim3(64), dim3(256), 0, s, off, N, S, positions, d_ms, reinterpret_cast<int2 *>(d_lohi));
+        int rc = lr_match_stats(ix, d_bases, lr, uoff, S * N, usrc, nullptr, d_ms, d_lohi, s);       // a strand-read's offset is its virtual position
+        if (rc) return rc;
+        if (d_status) HIP_TRY(hipMemcpyAsync(d_status, lr.st, S * N * 4, hipMemcpyDeviceToDevice, s));
+        return GENIE_OK;
+    }
+    int broken(long long)
+    {
+        if (d_status) HIP_TRY(hipMemsetAsync(d_status, 0, S * N * 4, s));
+        return fill();
+    }
+    int pass(const LuPass &p) { return lr_match_stats(ix, d_bases, p.a.lr, p.a.uoff, p.p1 - p.p0, p.a.ub, p.a.ua, d_ms, d_lohi, s); }
+};
+
+}  // namespace
+
+int64_t find_smems_long_ex_workspace_bytes(int64_t N, int64_t total_bases, int32_t flags)
+{
+    return long_ex_bytes(N, total_bases, flags, true);
+}
+
+int launch_find_smems_long_ex(const genie_index *ix, int32_t mode, int32_t flags, const uint8_t *d_bases, const int64_t *d_read_offsets,
+                              int64_t N, int64_t total_bases, int64_t max_len, int32_t min_len, int64_t *d_offsets, int32_t *d_rows,
+                              int64_t out_cap_rows, int32_t *d_status, void *d_ws, int64_t ws_bytes, void *stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    const int S = (flags & GENIE_READS_BOTH_STRANDS) ? 2 : 1;
+    LuSmemTail tail{ix, mode, min_len, d_bases, (long long)S * N, d_offsets, d_rows, out_cap_rows, d_status, s};
+    return lu_run(ix, mode, flags, d_bases, d_read_offsets, N, total_bases, max_len, d_ws, ws_bytes, s, tail);
+}
+
+int64_t match_stats_workspace_bytes(int64_t N, int64_t total_bases, int32_t flags)
+{
+    return long_ex_bytes(N, total_bases, flags, false);
+}
+
+int launch_match_stats(const genie_index *ix, int32_t flags, const uint8_t *d_bases, const int64_t *d_read_offsets, int64_t N,
+                       int64_t total_bases, int64_t max_len, int32_t *d_ms, int32_t *d_lohi, int32_t *d_status, void *d_ws,
+                       int64_t ws_bytes, void *stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    const int S = (flags & GENIE_READS_BOTH_STRANDS) ? 2 : 1;
+    LuMsTail tail{ix, d_bases, reinterpret_cast<const long long *>(d_read_offsets), (long long)N, S, (long long)S * total_bases,
+                  d_ms, d_lohi, d_status, s};
+    return lu_run(ix, GENIE_MODE_BWA, flags, d_bases, d_read_offsets, N, total_bases, max_len, d_ws, ws_bytes, s, tail);
 }

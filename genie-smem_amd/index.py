@@ -429,6 +429,32 @@ class GenieIndex:
                              strands * n_reads, int(rows_hint) if rows_hint else strands * max(8 * n_reads, total // 6),
                              (_ptr(ws), ws_bytes))
 
+    def match_stats(self, bases, read_offsets, intervals=True, both_strands=False, split_breaks=False):
+        """Matching statistics of every position of every read (genie_match_stats) -> (ms int32[S*total], lohi
+        int32[S*total, 2] or None, status int32[S*N]) on the device, S = 2 with both_strands, else 1.  bases / read_offsets
+        as find_smems_long.  Position p of strand-read S*i + s is element S*read_offsets[i] + s*L_i + p: ms = the length of the
+        longest match that starts there (0: none; -1 throughout a strand-read flagged READ_BAD_BASE), lohi its inclusive
+        suffix-array interval ((-1, -1) where there is none; not computed with intervals=False).  With split_breaks codes
+        > 3 and bases the reference lacks are breaks that no match covers, and every status is READ_OK."""
+        self._need_device()
+        bases = self._as_dev(bases, torch.uint8).reshape(-1)
+        read_offsets = self._as_dev(read_offsets, torch.int64).reshape(-1)
+        if read_offsets.numel() < 1:
+            raise ValueError("read_offsets needs N + 1 entries")
+        n_reads = read_offsets.numel() - 1
+        total = bases.numel()
+        max_len = int((read_offsets[1:] - read_offsets[:-1]).max().item()) if n_reads else 0
+        max_len = min(max(max_len, 0), 2**31 - 1)
+        flags = (N.READS_BOTH_STRANDS if both_strands else 0) | (N.READS_SPLIT_BREAKS if split_breaks else 0)
+        strands = 2 if both_strands else 1
+        ms = torch.empty(strands * total, dtype=torch.int32, device=self.device)
+        lohi = torch.empty((strands * total, 2), dtype=torch.int32, device=self.device) if intervals else None
+        status = torch.empty(strands * n_reads, dtype=torch.int32, device=self.device)
+        ws, ws_bytes = self._workspace("genie_match_stats_workspace_bytes", n_reads, total, max_len, flags)
+        self._run("genie_match_stats", flags, _ptr(bases), _ptr(read_offsets), n_reads, total, max_len, _ptr(ms), _ptr(lohi),
+                  _ptr(status), _ptr(ws), ws_bytes)
+        return ms, lohi, status
+
     def find_smems_packed(self, mode, packed, max_len, lens=None, min_len=1, rows_hint=None, row_bytes=8):
         """genie_find_smems_packed (or, `row_bytes` = 6, genie_find_smems_packed6): 2-bit packed reads (packing.pack_reads;
         uint8 [N, stride] on the device) -> (counts8 uint8[N], status8 uint8[N], rows uint8[S, row_bytes], escapes int64[E, 2]);

@@ -143,6 +143,31 @@ class SMEM:
         res = ix.find_smems_long(mode, bases, read_offsets, minimum_length, both_strands=both_strands, split_breaks=split_breaks)
         return res + (read_offsets.numel() - 1, consumed)
 
+    def match_stats(self, reads, intervals=True, both_strands=False, split_breaks=False):
+        """Matching statistics of every position of every read (genie_match_stats): the batched forward_extension.  reads:
+        list[str], or (bases, read_offsets) as find_smems_long takes them.  -> (ms int32[S*total], lohi int32[S*total, 2] or
+        None with intervals=False, status int32[S*N]) on the device: position p of strand-read S*i + s is element
+        S*read_offsets[i] + s*L_i + p, ms the length of the longest match that starts there and lohi its interval, so that
+        forward_extension(q, p)[1] == q[p:p + ms] and its interval is lohi.  split_breaks: breaks are covered by no match
+        and flag no read; strings are then encoded with ExactMatch.encode_lenient."""
+        ix = self.matcher.index(self.lut.lut_size)
+        if isinstance(reads, tuple):
+            bases, read_offsets = reads
+        else:
+            encode = self.matcher.encode_lenient if split_breaks else self.matcher.encode
+            enc = [encode(r) for r in reads]
+            read_offsets = np.zeros(len(enc) + 1, np.int64)
+            read_offsets[1:] = np.cumsum([len(e) for e in enc]) if enc else []
+            bases = np.concatenate(enc).astype(np.uint8) if enc else np.zeros(0, np.uint8)
+        return ix.match_stats(bases, read_offsets, intervals, both_strands, split_breaks)
+
+    def match_stats_text(self, data, fmt="lines", intervals=True, both_strands=False, split_breaks=True, fold_case=False):
+        """match_stats of the reads in a text (find_smems_text's formats and translation) -> (ms, lohi, status,
+        read_offsets): read_offsets int64[N+1] on the device, to index the flat arrays with."""
+        ix = self.matcher.index(self.lut.lut_size)
+        bases, read_offsets, _ = reads_from_text(data, fmt, self.matcher.byte_codes(fold_case), False, ix.device)
+        return ix.match_stats(bases, read_offsets, intervals, both_strands, split_breaks) + (read_offsets,)
+
     def iter_text_smems(self, path, fmt, chunk_bytes=64 << 20, mode="bwa", minimum_length=1, both_strands=False, split_breaks=True,
                         fold_case=False):
         """find_smems_text over a file of any size, a chunk at a time: yields (offsets, smems, status) of the reads (records)

@@ -352,6 +352,48 @@ int genie_find_smems_long_ex(const genie_index *ix, int32_t mode, int32_t flags,
                              int32_t min_len, int64_t *d_offsets, int32_t *d_rows, int64_t out_cap_rows,
                              int32_t *d_status, void *d_workspace, int64_t workspace_bytes, void *stream);
 
+/* Matching statistics of EVERY position of every read: how far the longest match that starts there reaches, and its
+ * suffix-array interval -- the batched form of SMEM.forward_extension (SMEM.py:425-443), and the quantity every SMEM
+ * call derives its rows from.  Inputs as genie_find_smems_long_ex (CSR reads of any length, total_bases / max_len as
+ * host-side bounds, the same offset check on the device); `flags` ORs GENIE_READS_BOTH_STRANDS and
+ * GENIE_READS_SPLIT_BREAKS with the meanings they have there; S = 2 with BOTH_STRANDS, else 1.  There is no mode: the BWA
+ * traversal's input checks apply, so no read is GENIE_READ_TOO_SHORT.
+ * Layout: the virtual positions of the strand-reads back to back.  Position p of strand-read S i + s (read i of L_i bases
+ * at d_read_offsets[i] = o_i, strand s) is element v = S o_i + s L_i + p: on one strand d_ms lies parallel to d_bases.
+ * Strand 1 is the reverse complement and p a position in it, as for rows.
+ *   d_ms[v]    (S total_bases int32) the largest l >= 0 such that the l bases of the strand-read from p on hold no break
+ *              and occur in the reference.  A break is a code > 3; with SPLIT_BREAKS also a base the reference lacks
+ *              (without it such a base has l = 0 all the same: it occurs nowhere).
+ *   d_lohi[2v], d_lohi[2v + 1]  (2 S total_bases int32, may be NULL: lengths only) the inclusive suffix-array interval of
+ *              that match, what genie_sa_interval returns for it; (-1, -1) where l == 0.
+ *   d_status[S i + s]  (S N int32, may be NULL) without SPLIT_BREAKS: GENIE_READ_BAD_BASE for a strand-read that holds a code
+ *              > 3 -- all its d_ms are then -1 and all its d_lohi (-1, -1) --, GENIE_READ_ABSENT_BASE for one that holds a
+ *              base the reference lacks, whose values are written and correct all the same; else GENIE_READ_OK.  With
+ *              SPLIT_BREAKS every status is GENIE_READ_OK.
+ * After the call every element of the three arrays is defined: break positions hold 0 and (-1, -1), and so do the
+ * elements in front of S d_read_offsets[0] and from S d_read_offsets[N] on, which belong to no read.  Nothing outside the
+ * declared sizes is written.  N = 0 and total_bases = 0 are fine.  ms[v + 1] >= ms[v] - 1 inside a strand-read.
+ * Defining property, byte for byte: with BOTH_STRANDS the three outputs are those of the call without it on the explicit
+ * batch [r0, rc(r0), r1, rc(r1), ...].
+ * Checked before the device check, so on any handle: a null ix, d_read_offsets (N > 0), d_bases or d_ms (total_bases >
+ * 0), a negative size, max_len above 2^31 - 1, an unknown flag bit, d_ms not 4-byte or d_lohi not 8-byte aligned give
+ * GENIE_E_INVALID; then, for N > 0, a d_workspace that is null, not 256-byte aligned or smaller than
+ * genie_match_stats_workspace_bytes(N, total_bases, max_len, flags) gives GENIE_E_CAPACITY.  Bad offsets give
+ * GENIE_E_INVALID, found on the device.  The workspace function returns GENIE_E_INVALID for arguments the call would
+ * refuse; it never exceeds genie_find_smems_long_ex_workspace_bytes of the same arguments (two of that pipeline's five
+ * stages run: about 4.3 S bytes per base and 28 per read, 44 S with both strands; with SPLIT_BREAKS 6.1 S and 64 S).
+ * Synchronisations of `stream`: one, after the offset check; with SPLIT_BREAKS one more to read the number of units.
+ * Extra unit passes (units outnumbering what the workspace holds) cost none: no row count has to reach the host.
+ * Cost: the interval of a match of l bases that lies inside a repeat of the reference takes a suffix-array search whose
+ * probes compare up to l bases each; a read that follows a tandem repeat pays that at every one of its positions. */
+int64_t genie_match_stats_workspace_bytes(int64_t N, int64_t total_bases, int64_t max_len, int32_t flags);
+int genie_match_stats(const genie_index *ix, int32_t flags, const uint8_t *d_bases, const int64_t *d_read_offsets,
+                      int64_t N, int64_t total_bases, int64_t max_len,
+                      int32_t *d_ms,        /* S * total_bases */
+                      int32_t *d_lohi,      /* 2 * S * total_bases, may be NULL */
+                      int32_t *d_status,    /* S * N, may be NULL */
+                      void *d_workspace, int64_t workspace_bytes, void *stream);
+
 /* Reads from TEXT, on the device: the bytes of a file of reads -> the d_bases / d_read_offsets that genie_find_smems_long_ex
  * takes.  The reference has no counterpart (its reads are Python strings); this replaces encoding every string on the host.
  * Lines.  A line ends at a '\n' (0x0A), which is not part of it; if the line is then not empty and its last byte is '\r',
