@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import contract_calls as CC
+import match_stats_util as MS
 from guarded import Arena
 
 pytestmark = pytest.mark.gpu
@@ -64,6 +65,17 @@ def _steps(env, L, n, seed):
     return steps
 
 
+def _broken_reads(env, L, n, seed):
+    """n reads of K .. L bases cut from the reference (one of L bases, one empty), one position in a hundred a break."""
+    from genie_smem_amd import synth
+    rng = np.random.default_rng(seed)
+    mat = synth.reads_from_ref_fast(env.codes, n, L, seed).copy()
+    mat[rng.random(mat.shape) < 0.01] = 4
+    lens = rng.integers(K, L + 1, n)
+    lens[0], lens[1] = L, 0
+    return [mat[i, :lens[i]] for i in range(n)]
+
+
 def _alone(step):
     """The result of one step on the default stream, nothing else running."""
     import torch
@@ -79,14 +91,17 @@ def _alone(step):
 
 
 def test_explicit_stream(env):
-    """genie_find_smems_csr, _both, _split, _long_ex and genie_locate on a stream of their own: the results of the
-    default-stream run.  (Nothing waits for the call but a synchronisation of that stream.)"""
+    """genie_find_smems_csr, _both, _split, _long_ex, genie_locate and genie_match_stats (both strands, breaks, bases in front
+    of the first read and behind the last one, so that the kernel that fills those edges runs too) on a stream of their own:
+    the results of the default-stream run.  (Nothing waits for the call but a synchronisation of that stream.)"""
     import torch
     steps = [s for s in _steps(env, 150, 300, 1) + _steps(env, 1000, 24, 2) if s[0] in ("csr bwa", "both lut", "split", "long_ex both+split")]
     rows = _alone(steps[0])["rows"]
     lohi = np.ascontiguousarray(rows[:, 2:4])
     total = int((lohi[:, 1] - lohi[:, 0] + 1).sum())
     steps.append(("locate", lambda a, s: CC.locate(env.lib, env.ix, a, s, lohi, total), False))
+    steps.append(("match_stats both+split", lambda a, s: MS.guarded_call(env.lib, env.ix, a, s, MS.BOTH | MS.SPLIT, _broken_reads(env, 150, 300, 3),
+                                                                         lead=37, tail=5), True))
     stream = torch.cuda.Stream()
     assert stream.cuda_stream != torch.cuda.current_stream().cuda_stream
     for step in steps:
