@@ -881,6 +881,21 @@ int launch_match_table(Kernel km, const Geometry &g, hipStream_t s, Args... args
     return GENIE_OK;
 }
 
+// The K_C instance of a call: the rows kernel by table form and row format (four int32, or the 8- and 6-byte rows of the packed
+// calls), the 16-lane kernel by output form, read width and table form (its CSR rows are long reads').
+inline auto pick_interval_rows(bool c16, bool packed, int row_bytes) -> decltype(&interval_rows_kernel<true, 0>)
+{
+    if (!packed) return c16 ? interval_rows_kernel<true, 0> : interval_rows_kernel<false, 0>;
+    if (row_bytes == 6) return c16 ? interval_rows_kernel<true, 2> : interval_rows_kernel<false, 2>;
+    return c16 ? interval_rows_kernel<true, 1> : interval_rows_kernel<false, 1>;
+}
+inline auto pick_interval(bool csr, bool wide, bool c16) -> decltype(&interval_kernel<false, false, true>)
+{
+    if (csr) return c16 ? interval_kernel<true, true, true> : interval_kernel<true, true, false>;
+    if (wide) return c16 ? interval_kernel<false, true, true> : interval_kernel<false, true, false>;
+    return c16 ? interval_kernel<false, false, true> : interval_kernel<false, false, false>;
+}
+
 template <int MODE, bool WIDE>
 int launch_pipeline(const genie_index *ix, const Geometry &g, const FindRequest &r, const Workspace &ws, hipStream_t s)
 {
@@ -950,45 +965,38 @@ int launch_pipeline(const genie_index *ix, const Geometry &g, const FindRequest 
     while ((1 << block_shift) < reads_per_block) block_shift++;
     if (r.offsets)                           // scan of the traversal blocks' sums; K_C adds the in-block part
         LAUNCH(scan_block_sums_kernel, dim3(1), dim3(kScanBlock), 0, s, bsums, (N + reads_per_block - 1) / reads_per_block);
-    RowEscapes esc{nullptr, nullptr, 0};
     const int sched_c = ((ix->opt_scheduling >> 2) & 1) | cus << 8;  // bit 0: no priority rotation; bits 8..: CUs (blocks per round)
-    if (r.packed) {
-        esc.count = reinterpret_cast<unsigned long long *>(r.offsets) + 1;
-        esc.list = reinterpret_cast<long long *>(r.escapes);
-        esc.cap = r.cap_escapes;
-        HIP_TRY(hipMemsetAsync(r.offsets, 0, 16, s));
-    }
+    if (r.packed) HIP_TRY(hipMemsetAsync(r.offsets, 0, 16, s));      // the two totals: rows, escapes
     if (!WIDE && r.offsets) {
         // K_C, short reads, CSR rows: one lane per row over tiles of reads staged in LDS, persistent blocks -- as many per CU as
         // their LDS allows, four (eight waves per SIMD) up to 150 bases
+        RowEscapes esc{nullptr, nullptr, 0};
+        if (r.packed) esc = RowEscapes{reinterpret_cast<unsigned long long *>(r.offsets) + 1, reinterpret_cast<long long *>(r.escapes), r.cap_escapes};
         const int lds_c = kIvTile * g.qp_stride * 16;
-        auto kr = r.packed ? (r.row_bytes == 6 ? (c16 ? interval_rows_kernel<true, 2> : interval_rows_kernel<false, 2>)
-                                               : (c16 ? interval_rows_kernel<true, 1> : interval_rows_kernel<false, 1>))
-                           : (c16 ? interval_rows_kernel<true, 0> : interval_rows_kernel<false, 0>);
         const int bpc = std::max(1, std::min(32 / kIvWaves, kLdsBytes / (lds_c + kIvRowsStaticLds)));
         const long long grid_r = std::min((long long)cus * bpc, (N + kIvTile - 1) / kIvTile);
         // tiles of equal size, the same number for every block (10^6 reads in tiles of 256 are 3.8 per block: a last round
         // in which a fifth of the blocks have nothing to do)
         const long long rounds = (N + grid_r * kIvTile - 1) / (grid_r * kIvTile);
         const int tile_reads = (int)((N + grid_r * rounds - 1) / (grid_r * rounds));
-        LAUNCH(kr, dim3((unsigned)grid_r), dim3(kIvWaves * kWave), lds_c, s, ix->dev, N, reinterpret_cast<const uint16_t *>(ws.kj),
-               g.kj_row, ws.qp, g.qp_stride, g.qp_recs, reinterpret_cast<void *>(r.rows), reinterpret_cast<long long *>(r.offsets),
-               (long long)r.cap_rows, bsums, cnt, block_shift, esc, sched_c, tile_reads);
+        LAUNCH(pick_interval_rows(c16, r.packed, r.row_bytes), dim3((unsigned)grid_r), dim3(kIvWaves * kWave), lds_c, s, ix->dev, N,
+               reinterpret_cast<const uint16_t *>(ws.kj), g.kj_row, ws.qp, g.qp_stride, g.qp_recs, reinterpret_cast<void *>(r.rows),
+               reinterpret_cast<long long *>(r.offsets), (long long)r.cap_rows, bsums, cnt, block_shift, esc, sched_c, tile_reads);
         return GENIE_OK;
     }
     // K_C, long reads and the slot form: intervals + final rows, 16 lanes per read (4 reads per wave pass), persistent blocks
     // (half the blocks help on the 1 Mb reference, 1.50 -> 1.40 ms per 4 x 10^6 reads, but cost at 300 kb, 0.215 -> 0.250 ms
     // per 10^6, with the same 8 MB table: not worth a rule)
-    long long grid_c = (long long)cus * (32 / kIvWaves);
-    const long long need_c = (N + kIvWaves * 4 * kIvUnroll - 1) / (kIvWaves * 4 * kIvUnroll);
-    if (grid_c > need_c) grid_c = need_c;
-    auto kc = r.offsets ? (c16 ? interval_kernel<true, true, true> : interval_kernel<true, true, false>)
-                        : (c16 ? interval_kernel<false, WIDE, true> : interval_kernel<false, WIDE, false>);
-    // CSR rows: through the scanned block sums and the counts; slots: `cap` per read
-    LAUNCH(kc, dim3((unsigned)grid_c), dim3(kIvWaves * kWave), 0, s, ix->dev, N, ws.kj, g.kj_row, head, head_stride, ws.qp,
-           g.qp_stride, r.offsets ? reinterpret_cast<void *>(r.rows) : reinterpret_cast<void *>(r.slots), r.offsets ? 0 : r.cap,
-           reinterpret_cast<long long *>(r.offsets), r.offsets ? (long long)r.cap_rows : 0ll, bsums, r.offsets ? cnt : nullptr,
-           r.offsets ? block_shift : 0, esc, sched_c);
+    const long long grid_c = std::min((long long)cus * (32 / kIvWaves), (N + kIvWaves * 4 - 1) / (kIvWaves * 4));
+    // slots: `cap` per read; CSR rows: through the scanned block sums and the counts
+    void *out_c = r.slots;
+    int cap_c = r.cap, shift_c = 0;
+    long long cap_rows_c = 0;
+    const int32_t *before_c = nullptr;
+    if (r.offsets) { out_c = r.rows; cap_c = 0; cap_rows_c = r.cap_rows; before_c = cnt; shift_c = block_shift; }
+    LAUNCH(pick_interval(r.offsets != nullptr, WIDE, c16), dim3((unsigned)grid_c), dim3(kIvWaves * kWave), 0, s, ix->dev, N, ws.kj,
+           g.kj_row, head, head_stride, ws.qp, g.qp_stride, out_c, cap_c, reinterpret_cast<long long *>(r.offsets), cap_rows_c, bsums,
+           before_c, shift_c, sched_c);
     return GENIE_OK;
 }
 

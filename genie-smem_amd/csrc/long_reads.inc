@@ -38,7 +38,7 @@
 // another one has flagged its unit's absent base), then
 //   LRM lr_ms_kernel      one block per window, one lane per position: fwd[a] - a to the position's place in the caller's
 //                         array, and the SA interval of [a, fwd[a]) from the match-table entry of the position's P2-mer where
-//                         that decides (interval_from_entry, as K_C), else from sa_interval over the packed unit -- those
+//                         that decides (interval_from_window, as K_C), else from sa_interval over the packed unit -- those
 //                         positions are gathered per block so that the search runs on full waves.
 namespace {
 
@@ -347,18 +347,10 @@ __global__ void __launch_bounds__(kLrWin) lr_ms_kernel(DevIndex ix, const long l
     slen[t] = len;
     __syncthreads();
     const QPlain Q{packed + lr_wd(off, r)};
-    const int P2 = ix.P2;
-    const __amdgpu_buffer_rsrc_t ov =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<MatchOv16 *>(ix.ov), 0, ix.ov_entries * (int)sizeof(MatchOv16), 0x00020000);
     const bool act = len > 0;
     const uint64_t x = act ? Q.win(a) : 0ull;
-    const uint32_t c = (uint32_t)(x >> (64 - 2 * P2));
-    const int4 *en = C16 ? reinterpret_cast<const int4 *>(reinterpret_cast<const MatchRec16 *>(ix.mtab) + c)
-                         : reinterpret_cast<const int4 *>(ix.mtab + c);
-    int4 ra = make_int4(0, 0, 0, 0), rb = make_int4(0, 0, 0, 0);
-    if (act) { ra = en[0]; if (!C16) rb = en[1]; }
     int2 iv;                                                     // (-1, -1) where the match is empty
-    const bool fast = interval_from_entry<C16>(ra, rb, x, len, P2, ov, act, iv);
+    const bool fast = interval_from_window<C16>(ix, x, len, act, iv);
     if (in && (fast || !act)) lr_store_lohi(lohi + v0 + t, iv);
     const bool general = act && !fast;
     const unsigned long long gb = __ballot(general);

@@ -25,7 +25,8 @@
 //        SA interval [lo, hi] of every emitted substring: from ONE match-table entry where that decides
 //        (patterns of P2 .. P2 + 16 bases; longer ones that single out one key; the longest occurring prefix
 //        of an absent P2-mer; interval_from_entry), else the general bounded search over suffix-array rows, 64 at a
-//        time from a per-wave list; packed read from K_A's output.  Persistent 512-thread blocks.  Short reads in CSR
+//        time from a per-wave list (one step for both kernels: resolve_row, WaveList); packed read from K_A's output.
+//        Persistent 512-thread blocks.  Short reads in CSR
 //        form: interval_rows_kernel, the rows of a tile of 256 reads densely over the lanes, the tile's slots staged in
 //        LDS; long reads and the slot form: interval_kernel, 16 lanes per read.
 
@@ -414,17 +415,17 @@ __global__ void __launch_bounds__(256) traverse_long_kernel(const int32_t *__res
 }
 
 // ------------------------------------------------------------------ K_C
-// Final rows (start, end, lo, hi): 16 lanes per read, each row written exactly once, 16 lanes x 16 B
-// contiguous.  CSR = false: row t of read r goes to slots[r*cap + t] (t < cap);
-// CSR = true:  to out[offsets[r] + t] (offsets = exclusive scan of the counts, rows past out_cap dropped).
+// Final rows (start, end, lo, hi), each written exactly once.  CSR = false: row t of read r goes to slots[r*cap + t]
+// (t < cap); CSR = true:  to out[offsets[r] + t] (offsets = exclusive scan of the counts, rows past out_cap dropped).
 //
 // Patterns of P2 .. P2 + 16 bases whose match-table entry is not slow (most SMEMs) are answered on the spot from
 // that ONE entry: it holds the first row of the P2-mer and the 16-base continuation of each of (up to six of) its
 // suffixes in suffix-array order, so the rows that carry the pattern are those whose key agrees with it that far.
 // Everything else (shorter, longer, slow entries) goes onto a per-wave list and is searched 64 at a time with the
 // general interval search -- so that its (long) code runs on full waves, not on the odd lane of every wave.
+// That step is resolve_row (below), the same for interval_kernel (a row per lane of a read's 16) and interval_rows_kernel
+// (a row per lane); its entry half, interval_from_window, also gives lr_ms_kernel (long_reads.inc) its intervals.
 constexpr int kIvWaves = 8;          // waves per block
-constexpr int kIvUnroll = 1;         // reads per 16-lane group and iteration
 constexpr int kIvList = 128;         // list entries per wave: fewer than 64 pending + at most 64 appended at once
 
 // Final row: (start, end, lo, hi) as four int32 (COUT = 0), or the compact forms of genie_find_smems_packed / _packed6:
@@ -532,7 +533,96 @@ __device__ __forceinline__ bool interval_from_entry(const int4 ra, const int4 rb
     return fast;
 }
 
-// Long reads (WIDE) and the slot form; the CSR forms of short reads run interval_rows_kernel (below).
+// The overflow blocks of the compact table as a buffer resource (mt_ov_scan's loads are bounds-checked by it).
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t mt_ov_rsrc(const DevIndex &ix)
+{
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<MatchOv16 *>(ix.ov), 0, ix.ov_entries * (int)sizeof(MatchOv16), 0x00020000);
+}
+
+// The match-table entry of the P2-mer `code`: 16 bytes (`ra`) of the compact form, 32 (`ra`, `rb`) of the full one; zeros
+// for a lane that is not `act`.
+template <bool C16>
+__device__ __forceinline__ void mt_load_entry(const DevIndex &ix, uint32_t code, bool act, int4 &ra, int4 &rb)
+{
+    const int4 *en = C16 ? reinterpret_cast<const int4 *>(reinterpret_cast<const MatchRec16 *>(ix.mtab) + code)
+                         : reinterpret_cast<const int4 *>(ix.mtab + code);
+    ra = make_int4(0, 0, 0, 0);
+    rb = make_int4(0, 0, 0, 0);
+    if (act) { ra = en[0]; if (!C16) rb = en[1]; }
+}
+
+// The entry half of a row: the pattern's window -> its P2-mer's entry -> interval_from_entry (also lr_ms_kernel's).
+template <bool C16>
+__device__ __forceinline__ bool interval_from_window(const DevIndex &ix, uint64_t w, int len, bool act, int2 &iv)
+{
+    int4 ra, rb;
+    mt_load_entry<C16>(ix, (uint32_t)(w >> (64 - 2 * ix.P2)), act, ra, rb);
+    return interval_from_entry<C16>(ra, rb, w, len, ix.P2, mt_ov_rsrc(ix), act, iv);
+}
+
+// A wave's list of the rows that wait for the general search, {row index lo, hi, read, start | end << 16} in LDS, with
+// what the search needs: the packed reads as K_A left them (QIn: QRecs / QPlain, kernels.hip) and where the rows go.
+template <int COUT, class QIn>
+struct WaveList {
+    const DevIndex &ix;
+    const RefRec *qp_in;
+    int qp_stride;
+    void *out;
+    RowEscapes esc;
+    int4 *list;                      // kIvList entries
+    int nlist;
+
+    // the general search of list[o .. o + n), n <= 64
+    __device__ __forceinline__ void search(int o, int n) const
+    {
+        const int lane = threadIdx.x & (kWave - 1);
+        if (lane < n) {
+            const int4 en = list[o + lane];
+            const int k = en.w & 0xFFFF, j = (int)((uint32_t)en.w >> 16);
+            const QIn qp{reinterpret_cast<decltype(QIn::p)>(qp_in + (long long)en.z * qp_stride)};
+            const int2 iv = sa_interval(ix, ix.dir, qp, k, j - k);
+            emit_row<COUT>(out, ((long long)en.y << 32) | (uint32_t)en.x, k, j, iv.x, iv.y, esc);
+        }
+    }
+    // The lanes with `general` append their row, in lane order; 64 or more pending: the last 64 are searched.  Called by the
+    // whole wave.
+    __device__ __forceinline__ void append(bool general, long long row, int read, int k, int j)
+    {
+        const int lane = threadIdx.x & (kWave - 1);
+        const unsigned long long gb = __ballot(general);
+        if (gb) {
+            if (general)
+                list[nlist + __popcll(gb & ((1ull << lane) - 1ull))] = make_int4((int)(uint32_t)row, (int)(row >> 32), read, k | (j << 16));
+            nlist += __popcll(gb);
+            wave_lds_fence();
+            if (nlist >= 64) {
+                nlist -= 64;
+                search(nlist, 64);
+                wave_lds_fence();
+            }
+        }
+    }
+    // what is left when the kernel ends
+    __device__ __forceinline__ void drain() const
+    {
+        if (nlist) search(0, nlist);
+    }
+};
+
+// ONE ROW: the pattern [k, j) of `read`, whose window is `w`, to row `row` -- from its table entry where that decides, else
+// onto the wave's list.  Called by the whole wave (`act`: the lane has a row).
+template <bool C16, int COUT, class QIn>
+__device__ __forceinline__ void resolve_row(bool act, uint64_t w, int k, int j, long long row, int read, WaveList<COUT, QIn> &wl)
+{
+    int2 iv;
+    const bool fast = interval_from_window<C16>(wl.ix, w, j - k, act, iv);
+    if (fast) emit_row<COUT>(wl.out, row, k, j, iv.x, iv.y, wl.esc);
+    wl.append(act && !fast, row, read, k, j);
+}
+
+// Long reads (WIDE) and the slot form, 16 LANES PER READ, a read's rows 16 lanes x 16 B contiguous; the CSR forms of short
+// reads run interval_rows_kernel (below).  One read per 16-lane group and iteration (measured: 1 at 8 waves per SIMD beats 2 at 6; the kernel is bound by the
+// chain of dependent loads count+pair -> window -> entry -> row, whose stages add up).
 template <bool CSR, bool WIDE, bool C16>
 __global__ void __launch_bounds__(kIvWaves * 64, 8) interval_kernel(DevIndex ix, long long N,
                                                                     const void *__restrict__ kj_in, int kj_stride,
@@ -542,117 +632,47 @@ __global__ void __launch_bounds__(kIvWaves * 64, 8) interval_kernel(DevIndex ix,
                                                                     long long *__restrict__ offsets, long long out_cap,
                                                                     const unsigned long long *__restrict__ block_base,
                                                                     const int32_t *__restrict__ before_in_block, int block_shift,
-                                                                    RowEscapes esc, int sched)
+                                                                    int sched)
 {
     static_assert(WIDE || !CSR, "short reads, CSR rows: interval_rows_kernel");
-    constexpr int COUT = 0;
-    __shared__ int4 lists[kIvWaves][kIvList];            // {row index lo, hi, read, start | end << 16}
+    __shared__ int4 lists[kIvWaves][kIvList];
     typedef typename std::conditional<WIDE, uint32_t, uint16_t>::type kj_t;
     typedef typename std::conditional<WIDE, QRecs, QPlain>::type QIn;      // how K_A left the packed read (kernels.hip)
-    constexpr int kHeadEntries = kPairHeadWords * 8 / (int)sizeof(kj_t);
+    constexpr int kHeadEntries = kPairHeadWords * 8 / (int)sizeof(kj_t), kShift = ReadTraits<WIDE>::kj_shift;
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = rfl((int)(threadIdx.x >> 6));
     const int sub = lane & 15;
-    const int P2 = ix.P2;
-    const __amdgpu_buffer_rsrc_t ov =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<MatchOv16 *>(ix.ov), 0, ix.ov_entries * (int)sizeof(MatchOv16), 0x00020000);
-    int4 *list = lists[wave];
-    int nlist = 0;
-    // the general search of list[o .. o + n), n <= 64
-    auto search_list = [&](int o, int n) {
-        if (lane < n) {
-            const int4 en = list[o + lane];
-            const int k = en.w & 0xFFFF, j = (int)((uint32_t)en.w >> 16);
-            const QIn qp{reinterpret_cast<decltype(QIn::p)>(qp_in + (long long)en.z * qp_stride)};
-            const int2 iv = sa_interval(ix, ix.dir, qp, k, j - k);
-            emit_row<COUT>(out, ((long long)en.y << 32) | (uint32_t)en.x, k, j, iv.x, iv.y, esc);
-        }
-    };
-    // kIvUnroll reads per 16-lane group and iteration (measured: 1 at 8 waves per SIMD beats 2 at 6; the kernel is
-    // bound by the chain of dependent loads count+pair -> window -> entry -> row, whose stages add up)
-    constexpr int U = kIvUnroll;
-    const long long step = (long long)gridDim.x * kIvWaves * 4 * U;
+    WaveList<0, QIn> wl{ix, qp_in, qp_stride, out, RowEscapes{}, lists[wave], 0};      // four-int32 rows: no escapes
+    const long long step = (long long)gridDim.x * kIvWaves * 4;
     // (issue priority rotated per iteration, as in the match-statistics kernel: the CU serves its oldest waves first)
     const bool rotate = !(sched & 1);
-    const int round_of_block = (int)(blockIdx.x / (uint32_t)(sched >> 8));
-    int it = round_of_block;
-    for (long long r0 = ((long long)blockIdx.x * kIvWaves + wave) * 4 * U; r0 < N; r0 += step, it++) {
+    int it = (int)(blockIdx.x / (uint32_t)(sched >> 8));
+    for (long long r0 = ((long long)blockIdx.x * kIvWaves + wave) * 4; r0 < N; r0 += step, it++) {
         if (rotate) set_wave_priority(it);
-        long long r[U], base[U];
-        int c[U];
-        bool more = false;
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            r[u] = r0 + 4 * u + (lane >> 4);
-            const bool have = r[u] < N;
-            if (!have) r[u] = 0;
-            // the row's entry 0 is the count; the offset is only needed when the row is stored
-            c[u] = have ? (int)reinterpret_cast<const kj_t *>(head_in + r[u] * (long long)head_stride)[0] : 0;
-            // CSR: the row offset of a read = scanned sum of the traversal blocks before its block + the counts before
-            // it inside the block; written out here (offsets[N] by whoever holds the last read)
-            base[u] = CSR ? (have ? (long long)block_base[r[u] >> block_shift] + before_in_block[r[u]] : 0) : r[u] * (long long)cap;
-            if (CSR && have && sub == 0) {
-                if (!COUT) offsets[r[u]] = base[u];
-                if (r[u] == N - 1) offsets[COUT ? 0 : N] = base[u] + c[u];       // COUT: `offsets` is the one-word total
-            }
-            if (!CSR) c[u] = c[u] < cap ? c[u] : cap;
-            more |= c[u] > 0;
+        const bool have = r0 + (lane >> 4) < N;
+        const long long r = have ? r0 + (lane >> 4) : 0;
+        const kj_t *head = reinterpret_cast<const kj_t *>(head_in + r * (long long)head_stride);
+        // the row's entry 0 is the count
+        int c = have ? (int)head[0] : 0;
+        // CSR: the row offset of a read = scanned sum of the traversal blocks before its block + the counts before
+        // it inside the block; written out here (offsets[N] by whoever holds the last read)
+        const long long base = CSR ? (have ? (long long)block_base[r >> block_shift] + before_in_block[r] : 0) : r * (long long)cap;
+        if (CSR && have && sub == 0) {
+            offsets[r] = base;
+            if (r == N - 1) offsets[N] = base + c;
         }
-        for (int t0 = 0; __any(more); t0 += 16) {
+        if (!CSR) c = c < cap ? c : cap;
+        for (int t0 = 0; __any(t0 < c); t0 += 16) {
             const int t = t0 + sub;
-            uint32_t e[U];
-            uint64_t w[U];
-            int4 ra[U], rb[U];
-            bool act[U];
-            more = false;
-#pragma unroll
-            for (int u = 0; u < U; u++) {
-                act[u] = t < c[u] && (!CSR || base[u] + t < out_cap);
-                more |= t0 + 16 < c[u];
-                const kj_t *row = t + 1 < kHeadEntries ? reinterpret_cast<const kj_t *>(head_in + r[u] * (long long)head_stride)
-                                                       : reinterpret_cast<const kj_t *>(kj_in) + r[u] * (long long)kj_stride;
-                e[u] = act[u] ? (uint32_t)row[t + 1] : 0u;
-            }
-#pragma unroll
-            for (int u = 0; u < U; u++) {
-                const int k = (int)(e[u] & ((1u << ReadTraits<WIDE>::kj_shift) - 1));
-                w[u] = act[u] ? QIn{reinterpret_cast<decltype(QIn::p)>(qp_in + r[u] * (long long)qp_stride)}.win(k) : 0ull;
-            }
-#pragma unroll
-            for (int u = 0; u < U; u++) {
-                const uint32_t c = (uint32_t)(w[u] >> (64 - 2 * P2));
-                const int4 *en = C16 ? reinterpret_cast<const int4 *>(reinterpret_cast<const MatchRec16 *>(ix.mtab) + c)
-                                     : reinterpret_cast<const int4 *>(ix.mtab + c);
-                ra[u] = make_int4(0, 0, 0, 0);
-                rb[u] = make_int4(0, 0, 0, 0);
-                if (act[u]) { ra[u] = en[0]; if (!C16) rb[u] = en[1]; }
-            }
-#pragma unroll
-            for (int u = 0; u < U; u++) {
-                const int k = (int)(e[u] & ((1u << ReadTraits<WIDE>::kj_shift) - 1)), j = (int)(e[u] >> ReadTraits<WIDE>::kj_shift);
-                const int len = j - k;
-                int2 iv;
-                const bool fast = interval_from_entry<C16>(ra[u], rb[u], w[u], len, P2, ov, act[u], iv);
-                if (fast) emit_row<COUT>(out, base[u] + t, k, j, iv.x, iv.y, esc);
-                const bool general = act[u] && !fast;
-                const unsigned long long gb = __ballot(general);
-                if (gb) {
-                    if (general) {
-                        const long long row = base[u] + t;
-                        list[nlist + __popcll(gb & ((1ull << lane) - 1ull))] = make_int4((int)(uint32_t)row, (int)(row >> 32), (int)r[u], k | (j << 16));
-                    }
-                    nlist += __popcll(gb);
-                    wave_lds_fence();
-                    if (nlist >= 64) {
-                        nlist -= 64;
-                        search_list(nlist, 64);
-                        wave_lds_fence();
-                    }
-                }
-            }
+            const bool act = t < c && (!CSR || base + t < out_cap);
+            const kj_t *row = t + 1 < kHeadEntries ? head : reinterpret_cast<const kj_t *>(kj_in) + r * (long long)kj_stride;
+            const uint32_t e = act ? (uint32_t)row[t + 1] : 0u;
+            const int k = (int)(e & ((1u << kShift) - 1)), j = (int)(e >> kShift);
+            const uint64_t w = act ? QIn{reinterpret_cast<decltype(QIn::p)>(qp_in + r * (long long)qp_stride)}.win(k) : 0ull;
+            resolve_row<C16>(act, w, k, j, base + t, (int)r, wl);
         }
     }
-    if (nlist) search_list(0, nlist);
+    wl.drain();
 }
 
 // ------------------------------------------------------------------ K_C, short reads, CSR rows
@@ -667,8 +687,9 @@ __global__ void __launch_bounds__(kIvWaves * 64, 8) interval_kernel(DevIndex ix,
 //   3. the tile's rows are worked through in chunks of 64 per wave: a row finds its read by bisecting the starts between
 //      the reads of its chunk's first row and of the next chunk's (a handful: three steps, not eight), takes its pair and
 //      its window from LDS, loads ONE table entry, and stores at tile base + row -- a wave's stores are consecutive rows.
-// What the entry cannot decide goes to the wave's list and the general search, as above (the list outlives a tile, so the
-// search reads the packed read from global memory).  Rows, offsets, totals and escapes are those of interval_kernel.
+// From the window on a row takes interval_kernel's step (resolve_row); the wave's list outlives a tile, so its search reads
+// the packed read from global memory.  Rows and offsets are those of interval_kernel; the packed forms (COUT) add totals
+// and escapes.
 constexpr int kIvTile = 256;         // most reads per tile (tiles need not be traversal blocks)
 constexpr int kIvChunks = kIvTile * 255 / kWave + 2;                               // 64-row chunks of a tile's rows, and one
 constexpr int kIvRowsStaticLds = kIvWaves * kIvList * 16 + 2 * kIvTile * 4 + ((kIvChunks + 15) & ~15) + 16;   // lists, starts, chunk_read, row count
@@ -692,22 +713,8 @@ __global__ void __launch_bounds__(kIvWaves * 64, 8) interval_rows_kernel(DevInde
     constexpr int kHeadEntries = kPairHeadWords * 8 / 2;
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = rfl((int)(threadIdx.x >> 6));
-    const int P2 = ix.P2;
     const int slot_bytes = qp_stride * 16, head_off = qp_recs * 16;
-    const __amdgpu_buffer_rsrc_t ov =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<MatchOv16 *>(ix.ov), 0, ix.ov_entries * (int)sizeof(MatchOv16), 0x00020000);
-    int4 *list = lists[wave];
-    int nlist = 0;
-    // the general search of list[o .. o + n), n <= 64
-    auto search_list = [&](int o, int n) {
-        if (lane < n) {
-            const int4 en = list[o + lane];
-            const int k = en.w & 0xFFFF, j = (int)((uint32_t)en.w >> 16);
-            const QPlain qp{reinterpret_cast<const uint64_t *>(qp_in + (long long)en.z * qp_stride)};
-            const int2 iv = sa_interval(ix, ix.dir, qp, k, j - k);
-            emit_row<COUT>(out, ((long long)en.y << 32) | (uint32_t)en.x, k, j, iv.x, iv.y, esc);
-        }
-    };
+    WaveList<COUT, QPlain> wl{ix, qp_in, qp_stride, out, esc, lists[wave], 0};
     // (issue priority rotated per tile, as in the match-statistics kernel: the CU serves its oldest waves first)
     const bool rotate = !(sched & 1);
     int it = (int)(blockIdx.x / (uint32_t)(sched >> 8));
@@ -780,31 +787,9 @@ __global__ void __launch_bounds__(kIvWaves * 64, 8) interval_rows_kernel(DevInde
             // the window QPlain::win returns: words k / 32 and k / 32 + 1 of the slot
             const uint64_t *wp = reinterpret_cast<const uint64_t *>(slot) + (k >> 5);
             const uint64_t w = act ? funnel(wp[0], wp[1], (k & 31) * 2) : 0ull;
-            const uint32_t c = (uint32_t)(w >> (64 - 2 * P2));
-            const int4 *en = C16 ? reinterpret_cast<const int4 *>(reinterpret_cast<const MatchRec16 *>(ix.mtab) + c)
-                                 : reinterpret_cast<const int4 *>(ix.mtab + c);
-            int4 ra = make_int4(0, 0, 0, 0), rb = make_int4(0, 0, 0, 0);
-            if (act) { ra = en[0]; if (!C16) rb = en[1]; }
-            int2 iv;
-            const bool fast = interval_from_entry<C16>(ra, rb, w, j - k, P2, ov, act, iv);
-            if (fast) emit_row<COUT>(out, tile_base + q, k, j, iv.x, iv.y, esc);
-            const bool general = act && !fast;
-            const unsigned long long gb = __ballot(general);
-            if (gb) {
-                if (general) {
-                    const long long row = tile_base + q;
-                    list[nlist + __popcll(gb & ((1ull << lane) - 1ull))] = make_int4((int)(uint32_t)row, (int)(row >> 32), (int)(r0 + i), k | (j << 16));
-                }
-                nlist += __popcll(gb);
-                wave_lds_fence();
-                if (nlist >= 64) {
-                    nlist -= 64;
-                    search_list(nlist, 64);
-                    wave_lds_fence();
-                }
-            }
+            resolve_row<C16>(act, w, k, j, tile_base + q, (int)(r0 + i), wl);
         }
         __syncthreads();                                  // the next tile overwrites the slots and the starts
     }
-    if (nlist) search_list(0, nlist);
+    wl.drain();
 }
