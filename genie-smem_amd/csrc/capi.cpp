@@ -493,6 +493,35 @@ int genie_match_stats(const genie_index *ix, int32_t flags, const uint8_t *d_bas
                               workspace_bytes, stream);
 }
 
+int64_t genie_exact_match_workspace_bytes(int64_t N, int64_t total_bases, int64_t max_len, int32_t flags)
+{
+    if (N < 0 || total_bases < 0 || max_len < 0 || max_len > 0x7fffffffll) return (int64_t)GENIE_E_INVALID;
+    if (flags & ~GENIE_READS_BOTH_STRANDS) return (int64_t)GENIE_E_INVALID;
+    return exact_match_workspace_bytes(N, total_bases, flags);
+}
+
+int genie_exact_match(const genie_index *ix, int32_t flags, const uint8_t *d_bases, const int64_t *d_pat_offsets, int64_t N,
+                      int64_t total_bases, int64_t max_len, int32_t *d_lohi, int32_t *d_counts, int32_t *d_status, void *d_workspace,
+                      int64_t workspace_bytes, void *stream)
+{
+    // argument checks first: they need no device image
+    if (!ix) return GENIE_E_INVALID;
+    if (N < 0 || total_bases < 0 || max_len < 0 || max_len > 0x7fffffffll || workspace_bytes < 0 ||
+        (N > 0 && (!d_pat_offsets || !d_lohi)) || (total_bases > 0 && !d_bases))
+        return GENIE_E_INVALID;
+    if (flags & ~GENIE_READS_BOTH_STRANDS) return GENIE_E_INVALID;       // SPLIT_BREAKS too: a pattern with a break has no interval
+    if ((reinterpret_cast<uintptr_t>(d_lohi) & 7) != 0 || (reinterpret_cast<uintptr_t>(d_counts) & 3) != 0 ||
+        (reinterpret_cast<uintptr_t>(d_status) & 3) != 0)
+        return GENIE_E_INVALID;
+    if (N > 0 && (!d_workspace || (reinterpret_cast<uintptr_t>(d_workspace) & 255) != 0 ||
+                  workspace_bytes < exact_match_workspace_bytes(N, total_bases, flags)))
+        return GENIE_E_CAPACITY;
+    int rc = ready(ix);
+    if (rc) return rc;
+    return launch_exact_match(ix, flags, d_bases, d_pat_offsets, N, total_bases, max_len, d_lohi, d_counts, d_status, d_workspace,
+                              workspace_bytes, stream);
+}
+
 int64_t genie_reads_from_text_tmp_bytes(int64_t text_bytes, int64_t cap_reads)
 {
     if (text_bytes < 0 || cap_reads < 0) return (int64_t)GENIE_E_INVALID;

@@ -395,8 +395,9 @@ struct LongArea {
     long long total, nwords, nwin;
 };
 
-// smems false: the pieces LR1 and LR2 use (the match-statistics tail), the others empty
-inline int64_t long_layout(uint8_t *p, int64_t N, int64_t total, LongArea *a, bool smems = true)
+// smems false: the pieces LR1 and LR2 use (the match-statistics tail), the others empty; fwd false as well: those of LR1
+// alone (the exact-match tail)
+inline int64_t long_layout(uint8_t *p, int64_t N, int64_t total, LongArea *a, bool smems = true, bool fwd = true)
 {
     a->total = total;
     a->nwords = total / 32 + 3 * N + 4;
@@ -407,7 +408,7 @@ inline int64_t long_layout(uint8_t *p, int64_t N, int64_t total, LongArea *a, bo
     c.take(a->cnt, smems ? 4 * N : 0);
     c.take(a->sums, 8 * ((N + kScanBlock - 1) / kScanBlock + 1));
     c.take(a->packed, 8 * a->nwords);
-    c.take(a->fwd, 4 * total);
+    c.take(a->fwd, fwd ? 4 * total : 0);
     c.take(a->bst, smems ? 4 * total : 0);
     c.take(a->jc, smems ? 8 * total : 0);
     c.take(a->mark, smems ? total : 0);

@@ -30,6 +30,7 @@
 //   Between passes the host reads the pass's row total (one synchronisation per extra pass).
 // genie_match_stats shares all of this up to the units of a pass (lu_run); in place of lr_pipeline and LU4 it runs
 // lr_match_stats, which writes every position's values at its virtual position: ua[] of a segment, the offset of a strand-read.
+// genie_exact_match (exact_match.inc) shares it too, never with GENIE_READS_SPLIT_BREAKS: its units are the strand-patterns.
 namespace {
 
 constexpr int kLuChunk = 16384;           // virtual positions per block of LU1 / LU2 ...
@@ -290,11 +291,13 @@ struct LongExPass {
     long long *uoff, *loff;          // C + 1 each: unit offsets, the pass's row offsets
 };
 
-// smems false: the layout of the match-statistics tail (no rows: the pieces of LR3 .. LR5 and the row offsets are empty)
-inline int64_t long_ex_pass_layout(uint8_t *p, int64_t C, int64_t total, int S, bool split, LongExPass *a, bool smems = true)
+// smems false: the layout of the match-statistics tail (no rows: the pieces of LR3 .. LR5 and the row offsets are empty); fwd
+// false as well: that of the exact-match tail (no fwd[] either)
+inline int64_t long_ex_pass_layout(uint8_t *p, int64_t C, int64_t total, int S, bool split, LongExPass *a, bool smems = true,
+                                   bool fwd = true)
 {
     const bool table = S == 2 || split;
-    Carver c{p, long_layout(p, C, S * total, &a->lr, smems)};
+    Carver c{p, long_layout(p, C, S * total, &a->lr, smems, fwd)};
     c.take(a->ua, split ? 8 * C : 0);
     c.take(a->ub, table ? 8 * C : 0);
     c.take(a->ulen, split ? 4 * C : 0);
@@ -311,14 +314,14 @@ inline int64_t long_ex_units(int64_t N, int64_t total, int S, bool split)
     return (S == 2 || split ? std::max<int64_t>(1, S * N) : N) + (split ? S * total / kLuSpare : 0);
 }
 
-inline int64_t long_ex_bytes(int64_t N, int64_t total_bases, int32_t flags, bool smems)
+inline int64_t long_ex_bytes(int64_t N, int64_t total_bases, int32_t flags, bool smems, bool fwd = true)
 {
     const int S = (flags & GENIE_READS_BOTH_STRANDS) ? 2 : 1;
     const bool split = (flags & GENIE_READS_SPLIT_BREAKS) != 0;
     LongExFixed f;
     LongExPass a;
     return long_ex_fixed_layout(nullptr, N, total_bases, S, split, &f) +
-           long_ex_pass_layout(nullptr, long_ex_units(N, total_bases, S, split), total_bases, S, split, &a, smems);
+           long_ex_pass_layout(nullptr, long_ex_units(N, total_bases, S, split), total_bases, S, split, &a, smems, fwd);
 }
 
 // One pass of at most C units, as the front hands it to a tail
@@ -331,7 +334,7 @@ struct LuPass {
 
 // The front that genie_find_smems_long_ex and genie_match_stats share: everything up to "the units of this pass exist" (LU0,
 // the strand-read table, LU1 .. LU3, the passes).  What is done with the units is the TAIL's:
-//   tail.kSmems                      which workspace layout the call has
+//   tail.kSmems, tail.kFwd           which workspace layout the call has
 //   tail.empty()                     N == 0
 //   tail.whole(lr, uoff, usrc)       the units are the S N strand-reads (no SPLIT_BREAKS, or no break found); their statuses
 //                                    are in lr.st
@@ -351,7 +354,7 @@ int lu_run(const genie_index *ix, int32_t mode, int32_t flags, const uint8_t *d_
     uint8_t *pass = static_cast<uint8_t *>(d_ws) + fixed;
     // The strand-reads as units.  On one strand the caller's offsets are the unit offsets and there is no table.
     LongExPass whole;
-    long_ex_pass_layout(pass, SN, total_bases, S, false, &whole, Tail::kSmems);
+    long_ex_pass_layout(pass, SN, total_bases, S, false, &whole, Tail::kSmems, Tail::kFwd);
     int *const flag = whole.lr.flag;
     long long *const tsrc = S == 2 ? whole.ub : nullptr, *const toff = S == 2 ? whole.uoff : nullptr;
     HIP_TRY(hipMemsetAsync(flag, 0, 8, s));
@@ -382,9 +385,9 @@ int lu_run(const genie_index *ix, int32_t mode, int32_t flags, const uint8_t *d_
     LongExPass a;
     // units per pass: as many as the workspace holds (at least S N: the caller sized it for that many)
     const long long C = pass_size(std::max<long long>(SN, 1), U, [&](long long c) {
-        return long_ex_pass_layout(nullptr, c, total_bases, S, true, &a, Tail::kSmems) <= ws_bytes - fixed;
+        return long_ex_pass_layout(nullptr, c, total_bases, S, true, &a, Tail::kSmems, Tail::kFwd) <= ws_bytes - fixed;
     });
-    long_ex_pass_layout(pass, C, total_bases, S, true, &a, Tail::kSmems);
+    long_ex_pass_layout(pass, C, total_bases, S, true, &a, Tail::kSmems, Tail::kFwd);
     for (long long p0 = 0; p0 < U; p0 += C) {
         const long long p1 = std::min(U, p0 + C), Cp = p1 - p0;
         HIP_TRY(hipMemsetAsync(a.lr.st, 0, Cp * 4, s));           // GENIE_READ_OK: a unit holds no break
@@ -400,7 +403,7 @@ int lu_run(const genie_index *ix, int32_t mode, int32_t flags, const uint8_t *d_
 
 // The SMEM tail: lr_pipeline over the units, then LU4.  Between passes the host reads the pass's row total.
 struct LuSmemTail {
-    static constexpr bool kSmems = true;
+    static constexpr bool kSmems = true, kFwd = true;
     const genie_index *ix;
     int32_t mode, min_len;
     const uint8_t *d_bases;
@@ -455,7 +458,7 @@ struct LuSmemTail {
 // The match-statistics tail: lr_match_stats over the units.  Positions that no unit covers (breaks; what lies in front of the
 // first read and behind the last) are filled beforehand; nothing is read back between passes.
 struct LuMsTail {
-    static constexpr bool kSmems = false;
+    static constexpr bool kSmems = false, kFwd = true;
     const genie_index *ix;
     const uint8_t *d_bases;
     const long long *off;

@@ -2,7 +2,8 @@
 
 Same constructor, attribute and method names, same return conventions (0-based inclusive
 suffix-array interval tuple, the int -1 for "absent", KeyError for a symbol that does not
-occur in the reference).  The search itself is the HIP kernel behind `genie_sa_interval`;
+occur in the reference).  The search itself is the HIP kernel behind `genie_sa_interval`, for
+batches the one behind `genie_exact_match` (ragged patterns of any length, one lane each);
 index construction is the native suffix-array builder instead of the reference's O(n^2)
 rotation sort.  Files use the reference's own formats (FASTA, `<stem>-FM.json`).
 """
@@ -13,6 +14,7 @@ from os import path
 import numpy as np
 
 from .index import GenieIndex
+from .text_reads import reads_from_text
 
 
 class ExactMatch:
@@ -184,32 +186,39 @@ class ExactMatch:
         lohi = self.index(self._any_k()).sa_interval(codes.reshape(1, -1)).cpu().numpy()[0]
         return -1 if lohi[0] < 0 else (int(lohi[0]), int(lohi[1]))
 
-    def exact_match_batch(self, patterns):
-        """Batched form: list of strings -> int32 [N, 2] on the host ((-1,-1) = absent)."""
+    def _csr(self, patterns):
+        """list of strings -> (codes back to back uint8, offsets int64[N + 1]) on the host; KeyError as encode."""
         enc = [self.encode(p) for p in patterns]
-        width = max([len(e) for e in enc] + [1])
-        mat = np.zeros((len(enc), width), np.uint8)
-        lens = np.zeros(len(enc), np.int32)
-        for i, e in enumerate(enc):
-            mat[i, :len(e)] = e
-            lens[i] = len(e)
-        return self.index(self._any_k()).sa_interval(mat, lens).cpu().numpy()
+        offs = np.zeros(len(enc) + 1, np.int64)
+        offs[1:] = np.cumsum([len(e) for e in enc]) if enc else []
+        return (np.concatenate(enc).astype(np.uint8) if enc else np.zeros(0, np.uint8)), offs
+
+    def exact_match_batch(self, patterns):
+        """Batched form: list of strings of any lengths -> int32 [N, 2] on the host ((-1,-1) = absent).  The ragged list
+        goes to the device as it is, codes back to back and offsets (genie_exact_match): nothing is padded."""
+        bases, offs = self._csr(patterns)
+        return self.index(self._any_k()).exact_match(bases, offs)[0].cpu().numpy()
 
     def exact_match_positions_batch(self, patterns):
         """Batched exact_match (ExactMatch.py:174-192): for every pattern the ascending 1-based
-        positions of its occurrences ([] if absent), resolved on the device (genie_sa_interval +
+        positions of its occurrences ([] if absent), resolved on the device (genie_exact_match +
         genie_locate)."""
-        enc = [self.encode(p) for p in patterns]
-        width = max([len(e) for e in enc] + [1])
-        mat = np.zeros((len(enc), width), np.uint8)
-        lens = np.zeros(len(enc), np.int32)
-        for i, e in enumerate(enc):
-            mat[i, :len(e)] = e
-            lens[i] = len(e)
+        bases, offs = self._csr(patterns)
         ix = self.index(self._any_k())
-        off, pos = ix.locate(ix.sa_interval(mat, lens), sort=True)
+        off, pos = ix.locate(ix.exact_match(bases, offs)[0], sort=True)
         off, pos = off.cpu().numpy(), pos.cpu().numpy()
-        return [pos[off[i]:off[i + 1]].tolist() for i in range(len(enc))]
+        return [pos[off[i]:off[i + 1]].tolist() for i in range(len(offs) - 1)]
+
+    def exact_match_text(self, data, fmt="lines", both_strands=False, fold_case=False):
+        """exact_match_batch for the patterns in a text: every line a pattern (fmt "lines"), four-line FASTQ records
+        ("fastq") or FASTA records with wrapped sequences ("fasta").  data: bytes-like, numpy uint8 or torch uint8, on the
+        host or the device; it is cut and translated on the device (text_reads.reads_from_text with byte_codes(fold_case)).
+        -> (lohi int32[S*N, 2], counts int32[S*N], status int32[S*N], pattern_offsets int64[N+1]) on the device, rows as
+        GenieIndex.exact_match (S = 2 with both_strands: row 2i pattern i, 2i + 1 its reverse complement).  A symbol outside
+        the reference's alphabet becomes code 4: that pattern alone gets (-2, -2) and status READ_BAD_BASE."""
+        ix = self.index(self._any_k())
+        bases, offs, _ = reads_from_text(data, fmt, self.byte_codes(fold_case), False, ix.device)
+        return ix.exact_match(bases, offs, both_strands, counts=True) + (offs,)
 
     def exact_match_back_prop_add_one(self, char, prev_suffix_tuple):
         """ExactMatch.py:155-171: one backward-search step.  Host-side helper (not used by the

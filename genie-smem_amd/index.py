@@ -455,6 +455,32 @@ class GenieIndex:
                   _ptr(status), _ptr(ws), ws_bytes)
         return ms, lohi, status
 
+    def exact_match(self, bases, pattern_offsets, both_strands=False, counts=False):
+        """Suffix-array interval of every pattern of a CSR batch (genie_exact_match) -> (lohi int32[S*N, 2], counts
+        int32[S*N] or None without counts=True, status int32[S*N]) on the device, S = 2 with both_strands, else 1.  bases:
+        uint8 codes of all patterns back to back; pattern_offsets: int64[N+1], pattern i = bases[pattern_offsets[i] ..
+        pattern_offsets[i+1]), any length; either on the device or the host.  Row S*i + s is pattern i (s = 0) or its reverse
+        complement (s = 1): lohi as sa_interval -- (-1, -1) absent, (0, n) the empty pattern, (-2, -2) and status
+        READ_BAD_BASE for a code > 3 --, counts = hi - lo + 1 (0 where absent or bad)."""
+        self._need_device()
+        bases = self._as_dev(bases, torch.uint8).reshape(-1)
+        pattern_offsets = self._as_dev(pattern_offsets, torch.int64).reshape(-1)
+        if pattern_offsets.numel() < 1:
+            raise ValueError("pattern_offsets needs N + 1 entries")
+        n_pat = pattern_offsets.numel() - 1
+        total = bases.numel()
+        max_len = int((pattern_offsets[1:] - pattern_offsets[:-1]).max().item()) if n_pat else 0
+        max_len = min(max(max_len, 0), 2**31 - 1)
+        flags = N.READS_BOTH_STRANDS if both_strands else 0
+        strands = 2 if both_strands else 1
+        lohi = torch.empty((strands * n_pat, 2), dtype=torch.int32, device=self.device)
+        cnt = torch.empty(strands * n_pat, dtype=torch.int32, device=self.device) if counts else None
+        status = torch.empty(strands * n_pat, dtype=torch.int32, device=self.device)
+        ws, ws_bytes = self._workspace("genie_exact_match_workspace_bytes", n_pat, total, max_len, flags)
+        self._run("genie_exact_match", flags, _ptr(bases), _ptr(pattern_offsets), n_pat, total, max_len, _ptr(lohi), _ptr(cnt),
+                  _ptr(status), _ptr(ws), ws_bytes)
+        return lohi, cnt, status
+
     def find_smems_packed(self, mode, packed, max_len, lens=None, min_len=1, rows_hint=None, row_bytes=8):
         """genie_find_smems_packed (or, `row_bytes` = 6, genie_find_smems_packed6): 2-bit packed reads (packing.pack_reads;
         uint8 [N, stride] on the device) -> (counts8 uint8[N], status8 uint8[N], rows uint8[S, row_bytes], escapes int64[E, 2]);

@@ -394,6 +394,56 @@ int genie_match_stats(const genie_index *ix, int32_t flags, const uint8_t *d_bas
                       int32_t *d_status,    /* S * N, may be NULL */
                       void *d_workspace, int64_t workspace_bytes, void *stream);
 
+/* The suffix-array interval of every pattern of a batch given as CSR, on one strand or both: the batched form of
+ * ExactMatch.exact_match_back_prop (ExactMatch.py:132-151) for patterns of ANY length.  genie_sa_interval takes a padded
+ * matrix of patterns of at most GENIE_MAX_READ_LEN bases and gives each pattern a whole wave; here every pattern has its own
+ * length and one lane, and a batch of mixed lengths costs its bases, not N times its longest pattern.
+ * Inputs: pattern i is d_bases[d_pat_offsets[i] .. d_pat_offsets[i+1]) (codes 0..3; N+1 offsets, int64, on the device), any
+ * length from 0 to 2^31 - 1.  total_bases and max_len are host-side bounds, as for genie_find_smems_long: every offset must
+ * lie in [0, total_bases] and no pattern may be longer than max_len (checked on the device).  The offsets need not begin at 0
+ * nor end at total_bases: the bytes of d_bases outside [d_pat_offsets[0], d_pat_offsets[N]) are ignored.
+ * `flags`: GENIE_READS_BOTH_STRANDS or 0.  Any other bit gives GENIE_E_INVALID, GENIE_READS_SPLIT_BREAKS included (a pattern
+ * with a break has no interval).  S = 2 with the flag, else 1.  Strand-pattern q = S i + s is pattern i for s = 0 and its
+ * reverse complement for s = 1 (reversed, code c -> 3 - c, a code > 3 stays what it is), interleaved as
+ * genie_find_smems_both's strand-reads.  The reverse complement is never written to memory as bytes.
+ * Outputs, for strand-pattern q:
+ *   d_lohi[2q], d_lohi[2q + 1]  (2 S N int32) what genie_sa_interval gives for that pattern: the inclusive interval of the
+ *              suffix-array rows whose suffix starts with it; (-1, -1) if it occurs nowhere -- a base that the reference
+ *              lacks is nothing special, the pattern is simply absent --; (0, n) for the empty pattern; (-2, -2) if it
+ *              holds a code > 3.
+ *   d_counts[q]  (S N int32, may be NULL) its occurrences, hi - lo + 1: 0 where absent or bad, n + 1 for the empty pattern.
+ *   d_status[q]  (S N int32, may be NULL) GENIE_READ_BAD_BASE for (-2, -2), else GENIE_READ_OK.
+ * After the call every element of the three arrays is defined and nothing outside the declared sizes is written.  N = 0
+ * writes nothing and returns GENIE_OK; total_bases = 0 with N > 0 is a batch of empty patterns.  The output is a function of
+ * the inputs alone (no atomic decides a value).
+ * Defining properties, each byte for byte:
+ *   flags == 0     on patterns of at most GENIE_MAX_READ_LEN bases d_lohi is what genie_sa_interval writes for the same
+ *                  patterns padded into a matrix;
+ *   BOTH_STRANDS   the three outputs are those of the call without the flag on the explicit batch
+ *                  [p0, rc(p0), p1, rc(p1), ...].
+ * Checked before the device check, so on any handle: a null ix, a null d_pat_offsets or d_lohi (N > 0), a null d_bases
+ * (total_bases > 0), a negative size, max_len above 2^31 - 1, a flag bit other than BOTH_STRANDS, d_lohi not 8-byte or
+ * d_counts / d_status not 4-byte aligned give GENIE_E_INVALID; then, for N > 0, a d_workspace that is null, not 256-byte
+ * aligned or smaller than genie_exact_match_workspace_bytes(N, total_bases, max_len, flags) gives GENIE_E_CAPACITY.  Offsets
+ * that decrease or break a bound give GENIE_E_INVALID, found on the device; the outputs are then not written.
+ * The workspace function returns GENIE_E_INVALID for arguments the call would refuse, is monotone in N and total_bases and
+ * a multiple of 256, does not depend on max_len, and never exceeds genie_match_stats_workspace_bytes of the same arguments
+ * (one of that pipeline's stages runs, the packed stream: 0.25 S bytes per base -- 8 per 32 bases -- and 28 per pattern,
+ * 88 with both strands: a status word and three padding words per strand-pattern, and 16 for its entry of the strand table).
+ * Synchronisations of `stream`: one, after the offset check and before any other kernel runs.  No others.
+ * Cost: when max_len is at most 64 every lane packs its own pattern from d_bases; above that the whole batch first goes
+ * through the long-read pack stage, which then takes most of the call's time, so give max_len tightly and keep batches of
+ * short patterns apart from long ones.  A pattern of at most dir_bits bases is two directory reads; a longer one is a search of its bucket whose probes
+ * compare up to its length when it lies inside a repeat of the reference.  Lanes of a wave work on unrelated patterns, so
+ * a wave takes as long as its slowest pattern: sort a batch by length if its lengths differ by orders of magnitude. */
+int64_t genie_exact_match_workspace_bytes(int64_t N, int64_t total_bases, int64_t max_len, int32_t flags);
+int genie_exact_match(const genie_index *ix, int32_t flags, const uint8_t *d_bases, const int64_t *d_pat_offsets,
+                      int64_t N, int64_t total_bases, int64_t max_len,
+                      int32_t *d_lohi,      /* 2 * S * N */
+                      int32_t *d_counts,    /* S * N, may be NULL */
+                      int32_t *d_status,    /* S * N, may be NULL */
+                      void *d_workspace, int64_t workspace_bytes, void *stream);
+
 /* Reads from TEXT, on the device: the bytes of a file of reads -> the d_bases / d_read_offsets that genie_find_smems_long_ex
  * takes.  The reference has no counterpart (its reads are Python strings); this replaces encoding every string on the host.
  * Lines.  A line ends at a '\n' (0x0A), which is not part of it; if the line is then not empty and its last byte is '\r',
