@@ -729,6 +729,11 @@ int plan_find_smems(const genie_index *ix, int mode, int max_len, long long N, G
     const int cus = ix->num_cus > 0 ? ix->num_cus : 256;
     const int wpb = 8;                       // waves per block (block-wide in LDS: the group counter and the quad table)
     long long per_block;
+    // waves per SIMD the kernel is built for: 4 (two blocks per CU) where the table exceeds an XCD's L2; else 6 for the compact
+    // table (74 registers, nothing spilled, three blocks per CU: 595-607 us against 609-611 us per 10^6 reads with the
+    // 64-register build and its 10 spilled registers -- the miss queue is full with three blocks' requests) and 8 for the
+    // 32-byte one (on the 16 MB table of a 2.5 Mb reference the six-wave build was no faster than the four-wave one: 6.22 vs 6.10 ms)
+    g->wps = !g->wide && table_bytes(ix) > kTableFitsL2 ? 4 : ((ix->dev.flags & kFlagCompactTable) ? 6 : 8);
     if (g->wide) {
         g->grp = 1;
         g->lds = wpb * mt_long_wave_bytes(max_len, g->qp_recs) + 16;                  // + the block's counter of reads handed out
@@ -737,18 +742,22 @@ int plan_find_smems(const genie_index *ix, int mode, int max_len, long long N, G
         // `grp` reads per wave iteration: about kMtTarget positions (one round-1 pass of 3 x 64 quads), and no
         // more reads than one pack pass holds
         const int ml = std::max(max_len, 1);
-        const int grp = ix->opt_group_positions > 0 ? ix->opt_group_positions / ml : kMtTarget / ml;
-        g->grp = std::max(1, std::min(std::min(kMtMaxG, kWave / mt_pack_dwords(ml) * 4), grp));
-        g->lds = wpb * mt_wave_bytes(g->grp, ml, g->qp_recs, g->fwd_stride) + 16 + mt_quad_table_bytes(g->grp, ml);   // + the block's group counter and quad table
+        auto group_of = [&](int positions) { return std::max(1, std::min(std::min(kMtMaxG, kWave / mt_pack_dwords(ml) * 4), positions / ml)); };
+        auto lds_of = [&](int grp) {                                                   // + the block's group counter and quad table
+            return wpb * mt_wave_bytes(grp, ml, g->qp_recs, g->fwd_stride) + 16 + mt_quad_table_bytes(grp, ml);
+        };
+        g->grp = group_of(ix->opt_group_positions > 0 ? ix->opt_group_positions : kMtTarget);
+        // kMtTarget2 positions (two full round-1 passes; the slow passes, whose cost is their longest chain, then serve twice the
+        // reads) where the kernel is bound by instruction issue: a compact table of at most half an XCD's L2 (1 MB at 100 kb:
+        // -7 % of the kernel; the 4 MB table of a 1 Mb reference fills the L2, the time follows the misses and the larger
+        // group measured +1.3 %), and only where the larger group's LDS admits as many resident blocks as the register build
+        const bool issue_bound = g->wps != 4 && 2 * table_bytes(ix) <= kTableFitsL2;
+        if (ix->opt_group_positions <= 0 && issue_bound && lds_cap / lds_of(group_of(kMtTarget2)) >= 4 * g->wps / wpb) g->grp = group_of(kMtTarget2);
+        g->lds = lds_of(g->grp);
         per_block = (long long)wpb * g->grp;
     }
     if (g->lds > lds_cap) return GENIE_E_TOO_LONG;
     g->block = wpb * kWave;
-    // waves per SIMD the kernel is built for: 4 (two blocks per CU) where the table exceeds an XCD's L2; else 6 for the compact
-    // table (74 registers, nothing spilled, three blocks per CU: 595-607 us against 609-611 us per 10^6 reads with the
-    // 64-register build and its 10 spilled registers -- the miss queue is full with three blocks' requests) and 8 for the
-    // 32-byte one (on the 16 MB table of a 2.5 Mb reference the six-wave build was no faster than the four-wave one: 6.22 vs 6.10 ms)
-    g->wps = !g->wide && table_bytes(ix) > kTableFitsL2 ? 4 : ((ix->dev.flags & kFlagCompactTable) ? 6 : 8);
     int bpc = std::min(lds_cap / g->lds, 4 * g->wps / wpb);                     // resident blocks per CU
     if (ix->opt_search_blocks_per_cu > 0) bpc = std::min(bpc, ix->opt_search_blocks_per_cu);
     if (bpc < 1) bpc = 1;

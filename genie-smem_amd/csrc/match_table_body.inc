@@ -28,9 +28,14 @@
     int *Ls = reinterpret_cast<int *>(wb + mt_r16(grp * DW * 4));                                  // kMtMaxG
     uint8_t *fwL = reinterpret_cast<uint8_t *>(Ls) + 64;
     uint16_t *sl = reinterpret_cast<uint16_t *>(fwL + mt_r16(grp * FS));
-    uint16_t *qa = reinterpret_cast<uint16_t *>(reinterpret_cast<uint8_t *>(sl) + mt_r16(grp * max_len * 2));
+    uint16_t *qa = reinterpret_cast<uint16_t *>(reinterpret_cast<uint8_t *>(sl) + mt_r16(mt_slow_cap(grp, max_len) * 2));
     uint16_t *qb = qa + grp * mt_quads(max_len);
     for (int i = lane; i < grp * DW; i += kWave) Dp[i] = 0;                    // the zero padding behind every read
+    // The slow list holds mt_slow_cap entries.  Where that is fewer than the group has positions, a lookup pass runs only while
+    // the list has room for all it can add (kMtNsp x 64 entries in round 1, 64 in round 2); otherwise the pending slow passes
+    // run first and empty the list.  That changes no result: a slow item writes its own byte of fwL only, over the provisional
+    // value its lookup pass wrote before; round 2 starts after all of round 1's slow items, and a slow middle puts both its
+    // neighbours on qb whatever it resolves to.  An uncapped list never fills (nslow <= positions = its capacity).
     const uint8_t *reads_end = reads + (RC ? N >> 1 : N) * (long long)stride;
 
     // lane t of the pack pass: dword j of read u
@@ -199,8 +204,16 @@
             }
             // ---- round 1: the first position of every quad
             int nslow = 0;
+            // a 64-entry pass fits the list while nslow <= flush_at; worked out per group (the empty asm keeps it from being hoisted)
+            // so that it is not one more scalar kept across the pack stage: the kernel is at its scalar-register limit
+            int positions = grp * max_len;
+            asm volatile("" : "+s"(positions));
+            const int flush_at = positions > kMtSlowCap ? kMtSlowCap - kWave : 1 << 30;
+            const int n1 = (dbg & 4) ? 0 : nquads;
+            int c0 = 0;
+            do {
 #pragma nounroll
-            for (int c0 = 0; c0 < ((dbg & 4) ? 0 : nquads); c0 += kMtNsp * kWave) {
+            for (; c0 < n1 && nslow + (kMtNsp - 1) * kWave <= flush_at; c0 += kMtNsp * kWave) {
                 uint32_t ent[kMtNsp];                             // read << 28 | fwd-row byte offset << 16 | bases left << 8 | position
                 MtProbe pr[kMtNsp];
 #pragma unroll
@@ -233,15 +246,16 @@
             }
             wave_lds_fence();
 #pragma nounroll
-            for (int c0 = 0; c0 < ((dbg & 1) ? 0 : nslow); c0 += kWave) mt_slow<false, C16>(ix, mtab, ov, mode, lane, c0, nslow, sl, Dp, DW, Ls, fwL, FS);
+            for (int s0 = 0; s0 < ((dbg & 1) ? 0 : nslow); s0 += kWave) mt_slow<false, C16>(ix, mtab, ov, mode, lane, s0, nslow, sl, Dp, DW, Ls, fwL, FS);
             wave_lds_fence();
+            nslow = 0;
+            } while (__builtin_expect(c0 < n1, 0));                                    // more than once only where the list filled up
             // ---- round 2: the other three positions of a quad, looked up only where the quad's sample and the next
             // quad's differ (and the match does not already reach the end of the read): the MIDDLE position first, a
             // neighbour only where the middle leaves it open (fwd[] is non-decreasing: fwd[a+2] == fwd[a] settles a+1,
             // fwd[a+2] == fwd[a+4] or == L settles a+3).  Three passes, each over a DENSE list, so that every lane of a
             // lookup pass has work (a lane per quad with two dependent lookups inside ran at a third of the lanes and
             // three times the instructions per lookup of round 1): the quads to work on, their middles, the neighbours.
-            nslow = 0;
             int nqa = 0, nqb = 0;
             const unsigned long long below = (1ull << lane) - 1ull;
 #pragma nounroll
@@ -263,10 +277,12 @@
             wave_lds_fence();
             // the middles (position a + 2; a + 1 in a quad cut to two positions).  One lookup per lane and pass: the
             // CU's miss queue is full with a fraction of its waves' requests anyway.
+            int cm = 0, cn = 0;                                   // middles and neighbours looked up so far
+            do {
 #pragma nounroll
-            for (int c0 = 0; c0 < nqa; c0 += kWave) {
-                const bool valid = c0 + lane < nqa;
-                const uint32_t it = qa[valid ? c0 + lane : 0];
+            for (; cm < nqa && nslow <= flush_at; cm += kWave) {
+                const bool valid = cm + lane < nqa;
+                const uint32_t it = qa[valid ? cm + lane : 0];
                 const int u = (int)(it >> 8), a = (int)(it & 255u);
                 const int L = Ls[u], m = L - a;                    // m > 1: the quad is on the list
                 const int km = m > 2 ? 2 : 1;
@@ -305,11 +321,11 @@
                 nqb += __popcll(b3);
             }
             wave_lds_fence();
-            // the neighbours (positions a + 1 and a + 3) that the middles left open
+            // the neighbours (positions a + 1 and a + 3) that the middles left open, once all the middles are done
 #pragma nounroll
-            for (int c0 = 0; c0 < nqb; c0 += kWave) {
-                const bool valid = c0 + lane < nqb;
-                const uint32_t it = qb[valid ? c0 + lane : 0];
+            for (; cm >= nqa && cn < nqb && nslow <= flush_at; cn += kWave) {
+                const bool valid = cn + lane < nqb;
+                const uint32_t it = qb[valid ? cn + lane : 0];
                 const int u = (int)(it >> 8), a = (int)(it & 255u);
                 const int m = Ls[u] - a;                           // >= 1
                 const uint32_t o = 2u * (uint32_t)a + 1u;
@@ -329,8 +345,10 @@
             }
             wave_lds_fence();
 #pragma nounroll
-            for (int c0 = 0; c0 < ((dbg & 1) ? 0 : nslow); c0 += kWave) mt_slow<false, C16>(ix, mtab, ov, mode, lane, c0, nslow, sl, Dp, DW, Ls, fwL, FS);
+            for (int s0 = 0; s0 < ((dbg & 1) ? 0 : nslow); s0 += kWave) mt_slow<false, C16>(ix, mtab, ov, mode, lane, s0, nslow, sl, Dp, DW, Ls, fwL, FS);
             wave_lds_fence();
+            nslow = 0;
+            } while (__builtin_expect(cm < nqa || cn < nqb, 0));                       // more than once only where the list filled up
             // ---- results: fwd rows
             const int nrows = N - r < (long long)grp ? (int)(N - r) : grp;
             uint4 *dst = reinterpret_cast<uint4 *>(fwd_out + r * (long long)FS);                  // rows are multiples of 16 bytes

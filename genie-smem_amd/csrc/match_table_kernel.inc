@@ -45,7 +45,9 @@
 // exceeds an XCD's L2 -- fewer waves thrash the L2 less -- and 8 for the 32-byte form.
 constexpr int kMtNsp = 3;          // quads per lane per pass
 constexpr int kMtMaxG = 16;        // reads per wave iteration: chosen by the launch plan, at most this
-constexpr int kMtTarget = 768;     // ... so that a group holds about this many positions (one pass of 3 x 64 quads)
+constexpr int kMtTarget = 768;     // ... so that a group holds about this many positions (one pass of 3 x 64 quads) ...
+constexpr int kMtTarget2 = 1536;   // ... or two full passes, where the larger group costs no resident block (plan_find_smems)
+constexpr int kMtSlowCap = 512;    // entries of the slow list where a group has more positions than that (at least kMtNsp x 64)
 
 
 __host__ __device__ inline int mt_row_dwords(int max_len, int qp_recs)
@@ -64,9 +66,12 @@ __host__ __device__ inline int mt_quad_table_bytes(int grp, int max_len) { retur
 // short reads: the workspace gets the packed read as PLAIN 64-bit words, `chunks` 16-byte pieces of two (chunk j reads the
 // shifted dwords 4j .. 4j+4)
 __host__ __device__ inline int mt_short_row_dwords(int max_len, int chunks) { return mt_row_dwords(max_len, 2 * chunks - 1); }
+// entries of the slow list: one per position of the group -- no list can get longer -- up to kMtSlowCap; a group with more
+// positions than that runs its slow passes whenever the next lookup pass could overflow the list (match_table_body.inc)
+__host__ __device__ inline int mt_slow_cap(int grp, int max_len) { return grp * max_len <= kMtSlowCap ? grp * max_len : kMtSlowCap; }
 __host__ __device__ inline int mt_wave_bytes(int grp, int max_len, int qp_recs, int fwd_stride)
 {
-    return mt_r16(grp * mt_short_row_dwords(max_len, qp_recs) * 4) + 64 + mt_r16(grp * fwd_stride) + mt_r16(grp * max_len * 2) +
+    return mt_r16(grp * mt_short_row_dwords(max_len, qp_recs) * 4) + 64 + mt_r16(grp * fwd_stride) + mt_r16(mt_slow_cap(grp, max_len) * 2) +
            mt_r16(grp * mt_quads(max_len) * 6);          // round 2's lists: the quads to work on (2 B each), their open neighbours (2 x 2 B)
 }
 
