@@ -688,7 +688,7 @@ const char *genie_strerror(int status)
     case GENIE_E_NOMEM: return "out of host memory";
     case GENIE_E_NO_DEVICE: return "index has no device image";
     case GENIE_E_HIP: return "HIP runtime error";
-    case GENIE_E_TOO_LONG: return "read longer than the kernel supports";
+    case GENIE_E_TOO_LONG: return "read or batch larger than the kernels support";
     case GENIE_E_NO_MODEL: return "no RMI model installed";
     case GENIE_E_BAD_BLOB: return "not a serialized GENIE index";
     case GENIE_E_NO_LUT: return "no K-mer table (index built with K = 0, or an image serialized without its seed table)";

@@ -82,10 +82,10 @@ struct LuExactTail {
     {
         const bool direct = max_len <= kEmDirect;
         if (!direct)
-            LAUNCH(lr_pack_kernel, dim3((unsigned)((lr.nwords + 255) / 256)), dim3(256), 0, s, d_bases, uoff, SN, usrc, lr.nwords,
+            LAUNCH_BLOCKS(lr_pack_kernel, (lr.nwords + 255) / 256, 256, 0, s, d_bases, uoff, SN, usrc, lr.nwords,
                    lr.packed, lr.st);
         const auto kernel = direct ? exact_match_kernel<true> : exact_match_kernel<false>;
-        LAUNCH(kernel, dim3((unsigned)((SN + kEmBlock - 1) / kEmBlock)), dim3(kEmBlock), 0, s, ix->dev, d_bases, uoff, usrc, SN,
+        LAUNCH_BLOCKS(kernel, (SN + kEmBlock - 1) / kEmBlock, kEmBlock, 0, s, ix->dev, d_bases, uoff, usrc, SN,
                static_cast<const uint64_t *>(lr.packed), static_cast<const int32_t *>(lr.st), reinterpret_cast<int2 *>(d_lohi),
                d_counts, d_status);
         return GENIE_OK;

@@ -328,7 +328,9 @@ int launch_reads_from_fasta(const uint8_t *d_text, int64_t text_bytes, int32_t f
     FastaArea a;
     fasta_layout(static_cast<uint8_t *>(d_tmp), text_bytes, &a);
     const TrTable table = tr_table(code_of_byte);
-    const dim3 tgrid((unsigned)ntiles), tblock(kTrBlock);
+    const dim3 tblock(kTrBlock);
+    dim3 tgrid;
+    if (int rc = grid_for(ntiles, kTrBlock, &tgrid)) return rc;
     LAUNCH(tr_count_kernel, tgrid, tblock, 0, s, d_text, (long long)text_bytes, lead, a.cnt, a.last);
     LAUNCH(tr_scan_kernel, dim3(1), dim3(kScanBlock), 0, s, a.cnt, a.last, ntiles, (long long)text_bytes, (int)GENIE_TEXT_LINES, partial,
            a.state);

@@ -685,6 +685,41 @@ std::string g_err;
         HIP_TRY(hipGetLastError());                                           \
     } while (0)
 
+// HIP launches gridDim.x * blockDim.x < 2^32 threads (hip_runtime_api.h, hipModuleLaunchKernel).  More is not refused: the
+// launch returns no error and only a part of the grid runs (a dispatch packet holds the grid's size in 32 bits), so nothing
+// here may rely on an error.
+constexpr long long kMaxLaunchThreads = (1ll << 32) - 1;
+
+// The grid of `blocks` blocks of `block` threads, checked: GENIE_E_TOO_LONG where the product reaches 2^32 or the count
+// leaves 32 bits, and another grid would be launched without a word.
+inline int grid_for(long long blocks, int block, dim3 *grid)
+{
+    if (blocks < 0 || blocks > kMaxLaunchThreads / block) return GENIE_E_TOO_LONG;
+    *grid = dim3((unsigned)blocks);
+    return GENIE_OK;
+}
+
+// LAUNCH over a block count of the batch (the CSR paths: 64-bit counts throughout)
+#define LAUNCH_BLOCKS(kernel, blocks, block, lds, stream, ...)                \
+    do {                                                                      \
+        dim3 grid_;                                                           \
+        if (int rc_ = grid_for((blocks), (block), &grid_)) return rc_;        \
+        LAUNCH(kernel, grid_, dim3(block), lds, stream, __VA_ARGS__);         \
+    } while (0)
+
+// A kernel of one block per item (or per few items) whose count may pass that limit.  While the grid fits, which is every
+// ordinary batch, ONE launch of the instance `one`, which ignores its last argument; else slices of blocks through the instance
+// `sliced`, each told its first block there (long long).
+#define LAUNCH_SLICED(one, sliced, blocks, block, lds, stream, ...)           \
+    do {                                                                      \
+        const long long all_ = (blocks), per_ = kMaxLaunchThreads / (block);  \
+        if (all_ <= per_)                                                     \
+            LAUNCH(one, dim3((unsigned)all_), dim3(block), lds, stream, __VA_ARGS__, 0ll); \
+        else                                                                  \
+            for (long long first_ = 0; first_ < all_; first_ += per_)         \
+                LAUNCH(sliced, dim3((unsigned)std::min(per_, all_ - first_)), dim3(block), lds, stream, __VA_ARGS__, first_); \
+    } while (0)
+
 inline long long table_bytes(const genie_index *ix)
 {
     return (long long)((ix->dev.flags & kFlagCompactTable) ? sizeof(MatchRec16) : sizeof(MatchRec)) * ix->dev.mtab_entries;
@@ -1210,10 +1245,10 @@ int launch_compact(const int32_t *d_counts, const int32_t *d_slots, int64_t N, i
     }
     const long long nblocks = (N + kScanBlock - 1) / kScanBlock;
     unsigned long long *sums = reinterpret_cast<unsigned long long *>(d_tmp);
-    LAUNCH(compact_block_sums, dim3((unsigned)nblocks), dim3(kScanBlock), 0, s, d_counts, (long long)N, cap, sums);
+    LAUNCH_BLOCKS(compact_block_sums, nblocks, kScanBlock, 0, s, d_counts, (long long)N, cap, sums);
     LAUNCH(scan_block_sums_kernel, dim3(1), dim3(kScanBlock), 0, s, sums, nblocks);
-    LAUNCH(compact_scatter, dim3((unsigned)nblocks), dim3(kScanBlock), 0, s, d_counts, reinterpret_cast<const int4 *>(d_slots),
-           (long long)N, cap, sums, reinterpret_cast<long long *>(d_offsets), reinterpret_cast<int4 *>(d_out), (long long)out_cap_rows);
+    LAUNCH_BLOCKS(compact_scatter, nblocks, kScanBlock, 0, s, d_counts, reinterpret_cast<const int4 *>(d_slots), (long long)N, cap,
+                  sums, reinterpret_cast<long long *>(d_offsets), reinterpret_cast<int4 *>(d_out), (long long)out_cap_rows);
     return GENIE_OK;
 }
 
@@ -1373,11 +1408,12 @@ int launch_locate(const genie_index *ix, const int32_t *d_lohi, int32_t stride, 
     LocateArea a;
     if (!d_tmp || tmp_bytes < locate_layout(static_cast<uint8_t *>(d_tmp), S, &a) || (reinterpret_cast<uintptr_t>(d_tmp) & 255) != 0)
         return GENIE_E_CAPACITY;
-    const unsigned grid = (unsigned)((S + 255) / 256);
-    LAUNCH(locate_count_kernel, dim3(grid), dim3(256), 0, s, d_lohi, stride, (long long)S, a.counts);
+    dim3 grid;
+    if (int rc = grid_for((S + 255) / 256, 256, &grid)) return rc;
+    LAUNCH(locate_count_kernel, grid, dim3(256), 0, s, d_lohi, stride, (long long)S, a.counts);
     int rc = launch_compact(a.counts, nullptr, S, 0x7FFFFFFF, d_offsets, nullptr, 0, a.scan_tmp, stream);
     if (rc) return rc;
-    LAUNCH(locate_scatter_kernel, dim3(grid), dim3(256), 0, s, ix->dev, d_lohi, stride, (long long)S,
+    LAUNCH(locate_scatter_kernel, grid, dim3(256), 0, s, ix->dev, d_lohi, stride, (long long)S,
            reinterpret_cast<const long long *>(d_offsets), d_positions, (long long)cap);
     return GENIE_OK;
 }

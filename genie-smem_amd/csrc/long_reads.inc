@@ -104,20 +104,23 @@ __global__ void __launch_bounds__(256) lr_pack_kernel(const uint8_t *__restrict_
     packed[g] = w;
 }
 
+// LR2, LR3 and LRM take the first block (LR2) or window (LR3, LRM) of their launch as their last argument: a batch of 2^24
+// windows or more is launched in slices through the SLICED instance (LAUNCH_SLICED); any other batch is one launch of the
+// instance that does not read it, the kernel as it was.
 // MS (the match-statistics tail): fwd[] alone -- wmax and mark are not touched -- and only a bad base stops a window: fwd[]
 // of a unit with an absent base is still wanted, and another window of the unit may have flagged it already.
-template <bool C16, bool MS = false>
+template <bool C16, bool MS = false, bool SLICED = false>
 __global__ void __launch_bounds__(kLrFwdWaves * 64) lr_fwd_kernel(DevIndex ix, int mode, const long long *__restrict__ off, long long N,
                                                                   long long nwin, const uint64_t *__restrict__ packed,
                                                                   int32_t *__restrict__ st, int32_t *__restrict__ fwd,
                                                                   int2 *__restrict__ wmax, uint8_t *__restrict__ mark,
-                                                                  long long mtab_bytes)
+                                                                  long long mtab_bytes, long long block0)
 {
     __shared__ uint16_t lists[kLrFwdWaves][kLrWin];
     __shared__ int32_t rows[kLrFwdWaves][kLrWin];
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = rfl((int)(threadIdx.x >> 6));
-    const long long gw = (long long)blockIdx.x * kLrFwdWaves + wave;
+    const long long gw = (SLICED ? block0 + blockIdx.x : (long long)blockIdx.x) * kLrFwdWaves + wave;
     if (gw >= nwin) return;                                      // wave-uniform; no block-wide barrier below
     const long long r = lr_find(N, gw, [&](long long x) { return lr_wb(off, x); });
     const long long w = gw - lr_wb(off, r);
@@ -186,14 +189,15 @@ __global__ void __launch_bounds__(kLrFwdWaves * 64) lr_fwd_kernel(DevIndex ix, i
     }
 }
 
+template <bool SLICED>
 __global__ void __launch_bounds__(kLrWin) lr_walk_kernel(int mode, int min_len, const long long *__restrict__ off, long long N,
                                                          const int32_t *__restrict__ st, const int32_t *__restrict__ fwd,
                                                          const int2 *__restrict__ wmax, const uint8_t *__restrict__ mark,
-                                                         int32_t *__restrict__ bst, int2 *__restrict__ jc)
+                                                         int32_t *__restrict__ bst, int2 *__restrict__ jc, long long win0)
 {
     __shared__ int sJ[kLrWin], sC[kLrWin];
     __shared__ int32_t sf[2 * kLrWin];                         // fwd of the previous window and this one
-    const long long gw = blockIdx.x;
+    const long long gw = SLICED ? win0 + blockIdx.x : (long long)blockIdx.x;
     const long long r = lr_find(N, gw, [&](long long x) { return lr_wb(off, x); });
     const long long wb = lr_wb(off, r);
     const long long o = off[r], Ll = off[r + 1] - o;
@@ -317,16 +321,16 @@ __device__ __forceinline__ void lr_store_lohi(int2 *dst, int2 iv)
 
 // LRM.  uvirt[u]: the virtual position (long_units.inc) of unit u's first base, where the unit's values go in ms / lohi; null:
 // off[u].  lohi null: lengths only.  A unit with a bad base gets -1 and (-1, -1) everywhere.
-template <bool C16>
+template <bool C16, bool SLICED = false>
 __global__ void __launch_bounds__(kLrWin) lr_ms_kernel(DevIndex ix, const long long *__restrict__ off, long long N,
                                                        const uint64_t *__restrict__ packed, const int32_t *__restrict__ st,
                                                        const int32_t *__restrict__ fwd, const long long *__restrict__ uvirt,
-                                                       int32_t *__restrict__ ms, int2 *__restrict__ lohi)
+                                                       int32_t *__restrict__ ms, int2 *__restrict__ lohi, long long win0)
 {
     __shared__ int32_t slen[kLrWin];
     __shared__ uint16_t slist[kLrWin];                           // the positions the entry does not decide
     __shared__ int nlist;
-    const long long gw = blockIdx.x;
+    const long long gw = SLICED ? win0 + blockIdx.x : (long long)blockIdx.x;
     const long long r = lr_find(N, gw, [&](long long x) { return lr_wb(off, x); });
     const long long w = gw - lr_wb(off, r);
     const long long o = off[r], Ll = off[r + 1] - o;
@@ -425,21 +429,20 @@ int lr_pipeline(const genie_index *ix, int mode, int min_len, const uint8_t *d_b
 {
     HIP_TRY(hipMemsetAsync(a.entry, 0xFF, a.nwin * 4, s));
     if (a.total > 0) HIP_TRY(hipMemsetAsync(a.mark, 0, a.total, s));
-    LAUNCH(lr_pack_kernel, dim3((unsigned)((a.nwords + 255) / 256)), dim3(256), 0, s, d_bases, uoff, U, usrc, a.nwords, a.packed, a.st);
-    const dim3 fgrid((unsigned)((a.nwin + kLrFwdWaves - 1) / kLrFwdWaves)), fblock(kLrFwdWaves * 64);
-    if (ix->dev.flags & kFlagCompactTable)
-        LAUNCH(lr_fwd_kernel<true>, fgrid, fblock, 0, s, ix->dev, mode, uoff, U, a.nwin, a.packed, a.st, a.fwd, a.wmax, a.mark,
-               table_bytes(ix));
-    else
-        LAUNCH(lr_fwd_kernel<false>, fgrid, fblock, 0, s, ix->dev, mode, uoff, U, a.nwin, a.packed, a.st, a.fwd, a.wmax, a.mark,
-               table_bytes(ix));
-    LAUNCH(lr_walk_kernel, dim3((unsigned)a.nwin), dim3(kLrWin), 0, s, mode, min_len, uoff, U, a.st, a.fwd, a.wmax, a.mark, a.bst,
-           a.jc);
-    LAUNCH(lr_chain_kernel, dim3((unsigned)((U + 255) / 256)), dim3(256), 0, s, uoff, U, a.st, a.jc, a.entry, a.base, a.cnt);
+    LAUNCH_BLOCKS(lr_pack_kernel, (a.nwords + 255) / 256, 256, 0, s, d_bases, uoff, U, usrc, a.nwords, a.packed, a.st);
+    const bool c16 = (ix->dev.flags & kFlagCompactTable) != 0;
+    const auto fwd_one = c16 ? lr_fwd_kernel<true> : lr_fwd_kernel<false>;
+    const auto fwd_sliced = c16 ? lr_fwd_kernel<true, false, true> : lr_fwd_kernel<false, false, true>;
+    LAUNCH_SLICED(fwd_one, fwd_sliced, (a.nwin + kLrFwdWaves - 1) / kLrFwdWaves, kLrFwdWaves * 64, 0, s, ix->dev, mode, uoff, U, a.nwin,
+                  static_cast<const uint64_t *>(a.packed), a.st, a.fwd, a.wmax, a.mark, table_bytes(ix));
+    LAUNCH_SLICED(lr_walk_kernel<false>, lr_walk_kernel<true>, a.nwin, kLrWin, 0, s, mode, min_len, uoff, U,
+                  static_cast<const int32_t *>(a.st), static_cast<const int32_t *>(a.fwd), static_cast<const int2 *>(a.wmax),
+                  static_cast<const uint8_t *>(a.mark), a.bst, a.jc);
+    LAUNCH_BLOCKS(lr_chain_kernel, (U + 255) / 256, 256, 0, s, uoff, U, a.st, a.jc, a.entry, a.base, a.cnt);
     int rc = launch_compact(a.cnt, nullptr, U, 0x7fffffff, offsets, nullptr, 0, a.sums, s);
     if (rc) return rc;
-    LAUNCH(lr_emit_kernel, dim3((unsigned)((a.nwin + 255) / 256)), dim3(256), 0, s, ix->dev, mode, min_len, uoff, U, a.nwin, a.packed,
-           a.fwd, a.bst, a.entry, a.base, reinterpret_cast<const long long *>(offsets), ushift, reinterpret_cast<int4 *>(d_rows), cap);
+    LAUNCH_BLOCKS(lr_emit_kernel, (a.nwin + 255) / 256, 256, 0, s, ix->dev, mode, min_len, uoff, U, a.nwin, a.packed, a.fwd, a.bst,
+                  a.entry, a.base, reinterpret_cast<const long long *>(offsets), ushift, reinterpret_cast<int4 *>(d_rows), cap);
     return GENIE_OK;
 }
 
@@ -448,15 +451,17 @@ int lr_pipeline(const genie_index *ix, int mode, int min_len, const uint8_t *d_b
 int lr_match_stats(const genie_index *ix, const uint8_t *d_bases, const LongArea &a, const long long *uoff, long long U,
                    const long long *usrc, const long long *uvirt, int32_t *d_ms, int32_t *d_lohi, hipStream_t s)
 {
-    LAUNCH(lr_pack_kernel, dim3((unsigned)((a.nwords + 255) / 256)), dim3(256), 0, s, d_bases, uoff, U, usrc, a.nwords, a.packed, a.st);
+    LAUNCH_BLOCKS(lr_pack_kernel, (a.nwords + 255) / 256, 256, 0, s, d_bases, uoff, U, usrc, a.nwords, a.packed, a.st);
     const bool c16 = (ix->dev.flags & kFlagCompactTable) != 0;
     const auto fwd_kernel = c16 ? lr_fwd_kernel<true, true> : lr_fwd_kernel<false, true>;
-    LAUNCH(fwd_kernel, dim3((unsigned)((a.nwin + kLrFwdWaves - 1) / kLrFwdWaves)), dim3(kLrFwdWaves * 64), 0, s, ix->dev,
-           (int)GENIE_MODE_BWA, uoff, U, a.nwin, static_cast<const uint64_t *>(a.packed), a.st, a.fwd, static_cast<int2 *>(nullptr),
-           static_cast<uint8_t *>(nullptr), table_bytes(ix));
+    const auto fwd_sliced = c16 ? lr_fwd_kernel<true, true, true> : lr_fwd_kernel<false, true, true>;
+    LAUNCH_SLICED(fwd_kernel, fwd_sliced, (a.nwin + kLrFwdWaves - 1) / kLrFwdWaves, kLrFwdWaves * 64, 0, s, ix->dev, (int)GENIE_MODE_BWA, uoff, U,
+                  a.nwin, static_cast<const uint64_t *>(a.packed), a.st, a.fwd, static_cast<int2 *>(nullptr),
+                  static_cast<uint8_t *>(nullptr), table_bytes(ix));
     const auto ms_kernel = c16 ? lr_ms_kernel<true> : lr_ms_kernel<false>;
-    LAUNCH(ms_kernel, dim3((unsigned)a.nwin), dim3(kLrWin), 0, s, ix->dev, uoff, U, static_cast<const uint64_t *>(a.packed),
-           static_cast<const int32_t *>(a.st), static_cast<const int32_t *>(a.fwd), uvirt, d_ms, reinterpret_cast<int2 *>(d_lohi));
+    const auto ms_sliced = c16 ? lr_ms_kernel<true, true> : lr_ms_kernel<false, true>;
+    LAUNCH_SLICED(ms_kernel, ms_sliced, a.nwin, kLrWin, 0, s, ix->dev, uoff, U, static_cast<const uint64_t *>(a.packed),
+                  static_cast<const int32_t *>(a.st), static_cast<const int32_t *>(a.fwd), uvirt, d_ms, reinterpret_cast<int2 *>(d_lohi));
     return GENIE_OK;
 }
 

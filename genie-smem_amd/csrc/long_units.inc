@@ -358,7 +358,7 @@ int lu_run(const genie_index *ix, int32_t mode, int32_t flags, const uint8_t *d_
     int *const flag = whole.lr.flag;
     long long *const tsrc = S == 2 ? whole.ub : nullptr, *const toff = S == 2 ? whole.uoff : nullptr;
     HIP_TRY(hipMemsetAsync(flag, 0, 8, s));
-    LAUNCH(lu_check_kernel, dim3((unsigned)((N + 1 + 255) / 256)), dim3(256), 0, s, off, (long long)N, (long long)total_bases,
+    LAUNCH_BLOCKS(lu_check_kernel, (N + 1 + 255) / 256, 256, 0, s, off, (long long)N, (long long)total_bases,
            (long long)max_len, mode, ix->dev.K, S, flag, whole.lr.st, tsrc, toff);
     int bad = 0;
     HIP_TRY(hipMemcpyAsync(&bad, flag, 4, hipMemcpyDeviceToHost, s));
@@ -370,7 +370,7 @@ int lu_run(const genie_index *ix, int32_t mode, int32_t flags, const uint8_t *d_
     int *anybreak = flag + 1;
     HIP_TRY(hipMemsetAsync(f.qloc, 0xFF, (SN + 1) * 4, s));
     if (f.nblk > 0)
-        LAUNCH(lu_seg_kernel<false>, dim3((unsigned)f.nblk), dim3(256), 0, s, ix->dev, R, f.bsum, f.qloc, anybreak, 0ll, 0ll,
+        LAUNCH_BLOCKS(lu_seg_kernel<false>, f.nblk, 256, 0, s, ix->dev, R, f.bsum, f.qloc, anybreak, 0ll, 0ll,
                static_cast<long long *>(nullptr), static_cast<long long *>(nullptr));
     LAUNCH(scan_block_sums_kernel, dim3(1), dim3(kScanBlock), 0, s, f.bsum, f.nblk);
     unsigned long long units = 0;
@@ -391,8 +391,8 @@ int lu_run(const genie_index *ix, int32_t mode, int32_t flags, const uint8_t *d_
     for (long long p0 = 0; p0 < U; p0 += C) {
         const long long p1 = std::min(U, p0 + C), Cp = p1 - p0;
         HIP_TRY(hipMemsetAsync(a.lr.st, 0, Cp * 4, s));           // GENIE_READ_OK: a unit holds no break
-        LAUNCH(lu_seg_kernel<true>, dim3((unsigned)f.nblk), dim3(256), 0, s, ix->dev, R, f.bsum, f.qloc, anybreak, p0, p1, a.ua, a.ub);
-        LAUNCH(lu_units_kernel, dim3((unsigned)((Cp + 255) / 256)), dim3(256), 0, s, R, Cp, static_cast<const long long *>(a.ua), a.ub,
+        LAUNCH_BLOCKS(lu_seg_kernel<true>, f.nblk, 256, 0, s, ix->dev, R, f.bsum, f.qloc, anybreak, p0, p1, a.ua, a.ub);
+        LAUNCH_BLOCKS(lu_units_kernel, (Cp + 255) / 256, 256, 0, s, R, Cp, static_cast<const long long *>(a.ua), a.ub,
                a.ulen, a.ushift);
         rc = launch_compact(a.ulen, nullptr, Cp, 0x7fffffff, reinterpret_cast<int64_t *>(a.uoff), nullptr, 0, a.lr.sums, s);
         if (rc) return rc;
@@ -442,7 +442,7 @@ struct LuSmemTail {
         int rc = lr_pipeline(ix, mode, min_len, d_bases, a.lr, a.uoff, Cp, a.ub, a.ushift, reinterpret_cast<int64_t *>(a.loff),
                              cap_left > 0 ? d_rows + 4 * row0 : d_rows, cap_left, s);
         if (rc) return rc;
-        LAUNCH(lu_offsets_kernel, dim3((unsigned)((SN + 1 + 255) / 256)), dim3(256), 0, s, p.R, static_cast<const unsigned long long *>(p.f.bsum),
+        LAUNCH_BLOCKS(lu_offsets_kernel, (SN + 1 + 255) / 256, 256, 0, s, p.R, static_cast<const unsigned long long *>(p.f.bsum),
                static_cast<const int32_t *>(p.f.qloc), p.U, p.p0, p.p1, last, static_cast<const long long *>(a.loff), row0,
                reinterpret_cast<long long *>(d_offsets));
         if (!last) {

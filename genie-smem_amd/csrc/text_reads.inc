@@ -506,7 +506,9 @@ int launch_reads_from_text(const uint8_t *d_text, int64_t text_bytes, int32_t fo
     TextArea a;
     text_layout(static_cast<uint8_t *>(d_tmp), text_bytes, cap_reads, &a);
     const TrTable table = tr_table(code_of_byte);
-    const dim3 tgrid((unsigned)ntiles), tblock(kTrBlock);
+    const dim3 tblock(kTrBlock);
+    dim3 tgrid;
+    if (int rc = grid_for(ntiles, kTrBlock, &tgrid)) return rc;
     LAUNCH(tr_count_kernel, tgrid, tblock, 0, s, d_text, (long long)text_bytes, lead, a.cnt, a.last);
     LAUNCH(tr_scan_kernel, dim3(1), dim3(kScanBlock), 0, s, a.cnt, a.last, ntiles, (long long)text_bytes, (int)format, partial, a.state);
     LAUNCH(tr_length_kernel, tgrid, tblock, 0, s, d_text, (long long)text_bytes, lead, (int)format, partial, a.cnt, a.last, a.state, offs,
@@ -514,9 +516,9 @@ int launch_reads_from_text(const uint8_t *d_text, int64_t text_bytes, int32_t fo
     LAUNCH(tr_reduce_kernel, dim3(1), dim3(kScanBlock), 0, s, a.tile_sum, a.tile_max, ntiles, a.state);
     if (offs) {
         const long long nblocks = tr_scan_blocks(text_bytes, cap_reads);
-        LAUNCH(tr_offsets_block_sums, dim3((unsigned)nblocks), dim3(kScanBlock), 0, s, offs, a.state, (long long)cap_reads, a.sums);
+        LAUNCH_BLOCKS(tr_offsets_block_sums, nblocks, kScanBlock, 0, s, offs, a.state, (long long)cap_reads, a.sums);
         LAUNCH(scan_block_sums_kernel, dim3(1), dim3(kScanBlock), 0, s, a.sums, nblocks);
-        LAUNCH(tr_offsets_apply, dim3((unsigned)nblocks), dim3(kScanBlock), 0, s, offs, a.state, (long long)cap_reads, a.sums);
+        LAUNCH_BLOCKS(tr_offsets_apply, nblocks, kScanBlock, 0, s, offs, a.state, (long long)cap_reads, a.sums);
         LAUNCH(tr_translate_kernel, tgrid, tblock, 0, s, d_text, (long long)text_bytes, lead, (int)format, table, a.cnt, a.last, a.state,
                offs, (long long)cap_reads, d_bases, (long long)cap_bases);
     }

@@ -45,7 +45,8 @@ typedef enum genie_status {
     GENIE_E_NOMEM = -3,
     GENIE_E_NO_DEVICE = -4,    /* index has no device image (call genie_index_open / _to_device) */
     GENIE_E_HIP = -5,          /* HIP runtime error; see genie_last_hip_error() */
-    GENIE_E_TOO_LONG = -6,     /* read/pattern longer than GENIE_MAX_READ_LEN */
+    GENIE_E_TOO_LONG = -6,     /* read/pattern longer than GENIE_MAX_READ_LEN, or a batch beyond what one launch covers
+                                  ("Batch sizes" at genie_find_smems_long) */
     GENIE_E_NO_MODEL = -7,     /* RMI mode requested but no model was set */
     GENIE_E_BAD_BLOB = -8,     /* serialized index: wrong magic / version / size */
     GENIE_E_NO_LUT = -9,       /* LUT mode requested but the index was built with K = 0, or the image has no seed table */
@@ -310,7 +311,16 @@ int genie_find_smems_split(const genie_index *ix, const uint8_t *d_reads, const 
  * d_rows 16-byte aligned; d_workspace 256-byte aligned, genie_find_smems_long_workspace_bytes(N, total_bases, max_len)
  * bytes (GENIE_E_CAPACITY when smaller): about 17.3 bytes per base plus 48 per read.  Argument checks come before the
  * device check.  This call synchronizes `stream` once, after the offset check and before any other kernel runs.
- * Both functions are genie_find_smems_long_ex (below) with flags == 0: the same checks, workspace and launches. */
+ * Both functions are genie_find_smems_long_ex (below) with flags == 0: the same checks, workspace and launches.
+ * Batch sizes, for this call and for genie_find_smems_long_ex, genie_match_stats, genie_exact_match, genie_reads_from_text,
+ * genie_reads_from_fasta and genie_locate: N, total_bases, text_bytes, out_cap_rows, cap_positions and every offset are
+ * 64-bit and are used as such; 2^24 reads, units or windows, 2^31 bases or bytes and 2^32 virtual positions are ordinary
+ * (kernels with one block per 256-position window are launched in slices once a launch would pass HIP's 2^32 threads).
+ * What a single launch still cannot cover returns GENIE_E_TOO_LONG (the outputs are then undefined): 2^32 or more strand-reads,
+ * strand-patterns, units of one pass, intervals or windows (total_bases / 256 + units + 1); 2^32 words of the packed stream
+ * (total_bases / 32 + 3 units + 4); 2^38 virtual positions with GENIE_READS_SPLIT_BREAKS; a text of 2^36 bytes, or one of
+ * 2^32 bytes with cap_reads as large.  The smallest of these (2^32 intervals for genie_locate) takes some 80 GB of caller
+ * buffers. */
 int64_t genie_find_smems_long_workspace_bytes(int64_t N, int64_t total_bases, int64_t max_len);
 int genie_find_smems_long(const genie_index *ix, int32_t mode, const uint8_t *d_bases, const int64_t *d_read_offsets,
                           int64_t N, int64_t total_bases, int64_t max_len, int32_t min_len,
