@@ -30,7 +30,7 @@ OPT_SEARCH_BLOCKS_PER_CU = 6
 OPT_SEARCH_STAGES_OFF = 7
 OPT_SCHEDULING = 8
 READ_OK, READ_BAD_BASE, READ_TOO_SHORT, READ_ABSENT_BASE, READ_OVERFLOW = 0, 1, 2, 3, 4
-READS_BOTH_STRANDS, READS_SPLIT_BREAKS = 1, 2       # flags of genie_find_smems_long_ex, genie_match_stats, genie_exact_match
+READS_BOTH_STRANDS, READS_SPLIT_BREAKS = 1, 2       # flags of genie_find_smems_long_ex, genie_match_stats, genie_exact_match, genie_find_mems
 TEXT_LINES, TEXT_FASTQ = 0, 1                       # formats of genie_reads_from_text
 TEXT_FORMATS = {"lines": TEXT_LINES, "fastq": TEXT_FASTQ}
 TEXT_PARTIAL = 1                                    # its flag
@@ -48,6 +48,7 @@ SYMBOLS = [
     "genie_find_smems_both", "genie_find_smems_both_workspace_bytes",
     "genie_match_stats", "genie_match_stats_workspace_bytes",
     "genie_exact_match", "genie_exact_match_workspace_bytes",
+    "genie_find_mems", "genie_find_mems_workspace_bytes",
     "genie_reads_from_text", "genie_reads_from_text_tmp_bytes",
     "genie_reads_from_fasta", "genie_reads_from_fasta_tmp_bytes",
     "genie_compact_tmp_bytes",
@@ -72,7 +73,7 @@ class GenieError(RuntimeError):
 
 def build(force=False):
     """Compile libgenie_smem.so for gfx950 with hipcc (csrc/Makefile), in-tree."""
-    srcs = [os.path.join(CSRC, f) for f in ("kernels.hip", "index_build.hip", "short_read_kernel.inc", "match_table_kernel.inc", "match_table_body.inc", "match_table_long_body.inc", "split_reads.inc", "long_reads.inc", "long_units.inc", "exact_match.inc", "text_reads.inc", "fasta_reads.inc", "capi.cpp", "index_host.cpp", "genie_internal.h", "Makefile")]
+    srcs = [os.path.join(CSRC, f) for f in ("kernels.hip", "index_build.hip", "short_read_kernel.inc", "match_table_kernel.inc", "match_table_body.inc", "match_table_long_body.inc", "split_reads.inc", "long_reads.inc", "long_units.inc", "exact_match.inc", "mems.inc", "text_reads.inc", "fasta_reads.inc", "capi.cpp", "index_host.cpp", "genie_internal.h", "Makefile")]
     srcs.append(os.path.join(os.path.dirname(_PKG), "include", "genie_smem.h"))
     newest = max(os.path.getmtime(s) for s in srcs)
     if force or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < newest:
@@ -137,6 +138,8 @@ def lib():
         "genie_match_stats_workspace_bytes": (i64, [i64, i64, i64, i32]),
         "genie_exact_match": (C.c_int, [vp, i32, vp, vp, i64, i64, i64, vp, vp, vp, vp, i64, vp]),
         "genie_exact_match_workspace_bytes": (i64, [i64, i64, i64, i32]),
+        "genie_find_mems": (C.c_int, [vp, i32, vp, vp, i64, i64, i64, i32, i32, vp, vp, i64, vp, vp, vp, i64, vp]),
+        "genie_find_mems_workspace_bytes": (i64, [i64, i64, i64, i32]),
         "genie_reads_from_text_tmp_bytes": (i64, [i64, i64]),
         "genie_reads_from_text": (C.c_int, [vp, i64, i32, i32, vp, vp, i64, vp, i64, vp, vp, i64, vp]),
         "genie_reads_from_fasta_tmp_bytes": (i64, [i64, i64]),

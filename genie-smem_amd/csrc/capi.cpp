@@ -493,6 +493,36 @@ int genie_match_stats(const genie_index *ix, int32_t flags, const uint8_t *d_bas
                               workspace_bytes, stream);
 }
 
+int64_t genie_find_mems_workspace_bytes(int64_t N, int64_t total_bases, int64_t max_len, int32_t flags)
+{
+    if (N < 0 || total_bases < 0 || max_len < 0 || max_len > 0x7fffffffll) return (int64_t)GENIE_E_INVALID;
+    if (flags & ~(GENIE_READS_BOTH_STRANDS | GENIE_READS_SPLIT_BREAKS)) return (int64_t)GENIE_E_INVALID;
+    return find_mems_workspace_bytes(N, total_bases, flags);
+}
+
+int genie_find_mems(const genie_index *ix, int32_t flags, const uint8_t *d_bases, const int64_t *d_read_offsets, int64_t N,
+                    int64_t total_bases, int64_t max_len, int32_t min_len, int32_t max_occ, int64_t *d_offsets, int32_t *d_rows,
+                    int64_t out_cap_rows, int32_t *d_status, int64_t *d_totals, void *d_workspace, int64_t workspace_bytes,
+                    void *stream)
+{
+    // argument checks first: they need no device image
+    if (!ix) return GENIE_E_INVALID;
+    if (N < 0 || total_bases < 0 || max_len < 0 || max_len > 0x7fffffffll || out_cap_rows < 0 || workspace_bytes < 0 ||
+        min_len < 1 || max_occ < 0 || !d_offsets || !d_read_offsets || (total_bases > 0 && !d_bases))
+        return GENIE_E_INVALID;
+    if (flags & ~(GENIE_READS_BOTH_STRANDS | GENIE_READS_SPLIT_BREAKS)) return GENIE_E_INVALID;
+    if ((reinterpret_cast<uintptr_t>(d_rows) & 15) != 0 || (reinterpret_cast<uintptr_t>(d_offsets) & 7) != 0 ||
+        (reinterpret_cast<uintptr_t>(d_totals) & 7) != 0 || (reinterpret_cast<uintptr_t>(d_status) & 3) != 0)
+        return GENIE_E_INVALID;
+    if (N > 0 && (!d_workspace || (reinterpret_cast<uintptr_t>(d_workspace) & 255) != 0 ||
+                  workspace_bytes < find_mems_workspace_bytes(N, total_bases, flags)))
+        return GENIE_E_CAPACITY;
+    int rc = ready(ix);
+    if (rc) return rc;
+    return launch_find_mems(ix, flags, d_bases, d_read_offsets, N, total_bases, max_len, min_len, max_occ, d_offsets, d_rows,
+                            out_cap_rows, d_status, d_totals, d_workspace, workspace_bytes, stream);
+}
+
 int64_t genie_exact_match_workspace_bytes(int64_t N, int64_t total_bases, int64_t max_len, int32_t flags)
 {
     if (N < 0 || total_bases < 0 || max_len < 0 || max_len > 0x7fffffffll) return (int64_t)GENIE_E_INVALID;

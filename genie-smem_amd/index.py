@@ -455,6 +455,39 @@ class GenieIndex:
                   _ptr(status), _ptr(ws), ws_bytes)
         return ms, lohi, status
 
+    def find_mems(self, bases, read_offsets, min_len, both_strands=False, split_breaks=False, max_occ=0, rows_hint=None):
+        """Every maximal exact match of at least min_len bases (genie_find_mems) -> (offsets int64[S*N+1], mems
+        int32[R, 4] = (start, end, pos, row), status int32[S*N], skipped int) on the device, S = 2 with both_strands, else
+        1.  bases / read_offsets, the strand-reads, breaks and status as match_stats.  A row says that the strand-read's
+        bases [start, end) equal the reference's from the 1-based position pos on (the suffix of suffix-array row `row`) and
+        that neither side can be extended.  The rows of a strand-read are ordered by (start, row).  max_occ > 0 skips every
+        position whose first min_len bases occur more than max_occ times in the reference; `skipped` counts them.  If the
+        rows outnumber rows_hint the call is made again with room for all."""
+        self._need_device()
+        bases = self._as_dev(bases, torch.uint8).reshape(-1)
+        read_offsets = self._as_dev(read_offsets, torch.int64).reshape(-1)
+        if read_offsets.numel() < 1:
+            raise ValueError("read_offsets needs N + 1 entries")
+        n_reads = read_offsets.numel() - 1
+        total = bases.numel()
+        max_len = int((read_offsets[1:] - read_offsets[:-1]).max().item()) if n_reads else 0
+        max_len = min(max(max_len, 0), 2**31 - 1)
+        flags = (N.READS_BOTH_STRANDS if both_strands else 0) | (N.READS_SPLIT_BREAKS if split_breaks else 0)
+        strands = 2 if both_strands else 1
+        offsets = torch.empty(strands * n_reads + 1, dtype=torch.int64, device=self.device)
+        status = torch.empty(strands * n_reads, dtype=torch.int32, device=self.device)
+        totals = torch.empty(2, dtype=torch.int64, device=self.device)
+        ws, ws_bytes = self._workspace("genie_find_mems_workspace_bytes", n_reads, total, max_len, flags)
+        cap_rows = int(rows_hint) if rows_hint else strands * max(8 * n_reads, total)
+        while True:
+            rows = torch.empty((max(cap_rows, 1), 4), dtype=torch.int32, device=self.device)
+            self._run("genie_find_mems", flags, _ptr(bases), _ptr(read_offsets), n_reads, total, max_len, int(min_len),
+                      int(max_occ), _ptr(offsets), _ptr(rows), rows.shape[0], _ptr(status), _ptr(totals), _ptr(ws), ws_bytes)
+            found, skipped = (int(x) for x in totals.tolist())
+            if found <= rows.shape[0]:
+                return offsets, rows[:found], status, skipped
+            cap_rows = found                      # capacity guess too small: rerun with the exact size
+
     def exact_match(self, bases, pattern_offsets, both_strands=False, counts=False):
         """Suffix-array interval of every pattern of a CSR batch (genie_exact_match) -> (lohi int32[S*N, 2], counts
         int32[S*N] or None without counts=True, status int32[S*N]) on the device, S = 2 with both_strands, else 1.  bases:

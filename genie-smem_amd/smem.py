@@ -161,6 +161,24 @@ class SMEM:
             bases = np.concatenate(enc).astype(np.uint8) if enc else np.zeros(0, np.uint8)
         return ix.match_stats(bases, read_offsets, intervals, both_strands, split_breaks)
 
+    def find_mems(self, reads, minimum_length, both_strands=False, split_breaks=False, max_occ=0):
+        """Every maximal exact match of at least minimum_length bases, with its reference position (genie_find_mems).
+        reads: list[str], or (bases, read_offsets) as match_stats takes them.  -> (offsets int64[S*N+1], mems int32[R, 4] =
+        (start, end, pos, row), status int32[S*N], skipped) on the device: bases [start, end) of the strand-read equal the
+        reference from the 1-based position pos on, and neither side extends; rows of a strand-read by (start, row).
+        max_occ > 0 skips positions whose first minimum_length bases occur more often than that (`skipped` counts them).
+        split_breaks: breaks end a match and flag no read; strings are then encoded with ExactMatch.encode_lenient."""
+        ix = self.matcher.index(self.lut.lut_size)
+        if isinstance(reads, tuple):
+            bases, read_offsets = reads
+        else:
+            encode = self.matcher.encode_lenient if split_breaks else self.matcher.encode
+            enc = [encode(r) for r in reads]
+            read_offsets = np.zeros(len(enc) + 1, np.int64)
+            read_offsets[1:] = np.cumsum([len(e) for e in enc]) if enc else []
+            bases = np.concatenate(enc).astype(np.uint8) if enc else np.zeros(0, np.uint8)
+        return ix.find_mems(bases, read_offsets, minimum_length, both_strands, split_breaks, max_occ)
+
     def match_stats_text(self, data, fmt="lines", intervals=True, both_strands=False, split_breaks=True, fold_case=False):
         """match_stats of the reads in a text (find_smems_text's formats and translation) -> (ms, lohi, status,
         read_offsets): read_offsets int64[N+1] on the device, to index the flat arrays with."""

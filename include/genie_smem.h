@@ -454,6 +454,57 @@ int genie_exact_match(const genie_index *ix, int32_t flags, const uint8_t *d_bas
                       int32_t *d_status,    /* S * N, may be NULL */
                       void *d_workspace, int64_t workspace_bytes, void *stream);
 
+/* Every maximal exact match (MEM) of at least min_len bases of every strand-read, with its reference position: MUMmer's
+ * -maxmatch, the input of chaining and dot-plots.  The SMEM calls report only matches that no other match of the read
+ * contains, and genie_match_stats only the longest match from each position; this call reports every occurrence.
+ * Inputs and flags are those of genie_match_stats: CSR reads of any length, total_bases / max_len as host-side bounds, the
+ * same offset check on the device, GENIE_READS_BOTH_STRANDS and GENIE_READS_SPLIT_BREAKS with the same meanings; S = 2 with
+ * BOTH_STRANDS, else 1; on strand 1 positions are in the reverse complement.
+ * Definition.  The reference T has n bases, a strand-read Q has L, m = min_len >= 1.  A break is a position of Q whose
+ * code is > 3, with SPLIT_BREAKS also one whose base the reference lacks; a break equals nothing.  A MEM is (p, t, l)
+ * with l >= m, Q[p .. p+l) == T[t .. t+l) base for base, no break inside, and
+ *   right-maximal   p + l == L, or t + l == n, or Q[p+l] != T[t+l];
+ *   left-maximal    p == 0, or t == 0, or Q[p-1] != T[t-1].
+ * Output: d_offsets[S N + 1] and int32 rows (start, end, pos, row) = (p, p + l, t + 1, r): pos is 1-based, what
+ * genie_locate returns, and r is the suffix-array row of suffix t.  The rows of a strand-read are ordered by (start
+ * ascending, row ascending), strand-reads are in input order: the output is a function of the inputs alone (no atomic
+ * decides a value).  Rows past out_cap_rows are dropped and d_offsets[S N] keeps the true total; d_rows == NULL is the
+ * sizing call (offsets and totals are written all the same); N = 0 writes d_offsets[0] = 0.
+ *   d_status[S i + s]  (S N int32, may be NULL) what genie_match_stats writes.  Without SPLIT_BREAKS a strand-read flagged
+ *              GENIE_READ_BAD_BASE has no rows; one flagged GENIE_READ_ABSENT_BASE keeps its rows.
+ *   d_totals   (2 int64, may be NULL) {rows in all, positions skipped by max_occ}.
+ *   max_occ    0: no limit.  max_occ > 0: a position whose seed Q[p .. p+m) has more than max_occ occurrences in the
+ *              reference contributes no rows and is counted in d_totals[1].  This bounds the work; it is no seeding policy.
+ * Two consequences: the rows that start at p and are ms[p] long are the rows of genie_match_stats's lohi[p] whose occurrence
+ * is left-maximal; and every row (s, e, lo, hi) of genie_find_smems_long_ex (same flags, BWA mode) with e - s >= m gives a
+ * row (s, e, SA[r] + 1, r) of this call for every r in [lo, hi].
+ * Checked before the device check, so on any handle: a null ix, d_offsets or d_read_offsets, a null d_bases (total_bases >
+ * 0), a negative size, min_len < 1, max_occ < 0, max_len above 2^31 - 1, an unknown flag bit, d_rows not 16-byte, d_offsets
+ * or d_totals not 8-byte or d_status not 4-byte aligned give GENIE_E_INVALID; then, for N > 0, a d_workspace that is null,
+ * not 256-byte aligned or smaller than genie_find_mems_workspace_bytes(N, total_bases, max_len, flags) gives
+ * GENIE_E_CAPACITY.  Bad offsets give GENIE_E_INVALID, found on the device; GENIE_E_TOO_LONG on the single-launch limits of
+ * genie_match_stats.  The workspace function returns GENIE_E_INVALID for arguments the call would refuse, is a multiple of
+ * 256, monotone in N and total_bases, does not depend on max_len and is at least genie_match_stats_workspace_bytes of the
+ * same arguments: that workspace plus 33 S bytes per base (ms 4, lohi 8, the seed's rows 8, the position in its strand-read
+ * 4, the base in front 1, the row offset inside its block 8) and 8 per 64 positions, i.e. about 37.4 S bytes per base and
+ * 28 per read (44 S with both strands; with SPLIT_BREAKS 39.2 S and 64 S).
+ * Synchronisations of `stream`: those of genie_match_stats and no more; the row total stays on the device.
+ * Cost: genie_match_stats with intervals, then per position with ms >= m the rows of its seed -- two directory reads when m
+ * is at most dir_bits, else two bisections of the seed's directory bucket (one 16-byte row per probe, the packed reference
+ * only past dir_bits + 32 bases) --, then twice (count, fill) one suffix-array row and one reference base for EVERY
+ * occurrence of the seed, left-maximal or not: on a repeat-rich reference with a small min_len the call's time is the
+ * number of seed occurrences, which max_occ bounds.  A row outside the longest match's interval costs a word-wise
+ * comparison of two reference suffixes up to its length. */
+int64_t genie_find_mems_workspace_bytes(int64_t N, int64_t total_bases, int64_t max_len, int32_t flags);
+int genie_find_mems(const genie_index *ix, int32_t flags, const uint8_t *d_bases, const int64_t *d_read_offsets,
+                    int64_t N, int64_t total_bases, int64_t max_len, int32_t min_len, int32_t max_occ,
+                    int64_t *d_offsets,      /* S * N + 1 */
+                    int32_t *d_rows,         /* 4 * out_cap_rows, 16-byte aligned; may be NULL: counting only */
+                    int64_t out_cap_rows,
+                    int32_t *d_status,       /* S * N, may be NULL */
+                    int64_t *d_totals,       /* 2, may be NULL: {rows in all, positions skipped by max_occ} */
+                    void *d_workspace, int64_t workspace_bytes, void *stream);
+
 /* Reads from TEXT, on the device: the bytes of a file of reads -> the d_bases / d_read_offsets that genie_find_smems_long_ex
  * takes.  The reference has no counterpart (its reads are Python strings); this replaces encoding every string on the host.
  * Lines.  A line ends at a '\n' (0x0A), which is not part of it; if the line is then not empty and its last byte is '\r',
