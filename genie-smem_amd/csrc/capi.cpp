@@ -523,6 +523,84 @@ int genie_find_mems(const genie_index *ix, int32_t flags, const uint8_t *d_bases
                             out_cap_rows, d_status, d_totals, d_workspace, workspace_bytes, stream);
 }
 
+// A contig table as an argument: present, 8-byte aligned, at least one contig and no more than an int counts
+static int contig_args(const int64_t *d_contig_offsets, int64_t n_contigs)
+{
+    if (!d_contig_offsets || n_contigs < 1 || (reinterpret_cast<uintptr_t>(d_contig_offsets) & 7) != 0) return GENIE_E_INVALID;
+    return n_contigs > 0x7ffffffell ? GENIE_E_TOO_LONG : GENIE_OK;
+}
+
+int genie_contigs_validate(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs, void *stream)
+{
+    if (!ix) return GENIE_E_INVALID;
+    int rc = contig_args(d_contig_offsets, n_contigs);
+    if (rc || (rc = ready(ix))) return rc;
+    return contigs_validate(ix, d_contig_offsets, n_contigs, stream);
+}
+
+int64_t genie_find_mems_contigs_workspace_bytes(int64_t N, int64_t total_bases, int64_t max_len, int32_t flags, int64_t n_contigs)
+{
+    if (n_contigs < 1 || n_contigs > 0x7ffffffell) return (int64_t)GENIE_E_INVALID;
+    const int64_t parent = genie_find_mems_workspace_bytes(N, total_bases, max_len, flags);
+    return parent < 0 ? parent : find_mems_contigs_workspace_bytes(N, total_bases, flags, n_contigs);
+}
+
+int genie_find_mems_contigs(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs, int32_t flags,
+                            const uint8_t *d_bases, const int64_t *d_read_offsets, int64_t N, int64_t total_bases, int64_t max_len,
+                            int32_t min_len, int32_t max_occ, int64_t *d_offsets, int32_t *d_rows, int64_t out_cap_rows,
+                            int32_t *d_status, int64_t *d_totals, void *d_workspace, int64_t workspace_bytes, void *stream)
+{
+    // argument checks first: they need no device image
+    if (!ix) return GENIE_E_INVALID;
+    if (N < 0 || total_bases < 0 || max_len < 0 || max_len > 0x7fffffffll || out_cap_rows < 0 || workspace_bytes < 0 ||
+        min_len < 1 || max_occ < 0 || !d_offsets || !d_read_offsets || (total_bases > 0 && !d_bases))
+        return GENIE_E_INVALID;
+    if (flags & ~(GENIE_READS_BOTH_STRANDS | GENIE_READS_SPLIT_BREAKS)) return GENIE_E_INVALID;
+    if ((reinterpret_cast<uintptr_t>(d_rows) & 15) != 0 || (reinterpret_cast<uintptr_t>(d_offsets) & 7) != 0 ||
+        (reinterpret_cast<uintptr_t>(d_totals) & 7) != 0 || (reinterpret_cast<uintptr_t>(d_status) & 3) != 0)
+        return GENIE_E_INVALID;
+    int rc = contig_args(d_contig_offsets, n_contigs);
+    if (rc) return rc;
+    if (N > 0 && (!d_workspace || (reinterpret_cast<uintptr_t>(d_workspace) & 255) != 0 ||
+                  workspace_bytes < find_mems_contigs_workspace_bytes(N, total_bases, flags, n_contigs)))
+        return GENIE_E_CAPACITY;
+    if ((rc = ready(ix))) return rc;
+    return launch_find_mems_contigs(ix, d_contig_offsets, n_contigs, flags, d_bases, d_read_offsets, N, total_bases, max_len, min_len,
+                                    max_occ, d_offsets, d_rows, out_cap_rows, d_status, d_totals, d_workspace, workspace_bytes, stream);
+}
+
+int64_t genie_locate_contigs_tmp_bytes(int64_t S) { return S < 0 ? (int64_t)GENIE_E_INVALID : locate_contigs_tmp_bytes(S); }
+
+int genie_locate_contigs(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs, const int32_t *d_rows, int64_t S,
+                         int64_t *d_hit_offsets, int32_t *d_hits, int64_t cap_hits, int64_t *d_totals, void *d_tmp, int64_t tmp_bytes,
+                         void *stream)
+{
+    // argument checks first: they need no device image
+    if (!ix) return GENIE_E_INVALID;
+    if (S < 0 || cap_hits < 0 || tmp_bytes < 0 || !d_hit_offsets || (S > 0 && !d_rows)) return GENIE_E_INVALID;
+    if ((reinterpret_cast<uintptr_t>(d_rows) & 15) != 0 || (reinterpret_cast<uintptr_t>(d_hits) & 7) != 0 ||
+        (reinterpret_cast<uintptr_t>(d_hit_offsets) & 7) != 0 || (reinterpret_cast<uintptr_t>(d_totals) & 7) != 0)
+        return GENIE_E_INVALID;
+    int rc = contig_args(d_contig_offsets, n_contigs);
+    if (rc) return rc;
+    if (S > 0 && (!d_tmp || (reinterpret_cast<uintptr_t>(d_tmp) & 255) != 0 || tmp_bytes < locate_contigs_tmp_bytes(S)))
+        return GENIE_E_CAPACITY;
+    if ((rc = ready(ix))) return rc;
+    return launch_locate_contigs(ix, d_contig_offsets, n_contigs, d_rows, S, d_hit_offsets, d_hits, cap_hits, d_totals, d_tmp, stream);
+}
+
+int genie_contig_coords(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs, const int32_t *d_pos, int32_t stride,
+                        int64_t count, int32_t *d_out, void *stream)
+{
+    // argument checks first: they need no device image
+    if (!ix) return GENIE_E_INVALID;
+    if (count < 0 || stride < 1 || (count > 0 && (!d_pos || !d_out))) return GENIE_E_INVALID;
+    if (((reinterpret_cast<uintptr_t>(d_pos) | reinterpret_cast<uintptr_t>(d_out)) & 3) != 0) return GENIE_E_INVALID;
+    int rc = contig_args(d_contig_offsets, n_contigs);
+    if (rc || (rc = ready(ix))) return rc;
+    return launch_contig_coords(ix, d_contig_offsets, n_contigs, d_pos, stride, count, d_out, stream);
+}
+
 int64_t genie_exact_match_workspace_bytes(int64_t N, int64_t total_bases, int64_t max_len, int32_t flags)
 {
     if (N < 0 || total_bases < 0 || max_len < 0 || max_len > 0x7fffffffll) return (int64_t)GENIE_E_INVALID;

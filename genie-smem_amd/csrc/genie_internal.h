@@ -399,6 +399,18 @@ int64_t find_mems_workspace_bytes(int64_t N, int64_t total_bases, int32_t flags)
 int launch_find_mems(const genie_index *ix, int32_t flags, const uint8_t *d_bases, const int64_t *d_read_offsets, int64_t N,
                      int64_t total_bases, int64_t max_len, int32_t min_len, int32_t max_occ, int64_t *d_offsets, int32_t *d_rows,
                      int64_t out_cap_rows, int32_t *d_status, int64_t *d_totals, void *d_ws, int64_t ws_bytes, void *stream);
+// contigs.inc, mems.inc: a reference of several sequences
+int contigs_validate(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs, void *stream);
+int launch_contig_coords(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs, const int32_t *d_pos, int32_t stride,
+                         int64_t count, int32_t *d_out, void *stream);
+int64_t locate_contigs_tmp_bytes(int64_t S);
+int launch_locate_contigs(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs, const int32_t *d_rows, int64_t S,
+                          int64_t *d_hit_offsets, int32_t *d_hits, int64_t cap_hits, int64_t *d_totals, void *d_tmp, void *stream);
+int64_t find_mems_contigs_workspace_bytes(int64_t N, int64_t total_bases, int32_t flags, int64_t n_contigs);
+int launch_find_mems_contigs(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs, int32_t flags,
+                             const uint8_t *d_bases, const int64_t *d_read_offsets, int64_t N, int64_t total_bases, int64_t max_len,
+                             int32_t min_len, int32_t max_occ, int64_t *d_offsets, int32_t *d_rows, int64_t out_cap_rows,
+                             int32_t *d_status, int64_t *d_totals, void *d_ws, int64_t ws_bytes, void *stream);
 int64_t reads_from_text_tmp_bytes(int64_t text_bytes, int64_t cap_reads);
 int launch_reads_from_text(const uint8_t *d_text, int64_t text_bytes, int32_t format, int32_t flags, const uint8_t *code_of_byte,
                            uint8_t *d_bases, int64_t cap_bases, int64_t *d_read_offsets, int64_t cap_reads, int64_t *out5,

@@ -30,6 +30,9 @@
 //                           while that is below out_cap_rows.  Rows of a position are in row order, positions in their own
 //                           order: no atomic decides a value (one integer atomicAdd per block sums the skipped positions).
 // Kernels of one block per window are launched in slices (LAUNCH_SLICED), as lr_ms_kernel is.
+// genie_find_mems_contigs (a reference of several sequences, contigs.inc) is the same call with the CONTIGS instances of the
+// walks: per occurrence one lookup of t in the contig table; an occurrence with less room than m to its contig's end is no
+// row, a contig start is a left end, and a row's length is clipped to the room.  MEM1, the scan and MEM3 do not change.
 namespace {
 
 constexpr int kMemWin = 256;              // virtual positions per block
@@ -210,21 +213,33 @@ struct MemPos {
     uint32_t pc;                          // base in front, 4 = none
 };
 
-// Is the occurrence at row r left-maximal?  Its start (0-based) goes to t.
-__device__ __forceinline__ bool mem_left_maximal(const DevIndex &ix, int r, uint32_t pc, int &t)
+// Is the occurrence at row r left-maximal?  Its start (0-based) goes to t.  CONTIGS: its room (the bases from t to the end
+// of its contig) goes to room; an occurrence with less room than m is no row at all, and a contig start is a left end.
+template <bool CONTIGS>
+__device__ __forceinline__ bool mem_left_maximal(const DevIndex &ix, const CtgTab &cg, const int *__restrict__ cs, int m, int r,
+                                                 uint32_t pc, int &t, int &room)
 {
     t = ix.sa[r].s;
+    if (CONTIGS) {
+        const CtgHit h = ctg_find(cg, cs, ix.n, t);
+        room = h.room;
+        if (room < m) return false;
+        return pc > 3u || t == 0 || t == h.start || mem_ref_base(ix, t - 1) != pc;
+    }
     return pc > 3u || t == 0 || mem_ref_base(ix, t - 1) != pc;
 }
 
-// The row (start, end, pos, row) of a left-maximal occurrence; s0 = the start of row llo, loaded on first use (-1: not yet)
-__device__ __forceinline__ int4 mem_row(const DevIndex &ix, const MemPos &q, int r, int t, int &s0)
+// The row (start, end, pos, row) of a left-maximal occurrence; s0 = the start of row llo, loaded on first use (-1: not yet).
+// CONTIGS: the length is clipped to room >= m.
+template <bool CONTIGS>
+__device__ __forceinline__ int4 mem_row(const DevIndex &ix, const MemPos &q, int r, int t, int &s0, int room)
 {
     int l = q.ms;
     if (r < q.llo || r > q.lhi) {
         if (s0 < 0) s0 = ix.sa[q.llo].s;
         const int far = ix.n - (t > s0 ? t : s0);
-        const int lim = far < q.ms ? far : q.ms;
+        int lim = far < q.ms ? far : q.ms;
+        if (CONTIGS) lim = lim < room ? lim : room;
         l = q.m;
         while (l < lim) {
             const uint64_t x = rwin(ix.ref, t + l) ^ rwin(ix.ref, s0 + l);
@@ -232,13 +247,15 @@ __device__ __forceinline__ int4 mem_row(const DevIndex &ix, const MemPos &q, int
             l += 32;
         }
         l = l < lim ? l : lim;
+    } else if (CONTIGS) {
+        l = l < room ? l : room;
     }
     return make_int4(q.p, q.p + l, t + 1, r);
 }
 
 // MEM2 (FILL false) / MEM4
-template <bool FILL>
-__global__ void __launch_bounds__(kMemWalk) mem_walk_kernel(DevIndex ix, long long positions, int m, const int32_t *__restrict__ ms,
+template <bool FILL, bool CONTIGS>
+__global__ void __launch_bounds__(kMemWalk) mem_walk_kernel(DevIndex ix, CtgPair cgs, long long positions, int m, const int32_t *__restrict__ ms,
                                                             const int2 *__restrict__ lohi, const int2 *__restrict__ seed,
                                                             const int32_t *__restrict__ pos, const uint8_t *__restrict__ prev,
                                                             unsigned long long *__restrict__ pre, unsigned long long *__restrict__ kept,
@@ -246,6 +263,8 @@ __global__ void __launch_bounds__(kMemWalk) mem_walk_kernel(DevIndex ix, long lo
                                                             long long cap, long long win0)
 {
     __shared__ unsigned long long wtot[kMemWalk / kWave];
+    extern __shared__ int ctg_lds[];                             // CONTIGS: the staged samples of the contig table
+    __shared__ unsigned int ctg_occ;                             // CONTIGS: the seed rows of the block's positions (saturating)
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
     const long long win = win0 + blockIdx.x, v = win * kMemWalk + threadIdx.x;
     MemPos q{0, 0, 0, -1, 0, m, 0, 4u};
@@ -265,14 +284,34 @@ __global__ void __launch_bounds__(kMemWalk) mem_walk_kernel(DevIndex ix, long lo
             off = (long long)(bsum[win] + pre[v]);
         }
     }
+    // CONTIGS.  Staging costs a block one load per sample, a lookup one load per level left below the samples.  Where the
+    // table has more entries than the small staging holds (4 KB), a block whose positions have at least as many seed rows as
+    // the large staging has samples takes that one (up to 48 KB), any other the small one, and a block without seed rows
+    // none.  Count and fill see the same rows and choose alike.  A smaller table is staged whole, without the count.
+    CtgTab cg = cgs.small;
+    if (CONTIGS) {
+        unsigned int occ = 1;
+        if (cgs.big.ns != cgs.small.ns) {
+            if (threadIdx.x == 0) ctg_occ = 0;
+            __syncthreads();
+            occ = (unsigned int)(q.cnt < (1 << 20) ? q.cnt : (1 << 20));
+#pragma unroll
+            for (int o = kWave / 2; o > 0; o >>= 1) occ += (unsigned int)__shfl_xor((int)occ, o);
+            if (lane == 0 && occ) atomicAdd(&ctg_occ, occ);      // an integer sum: any order gives the same value
+            __syncthreads();
+            occ = ctg_occ;
+            if (occ >= (unsigned int)cgs.big.ns) cg = cgs.big;
+        }
+        if (occ) ctg_stage(cg, ix.n, ctg_lds);
+    }
     const bool wide = q.cnt > kMemLaneRows;
     unsigned long long n = 0;
     if (!wide) {
         int s0 = -1;
         for (int i = 0; i < q.cnt; i++) {
-            int t;
-            if (!mem_left_maximal(ix, q.lo + i, q.pc, t)) continue;
-            if (FILL && off + (long long)n < cap) rows[off + (long long)n] = mem_row(ix, q, q.lo + i, t, s0);
+            int t, room = 0;
+            if (!mem_left_maximal<CONTIGS>(ix, cg, ctg_lds, m, q.lo + i, q.pc, t, room)) continue;
+            if (FILL && off + (long long)n < cap) rows[off + (long long)n] = mem_row<CONTIGS>(ix, q, q.lo + i, t, s0, room);
             n++;
         }
     }
@@ -297,12 +336,12 @@ __global__ void __launch_bounds__(kMemWalk) mem_walk_kernel(DevIndex ix, long lo
         int s0 = -1;
         for (int i0 = 0; i0 < b.cnt; i0 += kWave) {              // wave-uniform trip count
             const int i = i0 + lane;
-            int t = 0;
-            const bool lm = i < b.cnt && mem_left_maximal(ix, b.lo + i, b.pc, t);
+            int t = 0, room = 0;
+            const bool lm = i < b.cnt && mem_left_maximal<CONTIGS>(ix, cg, ctg_lds, m, b.lo + i, b.pc, t, room);
             const unsigned long long mask = __ballot(lm);
             if (FILL && lm) {
                 const long long at = boff + (long long)seen + __popcll(mask & ((1ull << lane) - 1ull));
-                if (at < cap) rows[at] = mem_row(ix, b, b.lo + i, t, s0);
+                if (at < cap) rows[at] = mem_row<CONTIGS>(ix, b, b.lo + i, t, s0, room);
             }
             seen += (unsigned long long)__popcll(mask);
         }
@@ -364,9 +403,11 @@ int64_t find_mems_workspace_bytes(int64_t N, int64_t total_bases, int32_t flags)
     return mem_layout(nullptr, N, total_bases, flags, &a);
 }
 
-int launch_find_mems(const genie_index *ix, int32_t flags, const uint8_t *d_bases, const int64_t *d_read_offsets, int64_t N,
-                     int64_t total_bases, int64_t max_len, int32_t min_len, int32_t max_occ, int64_t *d_offsets, int32_t *d_rows,
-                     int64_t out_cap_rows, int32_t *d_status, int64_t *d_totals, void *d_ws, int64_t ws_bytes, void *stream)
+// cg == nullptr: genie_find_mems; else genie_find_mems_contigs, whose walks run the CONTIGS instances
+static int find_mems_any(const genie_index *ix, const CtgPair *cg, int32_t flags, const uint8_t *d_bases, const int64_t *d_read_offsets,
+                         int64_t N, int64_t total_bases, int64_t max_len, int32_t min_len, int32_t max_occ, int64_t *d_offsets,
+                         int32_t *d_rows, int64_t out_cap_rows, int32_t *d_status, int64_t *d_totals, void *d_ws, int64_t ws_bytes,
+                         void *stream)
 {
     hipStream_t s = (hipStream_t)stream;
     if (N == 0) {
@@ -383,11 +424,15 @@ int launch_find_mems(const genie_index *ix, int32_t flags, const uint8_t *d_base
                                 d_status, a.stats, stats_bytes, stream);
     if (rc) return rc;
     const LuReads R{d_bases, reinterpret_cast<const long long *>(d_read_offsets), (long long)N, S};
+    const CtgPair tab = cg ? *cg : CtgPair{{nullptr, 0, 0, 0}, {nullptr, 0, 0, 0}};
+    const size_t lds = cg ? ctg_lds_bytes(tab.big) : 0;
+    auto count_k = cg ? mem_walk_kernel<false, true> : mem_walk_kernel<false, false>;
+    auto fill_k = cg ? mem_walk_kernel<true, true> : mem_walk_kernel<true, false>;
     HIP_TRY(hipMemsetAsync(a.skipped, 0, 8, s));
     if (a.nwin > 0) {
         LAUNCH_SLICED(mem_seed_kernel, mem_seed_kernel, a.nwin, kMemWin, 0, s, ix->dev, R, positions, (int)min_len, (int)max_occ,
                       static_cast<const int32_t *>(a.ms), static_cast<const int2 *>(a.lohi), a.seed, a.pos, a.prev, a.skipped);
-        LAUNCH_SLICED(mem_walk_kernel<false>, mem_walk_kernel<false>, a.nwalk, kMemWalk, 0, s, ix->dev, positions, (int)min_len,
+        LAUNCH_SLICED(count_k, count_k, a.nwalk, kMemWalk, lds, s, ix->dev, tab, positions, (int)min_len,
                       static_cast<const int32_t *>(a.ms), static_cast<const int2 *>(a.lohi), static_cast<const int2 *>(a.seed),
                       static_cast<const int32_t *>(a.pos), static_cast<const uint8_t *>(a.prev), a.pre, a.kept, a.bsum,
                       static_cast<int4 *>(nullptr), 0ll);
@@ -398,9 +443,34 @@ int launch_find_mems(const genie_index *ix, int32_t flags, const uint8_t *d_base
                   static_cast<const unsigned long long *>(a.skipped), reinterpret_cast<long long *>(d_offsets),
                   reinterpret_cast<long long *>(d_totals));
     if (d_rows && out_cap_rows > 0 && a.nwin > 0)
-        LAUNCH_SLICED(mem_walk_kernel<true>, mem_walk_kernel<true>, a.nwalk, kMemWalk, 0, s, ix->dev, positions, (int)min_len,
+        LAUNCH_SLICED(fill_k, fill_k, a.nwalk, kMemWalk, lds, s, ix->dev, tab, positions, (int)min_len,
                       static_cast<const int32_t *>(a.ms), static_cast<const int2 *>(a.lohi), static_cast<const int2 *>(a.seed),
                       static_cast<const int32_t *>(a.pos), static_cast<const uint8_t *>(a.prev), a.pre, a.kept, a.bsum,
                       reinterpret_cast<int4 *>(d_rows), (long long)out_cap_rows);
     return GENIE_OK;
+}
+
+int launch_find_mems(const genie_index *ix, int32_t flags, const uint8_t *d_bases, const int64_t *d_read_offsets, int64_t N,
+                     int64_t total_bases, int64_t max_len, int32_t min_len, int32_t max_occ, int64_t *d_offsets, int32_t *d_rows,
+                     int64_t out_cap_rows, int32_t *d_status, int64_t *d_totals, void *d_ws, int64_t ws_bytes, void *stream)
+{
+    return find_mems_any(ix, nullptr, flags, d_bases, d_read_offsets, N, total_bases, max_len, min_len, max_occ, d_offsets, d_rows,
+                         out_cap_rows, d_status, d_totals, d_ws, ws_bytes, stream);
+}
+
+// The table is the caller's and the samples live in LDS: the workspace is the parent's
+int64_t find_mems_contigs_workspace_bytes(int64_t N, int64_t total_bases, int32_t flags, int64_t n_contigs)
+{
+    (void)n_contigs;
+    return find_mems_workspace_bytes(N, total_bases, flags);
+}
+
+int launch_find_mems_contigs(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs, int32_t flags,
+                             const uint8_t *d_bases, const int64_t *d_read_offsets, int64_t N, int64_t total_bases, int64_t max_len,
+                             int32_t min_len, int32_t max_occ, int64_t *d_offsets, int32_t *d_rows, int64_t out_cap_rows,
+                             int32_t *d_status, int64_t *d_totals, void *d_ws, int64_t ws_bytes, void *stream)
+{
+    const CtgPair tab{ctg_tab(d_contig_offsets, n_contigs, kCtgWalkSamples), ctg_tab(d_contig_offsets, n_contigs, kCtgSamples)};
+    return find_mems_any(ix, &tab, flags, d_bases, d_read_offsets, N, total_bases, max_len, min_len, max_occ, d_offsets, d_rows,
+                         out_cap_rows, d_status, d_totals, d_ws, ws_bytes, stream);
 }

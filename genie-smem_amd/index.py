@@ -463,6 +463,11 @@ class GenieIndex:
         that neither side can be extended.  The rows of a strand-read are ordered by (start, row).  max_occ > 0 skips every
         position whose first min_len bases occur more than max_occ times in the reference; `skipped` counts them.  If the
         rows outnumber rows_hint the call is made again with room for all."""
+        return self._find_mems("genie_find_mems", (), (), bases, read_offsets, min_len, both_strands, split_breaks, max_occ, rows_hint)
+
+    def _find_mems(self, name, table, size_tail, bases, read_offsets, min_len, both_strands, split_breaks, max_occ, rows_hint):
+        """genie_find_mems or genie_find_mems_contigs: `table` are the arguments between the handle and the flags,
+        `size_tail` those the workspace function takes behind the flags."""
         self._need_device()
         bases = self._as_dev(bases, torch.uint8).reshape(-1)
         read_offsets = self._as_dev(read_offsets, torch.int64).reshape(-1)
@@ -477,16 +482,68 @@ class GenieIndex:
         offsets = torch.empty(strands * n_reads + 1, dtype=torch.int64, device=self.device)
         status = torch.empty(strands * n_reads, dtype=torch.int32, device=self.device)
         totals = torch.empty(2, dtype=torch.int64, device=self.device)
-        ws, ws_bytes = self._workspace("genie_find_mems_workspace_bytes", n_reads, total, max_len, flags)
+        ws, ws_bytes = self._workspace(name + "_workspace_bytes", n_reads, total, max_len, flags, *size_tail)
         cap_rows = int(rows_hint) if rows_hint else strands * max(8 * n_reads, total)
         while True:
             rows = torch.empty((max(cap_rows, 1), 4), dtype=torch.int32, device=self.device)
-            self._run("genie_find_mems", flags, _ptr(bases), _ptr(read_offsets), n_reads, total, max_len, int(min_len),
+            self._run(name, *table, flags, _ptr(bases), _ptr(read_offsets), n_reads, total, max_len, int(min_len),
                       int(max_occ), _ptr(offsets), _ptr(rows), rows.shape[0], _ptr(status), _ptr(totals), _ptr(ws), ws_bytes)
             found, skipped = (int(x) for x in totals.tolist())
             if found <= rows.shape[0]:
                 return offsets, rows[:found], status, skipped
             cap_rows = found                      # capacity guess too small: rerun with the exact size
+
+    def _contig_table(self, contigs):
+        """The (pointer, count) of a ReferenceSet's table on this index's device; it must be the table of this reference."""
+        self._need_device()
+        off = contigs.device_offsets(self.device)
+        if int(contigs.offsets[-1]) != self.n:
+            raise ValueError(f"the contig table ends at {int(contigs.offsets[-1])}, the index holds {self.n} bases")
+        return off, (_ptr(off), off.numel() - 1)
+
+    def find_mems_contigs(self, contigs, bases, read_offsets, min_len, both_strands=False, split_breaks=False, max_occ=0,
+                          rows_hint=None):
+        """find_mems on a reference of several sequences (genie_find_mems_contigs; contigs: the ReferenceSet this index was
+        built from).  The same four results; a row lies inside one contig: matches are cut at the contig boundaries, a
+        contig start is a left end, and what is left of an occurrence with fewer than min_len bases to its contig's end is
+        no row.  pos stays 1-based in the concatenation (contig_coords names it); max_occ counts occurrences in the
+        concatenation.  If the rows outnumber rows_hint the call is made again with room for all."""
+        off, table = self._contig_table(contigs)
+        return self._find_mems("genie_find_mems_contigs", table, (table[1],), bases, read_offsets, min_len, both_strands,
+                               split_breaks, max_occ, rows_hint)
+
+    def locate_contigs(self, contigs, rows):
+        """SMEM rows int32 [S, 4] (start, end, lo, hi) of any find_smems* call -> (hit_offsets int64[S+1], hits int32[T, 2]
+        = (contig, 1-based offset inside it), dropped) (genie_locate_contigs).  The rows stay SMEMs of the concatenation;
+        this drops the occurrences that bridge two sequences (`dropped` counts them), BWA's rule.  Hits of a row are in
+        suffix-array row order."""
+        off, table = self._contig_table(contigs)
+        rows = self._as_dev(rows, torch.int32)
+        if rows.dim() != 2 or rows.shape[1] != 4:
+            raise ValueError("rows must be [S, 4] (start, end, lo, hi)")
+        S = rows.shape[0]
+        offsets = torch.empty(S + 1, dtype=torch.int64, device=self.device)
+        totals = torch.empty(2, dtype=torch.int64, device=self.device)
+        tmp, tmp_bytes = self._workspace("genie_locate_contigs_tmp_bytes", S)
+        self._run("genie_locate_contigs", *table, _ptr(rows), S, _ptr(offsets), C.c_void_p(0), 0, _ptr(totals), _ptr(tmp), tmp_bytes)
+        kept, dropped = (int(x) for x in totals.tolist())
+        hits = torch.empty((max(kept, 1), 2), dtype=torch.int32, device=self.device)
+        self._run("genie_locate_contigs", *table, _ptr(rows), S, _ptr(offsets), _ptr(hits), kept, _ptr(totals), _ptr(tmp), tmp_bytes)
+        return offsets, hits[:kept], dropped
+
+    def contig_coords(self, contigs, pos, stride=1):
+        """1-based concatenation positions -> int32 [count, 2] = (contig, 1-based offset inside it) on the device
+        (genie_contig_coords); (-1, -1) for a position outside [1, n].  pos: int32, flat; with stride > 1 every stride-th
+        element from the first on is taken (stride 4 on find_mems rows [R, 4][:, 2:] -- or simply pass rows[:, 2])."""
+        off, table = self._contig_table(contigs)
+        pos = self._as_dev(pos, torch.int32).reshape(-1)
+        stride = int(stride)
+        if stride < 1:
+            raise ValueError("stride must be at least 1")
+        count = (pos.numel() + stride - 1) // stride
+        out = torch.empty((count, 2), dtype=torch.int32, device=self.device)
+        self._run("genie_contig_coords", *table, _ptr(pos), stride, count, _ptr(out))
+        return out
 
     def exact_match(self, bases, pattern_offsets, both_strands=False, counts=False):
         """Suffix-array interval of every pattern of a CSR batch (genie_exact_match) -> (lohi int32[S*N, 2], counts

@@ -179,6 +179,27 @@ class SMEM:
             bases = np.concatenate(enc).astype(np.uint8) if enc else np.zeros(0, np.uint8)
         return ix.find_mems(bases, read_offsets, minimum_length, both_strands, split_breaks, max_occ)
 
+    def find_mems_contigs(self, contigs, reads, minimum_length, both_strands=False, split_breaks=False, max_occ=0):
+        """find_mems on a reference of several sequences (genie_find_mems_contigs): contigs is the ReferenceSet whose
+        concatenation this matcher's reference is.  reads and the four results as find_mems; every row lies inside one
+        contig (GenieIndex.find_mems_contigs), pos is 1-based in the concatenation (contigs.coords names it)."""
+        ix = self.matcher.index(self.lut.lut_size)
+        if isinstance(reads, tuple):
+            bases, read_offsets = reads
+        else:
+            encode = self.matcher.encode_lenient if split_breaks else self.matcher.encode
+            enc = [encode(r) for r in reads]
+            read_offsets = np.zeros(len(enc) + 1, np.int64)
+            read_offsets[1:] = np.cumsum([len(e) for e in enc]) if enc else []
+            bases = np.concatenate(enc).astype(np.uint8) if enc else np.zeros(0, np.uint8)
+        return ix.find_mems_contigs(contigs, bases, read_offsets, minimum_length, both_strands, split_breaks, max_occ)
+
+    def locate_contigs(self, contigs, rows):
+        """SMEM rows (start, end, lo, hi) of any find_smems* call -> (hit_offsets, hits int32[T, 2] = (contig, 1-based
+        offset), dropped): GenieIndex.locate_contigs.  The rows stay SMEMs of the concatenation; occurrences that bridge two
+        sequences are dropped."""
+        return self.matcher.index(self.lut.lut_size).locate_contigs(contigs, rows)
+
     def match_stats_text(self, data, fmt="lines", intervals=True, both_strands=False, split_breaks=True, fold_case=False):
         """match_stats of the reads in a text (find_smems_text's formats and translation) -> (ms, lohi, status,
         read_offsets): read_offsets int64[N+1] on the device, to index the flat arrays with."""

@@ -505,6 +505,82 @@ int genie_find_mems(const genie_index *ix, int32_t flags, const uint8_t *d_bases
                     int64_t *d_totals,       /* 2, may be NULL: {rows in all, positions skipped by max_occ} */
                     void *d_workspace, int64_t workspace_bytes, void *stream);
 
+/* A reference of SEVERAL sequences (chromosomes, scaffolds, plasmids): one index over their concatenation plus a contig
+ * table.  Without the table every call answers in the concatenation's coordinates and reports, without a word, matches that
+ * start in one sequence and end in the next; such a match exists in no molecule.
+ * Definitions.  A contig table is d_contig_offsets: a device array of n_contigs + 1 int64 values, n_contigs >= 1, 8-byte
+ * aligned, with off[0] = 0, non-decreasing values and off[n_contigs] = n, the reference length of the handle.  Contig c
+ * is T[off[c] .. off[c+1]); it may be empty (FASTA records may be).  The contig of a 0-based reference position t < n is the
+ * unique c with off[c] <= t < off[c+1] (empty contigs own nothing); room(t) = off[c+1] - t; t is a contig start iff t ==
+ * off[c].  Position n, the $ suffix of row 0, belongs to no contig.  This is the convention of the read CSR: the
+ * d_read_offsets that genie_reads_from_fasta writes for a reference file is a valid table as it is, its d_bases the
+ * concatenation to build the index from (genie_index_create_device).
+ * genie_contigs_validate checks the three conditions on the device, in one pass and one synchronisation of `stream` (as
+ * genie_index_validate does for an image): GENIE_OK or GENIE_E_INVALID.  The calls below do NOT repeat the check.  They are
+ * memory-safe on any table contents: a table that genie_contigs_validate would refuse gives undefined values, but no load
+ * or store outside the declared sizes (the lookup bisects over the indices 0 .. n_contigs only and clamps what it derives).
+ * In every call of this group a null ix, a null or not 8-byte aligned table or n_contigs < 1 gives GENIE_E_INVALID and
+ * n_contigs above 2^31 - 2 GENIE_E_TOO_LONG, before the device check.
+ * The lookup: a block stages samples of the table in LDS (every 2^shift-th offset, clamped, as int32) and a lane bisects
+ * those, then the 2^shift entries between two of them in global memory: up to 1023 contigs from LDS alone, four L2 loads on
+ * top at 10^4.  The walks of genie_find_mems_contigs stage up to 12 288 samples (48 KB) in blocks whose positions have that
+ * many seed rows. */
+int genie_contigs_validate(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs, void *stream);
+
+/* genie_find_mems on a reference of several sequences: the MEMs of a strand-read against the SET of contigs, i.e. the union
+ * over c of its MEMs against contig c alone.  Arguments: those of genie_find_mems with the table behind ix.  Inputs, flags,
+ * strands, breaks, d_status, max_occ, d_totals, the sizing call (d_rows == NULL), out_cap_rows and the synchronisations
+ * (those of genie_match_stats and no more) are genie_find_mems's.  The definition changes in two places.  A MEM is (p, t, l)
+ * with l >= m, Q[p .. p+l) == T[t .. t+l), no break inside, and it lies inside one contig: l <= room(t);
+ *   right-maximal   p + l == L, or l == room(t), or Q[p+l] != T[t+l];
+ *   left-maximal    p == 0, or t is a contig start, or Q[p-1] != T[t-1].
+ * Rows stay int32 (start, end, pos, row): pos is 1-based IN THE CONCATENATION (genie_contig_coords names it), row the
+ * suffix-array row of t, the order (start, row) within a strand-read, strand-reads in input order.  Every such MEM is found
+ * from an occurrence of its seed Q[p .. p+m) in the concatenation: an occurrence with room(t) < m is no row, the
+ * left-maximality rule gains the contig start, the length is clipped to room(t).  max_occ and GENIE_READ_ABSENT_BASE keep
+ * referring to the concatenation: it is the seed's interval there, bridging occurrences included, that bounds the work.
+ * Properties: with n_contigs == 1 the outputs are byte for byte those of genie_find_mems; the (start, end, pos) triples of a
+ * strand-read are the union over c of what genie_find_mems gives on an index of contig c alone, pos shifted by off[c].
+ * Checks: genie_find_mems's, then the table's (above), then the workspace's (GENIE_E_CAPACITY), all before the device
+ * check.  The workspace function takes genie_find_mems_workspace_bytes's arguments and n_contigs; it returns
+ * GENIE_E_INVALID for arguments the call would refuse, is a multiple of 256, monotone in N, total_bases and n_contigs, and
+ * at least genie_find_mems_workspace_bytes of the same batch; what it adds is a function of n_contigs alone (today
+ * nothing: the table is the caller's and its samples live in LDS).
+ * Cost: genie_find_mems plus one lookup per seed occurrence, in the count and in the fill. */
+int64_t genie_find_mems_contigs_workspace_bytes(int64_t N, int64_t total_bases, int64_t max_len, int32_t flags, int64_t n_contigs);
+int genie_find_mems_contigs(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs, int32_t flags,
+                            const uint8_t *d_bases, const int64_t *d_read_offsets, int64_t N, int64_t total_bases,
+                            int64_t max_len, int32_t min_len, int32_t max_occ,
+                            int64_t *d_offsets,      /* S * N + 1 */
+                            int32_t *d_rows,         /* 4 * out_cap_rows, 16-byte aligned; may be NULL: counting only */
+                            int64_t out_cap_rows,
+                            int32_t *d_status,       /* S * N, may be NULL */
+                            int64_t *d_totals,       /* 2, may be NULL: {rows in all, positions skipped by max_occ} */
+                            void *d_workspace, int64_t workspace_bytes, void *stream);
+
+/* SMEM rows -> hits named by contig, BWA's rule.  Input: S rows int32 (start, end, lo, hi), 16-byte aligned: the rows of any
+ * genie_find_smems* call.  The rows stay SMEMs OF THE CONCATENATION -- this call does not make them SMEMs of the sequence
+ * set --; it drops the occurrences that bridge two sequences.  For row j with len = end - start, every suffix-array row r in
+ * [lo, hi] gives t = SA[r]; the hit is kept iff t < n and len <= room(t), and is the int32 pair (contig, 1-based offset
+ * inside the contig); hits come out in row order.  An interval with lo < 0 or hi < lo contributes nothing.
+ *   d_hit_offsets  S + 1 int64, 8-byte aligned: row j's hits are d_hits[2 off[j] .. 2 off[j+1]); [S] keeps the true total
+ *   d_hits         2 * cap_hits int32, 8-byte aligned; may be NULL: the sizing call.  Hits past cap_hits are dropped.
+ *   d_totals       2 int64, may be NULL: {hits kept, occurrences dropped as bridging}
+ *   d_tmp          256-byte aligned scratch of genie_locate_contigs_tmp_bytes(S) bytes (GENIE_E_CAPACITY otherwise; the size
+ *                  function gives GENIE_E_INVALID for S < 0 and a multiple of 256 else, monotone in S)
+ * Count, scan and fill, one lane per interval up to 32 rows and the whole wave beyond; no atomic decides a value; no
+ * synchronisation of `stream`. */
+int64_t genie_locate_contigs_tmp_bytes(int64_t S);
+int genie_locate_contigs(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs, const int32_t *d_rows,
+                         int64_t S, int64_t *d_hit_offsets, int32_t *d_hits, int64_t cap_hits, int64_t *d_totals, void *d_tmp,
+                         int64_t tmp_bytes, void *stream);
+
+/* 1-based concatenation positions d_pos[i * stride], i < count, -> d_out[2 i .. 2 i + 2) = (contig, 1-based offset inside
+ * it); a position outside [1, n] gives (-1, -1).  Pass d_rows + 2 with stride 4 for MEM rows, a genie_locate result with
+ * stride 1.  stride >= 1; d_pos and d_out 4-byte aligned.  One lane per element, no synchronisation of `stream`. */
+int genie_contig_coords(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs, const int32_t *d_pos,
+                        int32_t stride, int64_t count, int32_t *d_out /* 2 * count */, void *stream);
+
 /* Reads from TEXT, on the device: the bytes of a file of reads -> the d_bases / d_read_offsets that genie_find_smems_long_ex
  * takes.  The reference has no counterpart (its reads are Python strings); this replaces encoding every string on the host.
  * Lines.  A line ends at a '\n' (0x0A), which is not part of it; if the line is then not empty and its last byte is '\r',
