@@ -601,6 +601,68 @@ int genie_contig_coords(const genie_index *ix, const int64_t *d_contig_offsets, 
     return launch_contig_coords(ix, d_contig_offsets, n_contigs, d_pos, stride, count, d_out, stream);
 }
 
+int64_t genie_match_stats_contigs_workspace_bytes(int64_t N, int64_t total_bases, int64_t max_len, int32_t flags, int64_t n_contigs)
+{
+    if (n_contigs < 1 || n_contigs > 0x7ffffffell) return (int64_t)GENIE_E_INVALID;
+    const int64_t parent = genie_match_stats_workspace_bytes(N, total_bases, max_len, flags);
+    return parent < 0 ? parent : match_stats_contigs_workspace_bytes(N, total_bases, flags, n_contigs);
+}
+
+int genie_match_stats_contigs(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs, int32_t flags,
+                              const uint8_t *d_bases, const int64_t *d_read_offsets, int64_t N, int64_t total_bases, int64_t max_len,
+                              int32_t *d_ms, int32_t *d_lohi, int32_t *d_status, int64_t *d_totals, void *d_workspace,
+                              int64_t workspace_bytes, void *stream)
+{
+    // argument checks first: they need no device image
+    if (!ix) return GENIE_E_INVALID;
+    if (N < 0 || total_bases < 0 || max_len < 0 || max_len > 0x7fffffffll || workspace_bytes < 0 || (N > 0 && !d_read_offsets) ||
+        (total_bases > 0 && (!d_bases || !d_ms)))
+        return GENIE_E_INVALID;
+    if (flags & ~(GENIE_READS_BOTH_STRANDS | GENIE_READS_SPLIT_BREAKS)) return GENIE_E_INVALID;
+    if ((reinterpret_cast<uintptr_t>(d_ms) & 3) != 0 || (reinterpret_cast<uintptr_t>(d_lohi) & 7) != 0 ||
+        (reinterpret_cast<uintptr_t>(d_totals) & 7) != 0)
+        return GENIE_E_INVALID;
+    int rc = contig_args(d_contig_offsets, n_contigs);
+    if (rc) return rc;
+    if (N > 0 && (!d_workspace || (reinterpret_cast<uintptr_t>(d_workspace) & 255) != 0 ||
+                  workspace_bytes < match_stats_contigs_workspace_bytes(N, total_bases, flags, n_contigs)))
+        return GENIE_E_CAPACITY;
+    if ((rc = ready(ix))) return rc;
+    return launch_match_stats_contigs(ix, d_contig_offsets, n_contigs, flags, d_bases, d_read_offsets, N, total_bases, max_len, d_ms,
+                                      d_lohi, d_status, d_totals, d_workspace, workspace_bytes, stream);
+}
+
+int64_t genie_find_smems_contigs_workspace_bytes(int64_t N, int64_t total_bases, int64_t max_len, int32_t flags, int64_t n_contigs)
+{
+    if (n_contigs < 1 || n_contigs > 0x7ffffffell) return (int64_t)GENIE_E_INVALID;
+    const int64_t parent = genie_find_smems_long_ex_workspace_bytes(N, total_bases, max_len, flags);
+    return parent < 0 ? parent : find_smems_contigs_workspace_bytes(N, total_bases, flags, n_contigs);
+}
+
+int genie_find_smems_contigs(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs, int32_t mode, int32_t flags,
+                             const uint8_t *d_bases, const int64_t *d_read_offsets, int64_t N, int64_t total_bases, int64_t max_len,
+                             int32_t min_len, int64_t *d_offsets, int32_t *d_rows, int64_t out_cap_rows, int32_t *d_status,
+                             int64_t *d_totals, void *d_workspace, int64_t workspace_bytes, void *stream)
+{
+    // argument checks first: they need no device image
+    if (!ix) return GENIE_E_INVALID;
+    if (N < 0 || total_bases < 0 || max_len < 0 || max_len > 0x7fffffffll || out_cap_rows < 0 || workspace_bytes < 0 || !d_offsets ||
+        (N > 0 && (!d_read_offsets || !d_rows)) || (total_bases > 0 && !d_bases))
+        return GENIE_E_INVALID;
+    if (mode < GENIE_MODE_BWA || mode > GENIE_MODE_RMI) return GENIE_E_INVALID;
+    if (flags & ~(GENIE_READS_BOTH_STRANDS | GENIE_READS_SPLIT_BREAKS)) return GENIE_E_INVALID;
+    if ((flags & GENIE_READS_SPLIT_BREAKS) && mode != GENIE_MODE_BWA) return GENIE_E_INVALID;
+    if ((reinterpret_cast<uintptr_t>(d_rows) & 15) != 0 || (reinterpret_cast<uintptr_t>(d_totals) & 7) != 0) return GENIE_E_INVALID;
+    int rc = contig_args(d_contig_offsets, n_contigs);
+    if (rc) return rc;
+    if (N > 0 && (!d_workspace || (reinterpret_cast<uintptr_t>(d_workspace) & 255) != 0 ||
+                  workspace_bytes < find_smems_contigs_workspace_bytes(N, total_bases, flags, n_contigs)))
+        return GENIE_E_CAPACITY;
+    if ((rc = ready(ix)) || (rc = mode_tables(ix, mode))) return rc;
+    return launch_find_smems_contigs(ix, d_contig_offsets, n_contigs, mode, flags, d_bases, d_read_offsets, N, total_bases, max_len,
+                                     min_len, d_offsets, d_rows, out_cap_rows, d_status, d_totals, d_workspace, workspace_bytes, stream);
+}
+
 int64_t genie_exact_match_workspace_bytes(int64_t N, int64_t total_bases, int64_t max_len, int32_t flags)
 {
     if (N < 0 || total_bases < 0 || max_len < 0 || max_len > 0x7fffffffll) return (int64_t)GENIE_E_INVALID;

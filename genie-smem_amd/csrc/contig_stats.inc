@@ -1,0 +1,555 @@
+// contig_stats.inc -- genie_match_stats_contigs and genie_find_smems_contigs: matching statistics and SMEMs that are exact
+// with respect to a reference of several sequences (included by kernels.hip behind contigs.inc, inside namespace genie).
+//
+// ms_c[v], the contig-exact matching statistic of a virtual position (long_units.inc), is the largest l for which the l
+// bases from there on hold no break and equal T[t .. t+l) for some t with l <= room(t) (contigs.inc): they occur inside ONE
+// contig.  Four facts carry the kernels (DESIGN.md section 19 proves them, tests/test_contig_stats_host.py checks them):
+//   1  ms_c <= ms, and ms_c >= 1 iff ms >= 1 (an occurrence t < n has room(t) >= 1): absent and bad bases are flagged as ever.
+//   2  ms_c[v+1] >= ms_c[v] - 1 inside a strand-read: fwd_c[p] = p + ms_c[p] is non-decreasing, so the traversal of LR3 .. LR5
+//      applies to fwd_c unchanged and yields the SMEMs with respect to the sequence set.
+//   3  Let p0 be a run start of fwd[] (p0 == 0 or fwd[p0] != fwd[p0-1]).  If some occurrence t of Q[p0 .. fwd[p0]) has
+//      room(t) >= fwd[p0] - p0, then ms_c = ms on the whole run (t + k serves p0 + k): only run starts need a room test.
+//   4  "some t in the interval of Q[p .. p+l) has room(t) >= l" is monotone in l: where the run start fails, ms_c[p] of every
+//      position of the run is found by bisection over l, from the largest room seen upward.
+// Both calls run the front of their parents (lu_run) with tails of their own, which put three kernels between LR2 and what
+// reads fwd[]:
+//   LR1, LR2 (MS instance)   fwd[] of the concatenation, nothing else (LUT / RMI mode: the SMEM instance, for its statuses;
+//                            its marks are cleared again)
+//   CS1 cs_start_kernel      one wave per window, four windows per block, four positions per lane (lr_fwd_kernel's shape;
+//                            one block per window, as lr_ms_kernel is cut, took 6.3 ms where this takes the time in
+//                            DESIGN.md section 19).  At a run start with a match: its interval as lr_ms_kernel gets it (the
+//                            positions the entry does not decide are gathered per wave), then SaRec.s of its rows with early
+//                            exit -- one lane up to kCsLaneRows rows, the whole wave beyond (cs_walk: lc_walk_kernel's
+//                            shape) -- and room(t) >= len through ctg_find on the staged table.  A run start without a
+//                            qualifying row is FLAGGED: the k-th one of a window goes to slot[first position of the window
+//                            + k] = {end of the run, position in the window, largest room seen}; the window's count to
+//                            wcnt[], the block's to bsum[].
+//   scan_block_sums_kernel   over the block counts: item j of the slow list belongs to the last block b with bsum[b] <= j,
+//                            and there to the window that wcnt[] says.  No atomic orders anything.
+//   CS2 cs_slow_kernel       rare.  A fixed grid of waves strides over the flagged runs (the count stays on the device); a
+//                            lane per position of the run searches l (fact 4: l = ms first, a gallop up from the bound, a bisection), l = ms holding where the
+//                            position's own interval has a qualifying row; the interval of Q[p .. p+l) is sa_interval's over
+//                            the packed unit, its rows are walked by cs_walk.  Writes fwd_c into fwd[] -- only the flagged
+//                            run's own positions, whose extent CS1 read before anything was changed -- and counts the
+//                            clipped positions, one word per block; cs_totals_kernel adds them to d_totals[0].
+//   then, match statistics:  lr_ms_kernel as it is, over the corrected fwd[]: the intervals of clipped positions are those
+//                            of the clipped matches in the concatenation.
+//   then, SMEMs:             CS3 cs_marks_kernel, one wave per window: what LR2's SMEM instance writes beside fwd[] (the
+//                            first maximum of fwd[a] - a, the mark at fwd[a]) from the corrected fwd[]; LR3, LR4,
+//                            launch_compact and LR5 as in lr_pipeline.
+// Workspace: the parent's, then the slots (8 bytes per virtual position), the window and block counts and CS2's clip counts.  The
+// parent's part is handed to lu_run at exactly its declared size, so that the units of a pass, and with them the windows,
+// never exceed what the counts were sized for (cs_units_cap).
+// Memory safety on any table contents is ctg_find's; rows come from the index, positions from fwd[], which LR2 bounds.
+namespace {
+
+constexpr int kCsLaneRows = 32;           // an interval of more rows is walked by the whole wave
+constexpr int kCsSlowBlocks = 1024;       // blocks of CS2: four flagged runs each per round
+constexpr uint32_t kCsRoomCap = 0xFFFFFFu;      // the largest room kept in a slot (a lower bound: capping it is safe)
+
+struct CsArea {
+    uint2 *slot;                          // positions: {run end, position in the window << 24 | largest room seen}
+    int32_t *wcnt;                        // windows: flagged run starts per window
+    unsigned long long *bsum;             // blocks of CS1 + 1: flagged run starts per block, scanned
+    unsigned long long *clip;             // kCsSlowBlocks: clipped positions per block of CS2
+    long long nwin_cap;                   // windows the counts hold
+};
+
+inline int64_t cs_layout(uint8_t *p, int64_t positions, int64_t units, CsArea *a)
+{
+    a->nwin_cap = positions / kLrWin + units + 1;
+    Carver c{p};
+    c.take(a->slot, 8 * positions);
+    c.take(a->wcnt, 4 * a->nwin_cap);
+    c.take(a->bsum, 8 * ((a->nwin_cap + kLrFwdWaves - 1) / kLrFwdWaves + 1));
+    c.take(a->clip, 8 * kCsSlowBlocks);
+    return c.at;
+}
+
+// What the tails need beside their parents' members
+struct CsCall {
+    CtgTab g;
+    CsArea a;
+    long long *totals;                    // d_totals or null
+};
+
+// room of the occurrence at suffix-array row `row`; 0 for the $ suffix
+__device__ __forceinline__ int cs_room(const DevIndex &ix, const CtgTab &g, const int *__restrict__ cs, int row)
+{
+    const int t = ix.sa[row].s;
+    return t >= 0 && t < ix.n ? ctg_find(g, cs, ix.n, t).room : 0;
+}
+
+// The largest room among the rows [lo, lo + cnt) of a lane's interval, or any room >= len once one is seen (early exit).
+// Called by every lane of the wave, cnt == 0 where a lane has nothing to walk.
+__device__ __forceinline__ int cs_walk(const DevIndex &ix, const CtgTab &g, const int *__restrict__ cs, int lo, int cnt, int len,
+                                       int lane)
+{
+    int best = 0;
+    const bool big = cnt > kCsLaneRows;
+    if (!big)
+        for (int k = 0; k < cnt; k++) {
+            const int room = cs_room(ix, g, cs, lo + k);
+            best = room > best ? room : best;
+            if (room >= len) break;
+        }
+    unsigned long long todo = __ballot(big);
+    while (todo) {
+        const int src = __ffsll((long long)todo) - 1;
+        todo &= todo - 1;
+        const int blo = __shfl(lo, src), bcnt = __shfl(cnt, src), blen = __shfl(len, src);
+        int top = 0;
+        for (int k0 = 0; k0 < bcnt; k0 += kWave) {               // wave-uniform trip count and exit
+            const int k = k0 + lane;
+            const int room = k < bcnt ? cs_room(ix, g, cs, blo + k) : 0;
+            top = room > top ? room : top;
+            if (__any(room >= blen)) break;
+        }
+#pragma unroll
+        for (int o = kWave / 2; o > 0; o >>= 1) {
+            const int x = __shfl_xor(top, o);
+            top = x > top ? x : top;
+        }
+        if (lane == src) best = top;
+    }
+    return best;
+}
+
+// rows of an inclusive interval that are followed: none for (-1, -1), none beyond the suffix array
+__device__ __forceinline__ int cs_rows(const DevIndex &ix, int2 iv)
+{
+    const int hi = iv.y < ix.n ? iv.y : ix.n;
+    return iv.x >= 0 && hi >= iv.x ? hi - iv.x + 1 : 0;
+}
+
+// CS1.  One wave per window, kLrFwdWaves windows per block (lr_fwd_kernel's shape: four positions per lane, no barrier between
+// the staging of the table and the block's count).  skip_flagged: the SMEM tail, where a unit with any status has no rows
+// (and, in LUT / RMI mode, no fwd[]); the match statistics want every unit but those with a bad base.
+template <bool C16, bool SLICED = false>
+__global__ void __launch_bounds__(kLrFwdWaves * 64) cs_start_kernel(DevIndex ix, CtgTab cg, int skip_flagged, const long long *__restrict__ off,
+                                                                    long long N, long long nwin, const uint64_t *__restrict__ packed,
+                                                                    const int32_t *__restrict__ st, const int32_t *__restrict__ fwd,
+                                                                    uint2 *__restrict__ slot, int32_t *__restrict__ wcnt,
+                                                                    unsigned long long *__restrict__ bsum, long long block0)
+{
+    constexpr int kPer = kLrWin / kWave;
+    extern __shared__ int ctg_lds[];
+    __shared__ uint16_t lists[kLrFwdWaves][kLrWin];              // the positions the entry does not decide
+    __shared__ int2 sivs[kLrFwdWaves][kLrWin];                   // ... and their intervals
+    __shared__ int bcnt[kLrFwdWaves];
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = rfl((int)(threadIdx.x >> 6));
+    const long long blk = SLICED ? block0 + blockIdx.x : (long long)blockIdx.x;
+    const long long gw = blk * kLrFwdWaves + wave;
+    ctg_stage(cg, ix.n, ctg_lds);
+    bool live = gw < nwin;                                       // wave-uniform, as everything that decides a branch below
+    long long r = 0, w = 0, o = 0, Ll = 0;
+    if (live) {
+        r = lr_find(N, gw, [&](long long x) { return lr_wb(off, x); });
+        w = gw - lr_wb(off, r);
+        o = off[r];
+        Ll = off[r + 1] - o;
+        live = w >= 0 && w * kLrWin < Ll;
+    }
+    if (live) {
+        const int32_t status = st[r];
+        live = skip_flagged ? status == GENIE_READ_OK : status != GENIE_READ_BAD_BASE;
+    }
+    int nflag = 0;
+    if (live) {
+        const int L = (int)Ll, w0 = (int)(w * kLrWin);
+        const int nw = L - w0 < kLrWin ? L - w0 : kLrWin;
+        const QPlain Q{packed + lr_wd(off, r)};
+        uint16_t *sl = lists[wave];
+        int2 *sv = sivs[wave];
+        const unsigned long long below = (1ull << lane) - 1ull;
+        int2 iv[kPer];
+        int len[kPer], fv[kPer];
+        bool gen[kPer];
+        int ngen = 0;
+#pragma unroll
+        for (int k = 0; k < kPer; k++) {
+            const int t = k * kWave + lane, a = w0 + t;
+            const bool in = t < nw;
+            fv[k] = in ? fwd[o + a] : 0;
+            const bool start = in && (a == 0 || fwd[o + a - 1] != fv[k]);
+            len[k] = start ? fv[k] - a : 0;
+            const bool act = len[k] > 0;
+            const uint64_t x = act ? Q.win(a) : 0ull;
+            const bool fast = interval_from_window<C16>(ix, x, len[k], act, iv[k]);
+            gen[k] = act && !fast;
+            const unsigned long long gb = __ballot(gen[k]);
+            if (gen[k]) sl[ngen + __popcll(gb & below)] = (uint16_t)t;
+            ngen += __popcll(gb);
+        }
+        wave_lds_fence();
+        for (int c0 = 0; c0 < ngen; c0 += kWave) {               // the general search on full waves
+            if (c0 + lane < ngen) {
+                const int g = sl[c0 + lane], ga = w0 + g;
+                sv[g] = sa_interval(ix, ix.dir, Q, ga, fwd[o + ga] - ga);
+            }
+        }
+        wave_lds_fence();
+#pragma unroll
+        for (int k = 0; k < kPer; k++) {
+            const int t = k * kWave + lane, a = w0 + t;
+            const bool act = len[k] > 0;
+            if (gen[k]) iv[k] = sv[t];
+            const int best = cs_walk(ix, cg, ctg_lds, iv[k].x, act ? cs_rows(ix, iv[k]) : 0, len[k], lane);
+            const bool flagged = act && best < len[k];
+            int p1 = a + 1;
+            if (flagged) {                                       // the run's end: the first position behind a whose fwd differs
+                int hi = L;
+                while (p1 < hi) {
+                    const int mid = p1 + ((hi - p1) >> 1);
+                    if (fwd[o + mid] == fv[k]) p1 = mid + 1; else hi = mid;
+                }
+            }
+            const unsigned long long fb = __ballot(flagged);
+            if (flagged) {
+                const uint32_t room = (uint32_t)best < kCsRoomCap ? (uint32_t)best : kCsRoomCap;
+                slot[o + w0 + nflag + __popcll(fb & below)] = make_uint2((uint32_t)p1, ((uint32_t)t << 24) | room);
+            }
+            nflag += __popcll(fb);
+        }
+    }
+    if (lane == 0) {
+        if (gw < nwin) wcnt[gw] = nflag;
+        bcnt[wave] = nflag;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int all = 0;
+        for (int k = 0; k < kLrFwdWaves; k++) all += bcnt[k];
+        bsum[blk] = (unsigned long long)all;
+    }
+}
+
+// CS2.  bsum is scanned: bsum[nblk] flagged runs in all, nblk the blocks of CS1.
+__global__ void __launch_bounds__(256) cs_slow_kernel(DevIndex ix, CtgTab cg, const long long *__restrict__ off, long long N,
+                                                      long long nwin, const uint64_t *__restrict__ packed, int32_t *__restrict__ fwd,
+                                                      const uint2 *__restrict__ slot, const int32_t *__restrict__ wcnt,
+                                                      const unsigned long long *__restrict__ bsum, unsigned long long *__restrict__ clip)
+{
+    extern __shared__ int ctg_lds[];
+    __shared__ unsigned long long wclip[256 / kWave];
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+    const long long nblk = (nwin + kLrFwdWaves - 1) / kLrFwdWaves;
+    const long long items = (long long)bsum[nblk];
+    if ((long long)blockIdx.x * (256 / kWave) >= items) {        // block-uniform: nothing to do, and no staging
+        if (threadIdx.x == 0) clip[blockIdx.x] = 0;
+        return;
+    }
+    ctg_stage(cg, ix.n, ctg_lds);
+    unsigned long long nclip = 0;
+    for (long long j = (long long)blockIdx.x * (256 / kWave) + wave; j < items; j += (long long)gridDim.x * (256 / kWave)) {
+        const long long blk = lr_find(nblk, j, [&](long long x) { return (long long)bsum[x]; });
+        long long k = j - (long long)bsum[blk], gw = blk * kLrFwdWaves;
+        for (int i = 0; i < kLrFwdWaves - 1 && gw + 1 < nwin && k >= wcnt[gw]; i++) k -= wcnt[gw++];      // the window inside its block
+        const long long r = lr_find(N, gw, [&](long long x) { return lr_wb(off, x); });
+        const long long w = gw - lr_wb(off, r);
+        const long long o = off[r], Ll = off[r + 1] - o;
+        if (w < 0 || w * kLrWin >= Ll || k < 0 || k >= kLrWin) continue;     // cannot happen: CS1 counted this window
+        const int L = (int)Ll, w0 = (int)(w * kLrWin);
+        const uint2 sl = slot[o + w0 + k];
+        const int p0 = w0 + (int)(sl.y >> 24), room0 = (int)(sl.y & kCsRoomCap);
+        const int p1 = (int)sl.x < L ? (int)sl.x : L;
+        if (p0 >= L) continue;
+        const int e = fwd[o + p0];                               // the run's fwd: this wave alone writes these positions, below
+        const QPlain Q{packed + lr_wd(off, r)};
+        for (int c0 = p0; c0 < p1; c0 += kWave) {                // wave-uniform
+            const int p = c0 + lane, ms = e - p;
+            const bool in = p < p1 && ms > 0;                    // ms == 0: an absent base that ends the run's match
+            // pred(lo) holds, pred(hi) does not (ms + 1: no match is that long); the run start failed at ms already
+            int lo = 0, hi = 1;
+            if (in) {
+                lo = room0 - (p - p0) > 1 ? room0 - (p - p0) : 1;
+                hi = p == p0 ? ms : ms + 1;
+                lo = lo < hi ? lo : hi - 1;
+            }
+            // The first probe is l = ms; then a gallop upward from lo (1, 2, 4 ... more), where the answer usually sits -- a match
+            // cut at its contig's end has ms_c = the room, which is lo --, and a bisection once a length is refuted.
+            bool first = p != p0;
+            int gal = 1;
+            while (__any(hi - lo > 1)) {
+                const bool open = hi - lo > 1;
+                const bool up = !first && gal > 0;
+                const int mid = first ? hi - 1 : (up ? (lo + gal < hi - 1 ? lo + gal : hi - 1) : lo + ((hi - lo) >> 1));
+                first = false;
+                int2 iv = make_int2(-1, -1);
+                if (open) iv = sa_interval(ix, ix.dir, Q, p, mid);
+                const int best = cs_walk(ix, cg, ctg_lds, iv.x, open ? cs_rows(ix, iv) : 0, mid, lane);
+                if (open) {
+                    if (best >= mid) {
+                        lo = mid;
+                        if (up) gal = gal < (1 << 28) ? gal << 1 : gal;
+                    } else {
+                        hi = mid;
+                        lo = best > lo ? best : lo;              // the rows match mid bases: one with room `best` serves l = best
+                        if (up) gal = 0;
+                    }
+                }
+            }
+            if (in) {
+                nclip += lo < ms ? 1ull : 0ull;
+                fwd[o + p] = p + lo;
+            }
+        }
+    }
+    nclip = wave_sum64(nclip);
+    if (lane == 0) wclip[wave] = nclip;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long all = 0;
+        for (int k = 0; k < 256 / kWave; k++) all += wclip[k];
+        clip[blockIdx.x] = all;
+    }
+}
+
+// d_totals[0] += the blocks' clipped positions (one block; the passes of a call follow each other on the stream)
+__global__ void __launch_bounds__(256) cs_totals_kernel(const unsigned long long *__restrict__ clip, int blocks,
+                                                        long long *__restrict__ totals)
+{
+    __shared__ unsigned long long wsum[256 / kWave];
+    unsigned long long d = 0;
+    for (int b = threadIdx.x; b < blocks; b += 256) d += clip[b];
+    d = wave_sum64(d);
+    if ((threadIdx.x & (kWave - 1)) == 0) wsum[threadIdx.x / kWave] = d;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long all = 0;
+        for (int k = 0; k < 256 / kWave; k++) all += wsum[k];
+        totals[0] += (long long)all;
+    }
+}
+
+// CS3: the window maxima and the marks of LR2's SMEM instance, from fwd[] as it stands
+template <bool SLICED>
+__global__ void __launch_bounds__(kLrFwdWaves * 64) cs_marks_kernel(const long long *__restrict__ off, long long N, long long nwin,
+                                                                    const int32_t *__restrict__ st, const int32_t *__restrict__ fwd,
+                                                                    int2 *__restrict__ wmax, uint8_t *__restrict__ mark,
+                                                                    long long block0)
+{
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = rfl((int)(threadIdx.x >> 6));
+    const long long gw = (SLICED ? block0 + blockIdx.x : (long long)blockIdx.x) * kLrFwdWaves + wave;
+    if (gw >= nwin) return;                                      // wave-uniform; no block-wide barrier below
+    const long long r = lr_find(N, gw, [&](long long x) { return lr_wb(off, x); });
+    const long long w = gw - lr_wb(off, r);
+    const long long o = off[r], Ll = off[r + 1] - o;
+    if (w < 0 || w * kLrWin >= Ll || st[r] != GENIE_READ_OK) return;
+    const int L = (int)Ll, w0 = (int)(w * kLrWin);
+    const int nw = L - w0 < kLrWin ? L - w0 : kLrWin;
+    unsigned long long best = 0;                                 // (fwd[a] - a) << 8 | 255 - (a - w0): the first maximum
+#pragma unroll
+    for (int k = 0; k < kLrWin / kWave; k++) {
+        const int t = k * kWave + lane, a = w0 + t;
+        if (t < nw) {
+            const int v = fwd[o + a];
+            const unsigned long long key = ((unsigned long long)(uint32_t)(v - a) << kLrWinShift) | (unsigned)(kLrWin - 1 - t);
+            best = key > best ? key : best;
+            if (v >= 0 && v < L) mark[o + v] = 1;                // every writer stores the same value
+        }
+    }
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) {
+        const unsigned long long x = lr_shfl_xor64(best, m);
+        best = x > best ? x : best;
+    }
+    if (lane == 0) wmax[gw] = make_int2((int)(best >> kLrWinShift), w0 + kLrWin - 1 - (int)(best & (kLrWin - 1)));
+}
+
+// CS1, the scan, CS2 and the total over the units of `uoff`, whose fwd[] LR2 has written
+int cs_correct(const genie_index *ix, const CsCall &cs, bool skip_flagged, const LongArea &a, const long long *uoff, long long U,
+               hipStream_t s)
+{
+    if (a.nwin > cs.a.nwin_cap) return GENIE_E_CAPACITY;         // cannot happen: cs_units_cap
+    const size_t lds = ctg_lds_bytes(cs.g);
+    const bool c16 = (ix->dev.flags & kFlagCompactTable) != 0;
+    const long long nblk = (a.nwin + kLrFwdWaves - 1) / kLrFwdWaves;
+    const auto start_one = c16 ? cs_start_kernel<true> : cs_start_kernel<false>;
+    const auto start_sliced = c16 ? cs_start_kernel<true, true> : cs_start_kernel<false, true>;
+    LAUNCH_SLICED(start_one, start_sliced, nblk, kLrFwdWaves * 64, lds, s, ix->dev, cs.g, (int)skip_flagged, uoff, U, a.nwin,
+                  static_cast<const uint64_t *>(a.packed), static_cast<const int32_t *>(a.st), static_cast<const int32_t *>(a.fwd),
+                  cs.a.slot, cs.a.wcnt, cs.a.bsum);
+    LAUNCH(scan_block_sums_kernel, dim3(1), dim3(kScanBlock), 0, s, cs.a.bsum, nblk);
+    const int blocks = (int)std::min<long long>(a.nwin, kCsSlowBlocks);
+    LAUNCH(cs_slow_kernel, dim3(blocks), dim3(256), lds, s, ix->dev, cs.g, uoff, U, a.nwin, static_cast<const uint64_t *>(a.packed),
+           a.fwd, static_cast<const uint2 *>(cs.a.slot), static_cast<const int32_t *>(cs.a.wcnt),
+           static_cast<const unsigned long long *>(cs.a.bsum), cs.a.clip);
+    if (cs.totals)
+        LAUNCH(cs_totals_kernel, dim3(1), dim3(256), 0, s, static_cast<const unsigned long long *>(cs.a.clip), blocks, cs.totals);
+    return GENIE_OK;
+}
+
+// lr_match_stats with the correction between LR2 and LRM
+int cs_match_stats(const genie_index *ix, const CsCall &cs, const uint8_t *d_bases, const LongArea &a, const long long *uoff,
+                   long long U, const long long *usrc, const long long *uvirt, int32_t *d_ms, int32_t *d_lohi, hipStream_t s)
+{
+    LAUNCH_BLOCKS(lr_pack_kernel, (a.nwords + 255) / 256, 256, 0, s, d_bases, uoff, U, usrc, a.nwords, a.packed, a.st);
+    const bool c16 = (ix->dev.flags & kFlagCompactTable) != 0;
+    const auto fwd_kernel = c16 ? lr_fwd_kernel<true, true> : lr_fwd_kernel<false, true>;
+    const auto fwd_sliced = c16 ? lr_fwd_kernel<true, true, true> : lr_fwd_kernel<false, true, true>;
+    LAUNCH_SLICED(fwd_kernel, fwd_sliced, (a.nwin + kLrFwdWaves - 1) / kLrFwdWaves, kLrFwdWaves * 64, 0, s, ix->dev, (int)GENIE_MODE_BWA, uoff, U,
+                  a.nwin, static_cast<const uint64_t *>(a.packed), a.st, a.fwd, static_cast<int2 *>(nullptr),
+                  static_cast<uint8_t *>(nullptr), table_bytes(ix));
+    if (int rc = cs_correct(ix, cs, false, a, uoff, U, s)) return rc;
+    const auto ms_kernel = c16 ? lr_ms_kernel<true> : lr_ms_kernel<false>;
+    const auto ms_sliced = c16 ? lr_ms_kernel<true, true> : lr_ms_kernel<false, true>;
+    LAUNCH_SLICED(ms_kernel, ms_sliced, a.nwin, kLrWin, 0, s, ix->dev, uoff, U, static_cast<const uint64_t *>(a.packed),
+                  static_cast<const int32_t *>(a.st), static_cast<const int32_t *>(a.fwd), uvirt, d_ms, reinterpret_cast<int2 *>(d_lohi));
+    return GENIE_OK;
+}
+
+// lr_pipeline with the correction and CS3 between LR2 and LR3
+int cs_pipeline(const genie_index *ix, const CsCall &cs, int mode, int min_len, const uint8_t *d_bases, const LongArea &a,
+                const long long *uoff, long long U, const long long *usrc, const int32_t *ushift, int64_t *offsets, int32_t *d_rows,
+                long long cap, hipStream_t s)
+{
+    HIP_TRY(hipMemsetAsync(a.entry, 0xFF, a.nwin * 4, s));
+    LAUNCH_BLOCKS(lr_pack_kernel, (a.nwords + 255) / 256, 256, 0, s, d_bases, uoff, U, usrc, a.nwords, a.packed, a.st);
+    const bool c16 = (ix->dev.flags & kFlagCompactTable) != 0;
+    const long long fwd_blocks = (a.nwin + kLrFwdWaves - 1) / kLrFwdWaves;
+    if (mode == GENIE_MODE_BWA) {
+        const auto fwd_kernel = c16 ? lr_fwd_kernel<true, true> : lr_fwd_kernel<false, true>;
+        const auto fwd_sliced = c16 ? lr_fwd_kernel<true, true, true> : lr_fwd_kernel<false, true, true>;
+        LAUNCH_SLICED(fwd_kernel, fwd_sliced, fwd_blocks, kLrFwdWaves * 64, 0, s, ix->dev, mode, uoff, U, a.nwin,
+                      static_cast<const uint64_t *>(a.packed), a.st, a.fwd, static_cast<int2 *>(nullptr),
+                      static_cast<uint8_t *>(nullptr), table_bytes(ix));
+    } else {
+        // LUT / RMI: a read shorter than K keeps its status only in the SMEM instance, which skips it; its marks go again
+        const auto fwd_one = c16 ? lr_fwd_kernel<true> : lr_fwd_kernel<false>;
+        const auto fwd_sliced = c16 ? lr_fwd_kernel<true, false, true> : lr_fwd_kernel<false, false, true>;
+        LAUNCH_SLICED(fwd_one, fwd_sliced, fwd_blocks, kLrFwdWaves * 64, 0, s, ix->dev, mode, uoff, U, a.nwin,
+                      static_cast<const uint64_t *>(a.packed), a.st, a.fwd, a.wmax, a.mark, table_bytes(ix));
+    }
+    if (a.total > 0) HIP_TRY(hipMemsetAsync(a.mark, 0, a.total, s));
+    if (int rc = cs_correct(ix, cs, true, a, uoff, U, s)) return rc;
+    LAUNCH_SLICED(cs_marks_kernel<false>, cs_marks_kernel<true>, fwd_blocks, kLrFwdWaves * 64, 0, s, uoff, U, a.nwin,
+                  static_cast<const int32_t *>(a.st), static_cast<const int32_t *>(a.fwd), a.wmax, a.mark);
+    LAUNCH_SLICED(lr_walk_kernel<false>, lr_walk_kernel<true>, a.nwin, kLrWin, 0, s, mode, min_len, uoff, U,
+                  static_cast<const int32_t *>(a.st), static_cast<const int32_t *>(a.fwd), static_cast<const int2 *>(a.wmax),
+                  static_cast<const uint8_t *>(a.mark), a.bst, a.jc);
+    LAUNCH_BLOCKS(lr_chain_kernel, (U + 255) / 256, 256, 0, s, uoff, U, a.st, a.jc, a.entry, a.base, a.cnt);
+    int rc = launch_compact(a.cnt, nullptr, U, 0x7fffffff, offsets, nullptr, 0, a.sums, s);
+    if (rc) return rc;
+    LAUNCH_BLOCKS(lr_emit_kernel, (a.nwin + 255) / 256, 256, 0, s, ix->dev, mode, min_len, uoff, U, a.nwin, a.packed, a.fwd, a.bst,
+                  a.entry, a.base, reinterpret_cast<const long long *>(offsets), ushift, reinterpret_cast<int4 *>(d_rows), cap);
+    return GENIE_OK;
+}
+
+// The tails: their parents', with cs_match_stats / cs_pipeline where those run lr_match_stats / lr_pipeline
+struct LuMsCtgTail {
+    static constexpr bool kSmems = false, kFwd = true;
+    LuMsTail t;
+    CsCall cs;
+
+    int empty() { return t.empty(); }
+    int whole(const LongArea &lr, const long long *uoff, const long long *usrc)
+    {
+        LAUNCH(lr_ms_edges_kernel, dim3(64), dim3(256), 0, t.s, t.off, t.N, t.S, t.positions, t.d_ms, reinterpret_cast<int2 *>(t.d_lohi));
+        int rc = cs_match_stats(t.ix, cs, t.d_bases, lr, uoff, t.S * t.N, usrc, nullptr, t.d_ms, t.d_lohi, t.s);
+        if (rc) return rc;
+        if (t.d_status) HIP_TRY(hipMemcpyAsync(t.d_status, lr.st, t.S * t.N * 4, hipMemcpyDeviceToDevice, t.s));
+        return GENIE_OK;
+    }
+    int broken(long long U) { return t.broken(U); }
+    int pass(const LuPass &p)
+    {
+        return cs_match_stats(t.ix, cs, t.d_bases, p.a.lr, p.a.uoff, p.p1 - p.p0, p.a.ub, p.a.ua, t.d_ms, t.d_lohi, t.s);
+    }
+};
+
+struct LuSmemCtgTail {
+    static constexpr bool kSmems = true, kFwd = true;
+    LuSmemTail t;
+    CsCall cs;
+
+    int empty() { return t.empty(); }
+    int whole(const LongArea &lr, const long long *uoff, const long long *usrc)
+    {
+        int rc = cs_pipeline(t.ix, cs, t.mode, t.min_len, t.d_bases, lr, uoff, t.SN, usrc, nullptr, t.d_offsets, t.d_rows,
+                             t.out_cap_rows, t.s);
+        if (rc) return rc;
+        if (t.d_status) HIP_TRY(hipMemcpyAsync(t.d_status, lr.st, t.SN * 4, hipMemcpyDeviceToDevice, t.s));
+        return GENIE_OK;
+    }
+    int broken(long long U) { return t.broken(U); }
+    int pass(const LuPass &p)
+    {
+        return t.pass_with(p, [&](const LongExPass &a, long long Cp, int32_t *rows, long long cap_left) {
+            return cs_pipeline(t.ix, cs, t.mode, t.min_len, t.d_bases, a.lr, a.uoff, Cp, a.ub, a.ushift,
+                               reinterpret_cast<int64_t *>(a.loff), rows, cap_left, t.s);
+        });
+    }
+};
+
+// The most units a pass of lu_run takes when the parent's part of the workspace has exactly its declared size: the
+// strand-reads without SPLIT_BREAKS, else what long_ex_pass_units, which lu_run asks too, finds for any number of units
+// (the padding of the pieces can admit a few more than long_ex_units)
+inline int64_t cs_units_cap(int64_t N, int64_t total, int32_t flags, bool smems)
+{
+    const int S = (flags & GENIE_READS_BOTH_STRANDS) ? 2 : 1;
+    const bool split = (flags & GENIE_READS_SPLIT_BREAKS) != 0;
+    const int64_t SN = std::max<int64_t>(1, (int64_t)S * N);
+    if (!split) return SN;
+    LongExFixed f;
+    const int64_t avail = long_ex_bytes(N, total, flags, smems) - long_ex_fixed_layout(nullptr, N, total, S, split, &f);
+    return long_ex_pass_units(SN, SN + (int64_t)S * total + 1, total, S, avail, smems, true);
+}
+
+inline int64_t cs_bytes(int64_t N, int64_t total, int32_t flags, bool smems, uint8_t *base, CsArea *a)
+{
+    const int S = (flags & GENIE_READS_BOTH_STRANDS) ? 2 : 1;
+    const int64_t parent = long_ex_bytes(N, total, flags, smems);
+    return parent + cs_layout(base ? base + parent : nullptr, (int64_t)S * total, cs_units_cap(N, total, flags, smems), a);
+}
+
+}  // namespace
+
+int64_t match_stats_contigs_workspace_bytes(int64_t N, int64_t total_bases, int32_t flags, int64_t n_contigs)
+{
+    (void)n_contigs;                                             // the table is the caller's and its samples live in LDS
+    CsArea a;
+    return cs_bytes(N, total_bases, flags, false, nullptr, &a);
+}
+
+int launch_match_stats_contigs(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs, int32_t flags,
+                               const uint8_t *d_bases, const int64_t *d_read_offsets, int64_t N, int64_t total_bases, int64_t max_len,
+                               int32_t *d_ms, int32_t *d_lohi, int32_t *d_status, int64_t *d_totals, void *d_ws, int64_t ws_bytes,
+                               void *stream)
+{
+    (void)ws_bytes;
+    hipStream_t s = (hipStream_t)stream;
+    const int S = (flags & GENIE_READS_BOTH_STRANDS) ? 2 : 1;
+    if (d_totals) HIP_TRY(hipMemsetAsync(d_totals, 0, 8, s));
+    LuMsCtgTail tail{{ix, d_bases, reinterpret_cast<const long long *>(d_read_offsets), (long long)N, S, (long long)S * total_bases,
+                      d_ms, d_lohi, d_status, s},
+                     {ctg_tab(d_contig_offsets, n_contigs), {}, reinterpret_cast<long long *>(d_totals)}};
+    if (N > 0) cs_bytes(N, total_bases, flags, false, static_cast<uint8_t *>(d_ws), &tail.cs.a);
+    return lu_run(ix, GENIE_MODE_BWA, flags, d_bases, d_read_offsets, N, total_bases, max_len, d_ws,
+                  long_ex_bytes(N, total_bases, flags, false), s, tail);
+}
+
+int64_t find_smems_contigs_workspace_bytes(int64_t N, int64_t total_bases, int32_t flags, int64_t n_contigs)
+{
+    (void)n_contigs;
+    CsArea a;
+    return cs_bytes(N, total_bases, flags, true, nullptr, &a);
+}
+
+int launch_find_smems_contigs(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs, int32_t mode, int32_t flags,
+                              const uint8_t *d_bases, const int64_t *d_read_offsets, int64_t N, int64_t total_bases, int64_t max_len,
+                              int32_t min_len, int64_t *d_offsets, int32_t *d_rows, int64_t out_cap_rows, int32_t *d_status,
+                              int64_t *d_totals, void *d_ws, int64_t ws_bytes, void *stream)
+{
+    (void)ws_bytes;
+    hipStream_t s = (hipStream_t)stream;
+    const int S = (flags & GENIE_READS_BOTH_STRANDS) ? 2 : 1;
+    if (d_totals) HIP_TRY(hipMemsetAsync(d_totals, 0, 8, s));
+    LuSmemCtgTail tail{{ix, mode, min_len, d_bases, (long long)S * N, d_offsets, d_rows, out_cap_rows, d_status, s},
+                       {ctg_tab(d_contig_offsets, n_contigs), {}, reinterpret_cast<long long *>(d_totals)}};
+    if (N > 0) cs_bytes(N, total_bases, flags, true, static_cast<uint8_t *>(d_ws), &tail.cs.a);
+    return lu_run(ix, mode, flags, d_bases, d_read_offsets, N, total_bases, max_len, d_ws, long_ex_bytes(N, total_bases, flags, true), s,
+                  tail);
+}

@@ -411,6 +411,17 @@ int launch_find_mems_contigs(const genie_index *ix, const int64_t *d_contig_offs
                              const uint8_t *d_bases, const int64_t *d_read_offsets, int64_t N, int64_t total_bases, int64_t max_len,
                              int32_t min_len, int32_t max_occ, int64_t *d_offsets, int32_t *d_rows, int64_t out_cap_rows,
                              int32_t *d_status, int64_t *d_totals, void *d_ws, int64_t ws_bytes, void *stream);
+// contig_stats.inc: matching statistics and SMEMs that are exact with respect to the sequence set
+int64_t match_stats_contigs_workspace_bytes(int64_t N, int64_t total_bases, int32_t flags, int64_t n_contigs);
+int launch_match_stats_contigs(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs, int32_t flags,
+                               const uint8_t *d_bases, const int64_t *d_read_offsets, int64_t N, int64_t total_bases, int64_t max_len,
+                               int32_t *d_ms, int32_t *d_lohi, int32_t *d_status, int64_t *d_totals, void *d_ws, int64_t ws_bytes,
+                               void *stream);
+int64_t find_smems_contigs_workspace_bytes(int64_t N, int64_t total_bases, int32_t flags, int64_t n_contigs);
+int launch_find_smems_contigs(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs, int32_t mode, int32_t flags,
+                              const uint8_t *d_bases, const int64_t *d_read_offsets, int64_t N, int64_t total_bases, int64_t max_len,
+                              int32_t min_len, int64_t *d_offsets, int32_t *d_rows, int64_t out_cap_rows, int32_t *d_status,
+                              int64_t *d_totals, void *d_ws, int64_t ws_bytes, void *stream);
 int64_t reads_from_text_tmp_bytes(int64_t text_bytes, int64_t cap_reads);
 int launch_reads_from_text(const uint8_t *d_text, int64_t text_bytes, int32_t format, int32_t flags, const uint8_t *code_of_byte,
                            uint8_t *d_bases, int64_t cap_bases, int64_t *d_read_offsets, int64_t cap_reads, int64_t *out5,

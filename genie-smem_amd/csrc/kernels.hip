@@ -1424,6 +1424,7 @@ int launch_locate(const genie_index *ix, const int32_t *d_lohi, int32_t stride, 
 #include "long_units.inc"
 #include "exact_match.inc"
 #include "contigs.inc"
+#include "contig_stats.inc"
 #include "mems.inc"
 #include "text_reads.inc"
 #include "fasta_reads.inc"

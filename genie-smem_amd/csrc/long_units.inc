@@ -324,6 +324,15 @@ inline int64_t long_ex_bytes(int64_t N, int64_t total_bases, int32_t flags, bool
            long_ex_pass_layout(nullptr, long_ex_units(N, total_bases, S, split), total_bases, S, split, &a, smems, fwd);
 }
 
+// Units per pass of lu_run when `avail` bytes follow the fixed part: as many as fit (at least S N: the caller sized the
+// workspace for that many), and no more than the U there are.  Whoever sizes a piece by the units of a pass asks here too.
+inline long long long_ex_pass_units(long long SN, long long U, int64_t total, int S, int64_t avail, bool smems, bool fwd)
+{
+    LongExPass a;
+    return pass_size(std::max<long long>(SN, 1), U,
+                     [&](long long c) { return long_ex_pass_layout(nullptr, c, total, S, true, &a, smems, fwd) <= avail; });
+}
+
 // One pass of at most C units, as the front hands it to a tail
 struct LuPass {
     const LuReads &R;
@@ -383,10 +392,7 @@ int lu_run(const genie_index *ix, int32_t mode, int32_t flags, const uint8_t *d_
     int rc = tail.broken(U);
     if (rc || U == 0) return rc;
     LongExPass a;
-    // units per pass: as many as the workspace holds (at least S N: the caller sized it for that many)
-    const long long C = pass_size(std::max<long long>(SN, 1), U, [&](long long c) {
-        return long_ex_pass_layout(nullptr, c, total_bases, S, true, &a, Tail::kSmems, Tail::kFwd) <= ws_bytes - fixed;
-    });
+    const long long C = long_ex_pass_units(SN, U, total_bases, S, ws_bytes - fixed, Tail::kSmems, Tail::kFwd);
     long_ex_pass_layout(pass, C, total_bases, S, true, &a, Tail::kSmems, Tail::kFwd);
     for (long long p0 = 0; p0 < U; p0 += C) {
         const long long p1 = std::min(U, p0 + C), Cp = p1 - p0;
@@ -435,12 +441,19 @@ struct LuSmemTail {
     }
     int pass(const LuPass &p)
     {
+        return pass_with(p, [&](const LongExPass &a, long long Cp, int32_t *rows, long long cap_left) {
+            return lr_pipeline(ix, mode, min_len, d_bases, a.lr, a.uoff, Cp, a.ub, a.ushift, reinterpret_cast<int64_t *>(a.loff), rows,
+                               cap_left, s);
+        });
+    }
+    // a pass whose rows come from pipeline(a, units, rows, room for rows): lr_pipeline, or a tail's own launch sequence
+    template <class F> int pass_with(const LuPass &p, F pipeline)
+    {
         const LongExPass &a = p.a;
         const long long Cp = p.p1 - p.p0;
         const bool last = p.p1 == p.U;
         const long long cap_left = std::max(0ll, (long long)out_cap_rows - row0);
-        int rc = lr_pipeline(ix, mode, min_len, d_bases, a.lr, a.uoff, Cp, a.ub, a.ushift, reinterpret_cast<int64_t *>(a.loff),
-                             cap_left > 0 ? d_rows + 4 * row0 : d_rows, cap_left, s);
+        int rc = pipeline(a, Cp, cap_left > 0 ? d_rows + 4 * row0 : d_rows, cap_left);
         if (rc) return rc;
         LAUNCH_BLOCKS(lu_offsets_kernel, (SN + 1 + 255) / 256, 256, 0, s, p.R, static_cast<const unsigned long long *>(p.f.bsum),
                static_cast<const int32_t *>(p.f.qloc), p.U, p.p0, p.p1, last, static_cast<const long long *>(a.loff), row0,

@@ -512,6 +512,60 @@ class GenieIndex:
         return self._find_mems("genie_find_mems_contigs", table, (table[1],), bases, read_offsets, min_len, both_strands,
                                split_breaks, max_occ, rows_hint)
 
+    def _csr_call(self, bases, read_offsets, both_strands, split_breaks):
+        """The CSR batch of the contig-exact calls on the device -> (bases, read_offsets, N, total, max_len, flags, S)."""
+        self._need_device()
+        bases = self._as_dev(bases, torch.uint8).reshape(-1)
+        read_offsets = self._as_dev(read_offsets, torch.int64).reshape(-1)
+        if read_offsets.numel() < 1:
+            raise ValueError("read_offsets needs N + 1 entries")
+        n_reads = read_offsets.numel() - 1
+        total = bases.numel()
+        max_len = int((read_offsets[1:] - read_offsets[:-1]).max().item()) if n_reads else 0
+        max_len = min(max(max_len, 0), 2**31 - 1)
+        if total == 0:
+            bases = torch.zeros(1, dtype=torch.uint8, device=self.device)
+        flags = (N.READS_BOTH_STRANDS if both_strands else 0) | (N.READS_SPLIT_BREAKS if split_breaks else 0)
+        return bases, read_offsets, n_reads, total, max_len, flags, 2 if both_strands else 1
+
+    def match_stats_contigs(self, contigs, bases, read_offsets, intervals=True, both_strands=False, split_breaks=False):
+        """match_stats that is exact with respect to a reference of several sequences (genie_match_stats_contigs; contigs:
+        the ReferenceSet this index was built from) -> (ms, lohi, status, clipped).  ms[v] is the longest match from that
+        position that lies inside ONE contig (the maximum over the contigs of the matching statistic against each alone),
+        lohi its inclusive interval in the concatenation -- it may hold bridging rows, which locate_contigs drops, and holds
+        at least one that does not --, status as match_stats, clipped the number of positions where ms is shorter than
+        match_stats's."""
+        off, table = self._contig_table(contigs)
+        bases, read_offsets, n_reads, total, max_len, flags, strands = self._csr_call(bases, read_offsets, both_strands, split_breaks)
+        ms = torch.empty(strands * total, dtype=torch.int32, device=self.device)
+        lohi = torch.empty((strands * total, 2), dtype=torch.int32, device=self.device) if intervals else None
+        status = torch.empty(strands * n_reads, dtype=torch.int32, device=self.device)
+        totals = torch.zeros(1, dtype=torch.int64, device=self.device)
+        ws, ws_bytes = self._workspace("genie_match_stats_contigs_workspace_bytes", n_reads, total, max_len, flags, table[1])
+        self._run("genie_match_stats_contigs", *table, flags, _ptr(bases), _ptr(read_offsets), n_reads, total, max_len, _ptr(ms),
+                  _ptr(lohi), _ptr(status), _ptr(totals), _ptr(ws), ws_bytes)
+        return ms, lohi, status, int(totals.item())
+
+    def find_smems_contigs(self, contigs, mode, bases, read_offsets, min_len=1, rows_hint=None, both_strands=False,
+                           split_breaks=False):
+        """find_smems_long whose rows are the SMEMs with respect to the SET of sequences (genie_find_smems_contigs; contigs:
+        the ReferenceSet this index was built from) -> (offsets, smems int32[S, 4], status, clipped).  The rows are what the
+        traversal gives on the contig-exact matching statistics: (lo, hi) is the interval of the row's bases in the
+        concatenation and at least one of its occurrences lies inside one contig, so every row has a hit in locate_contigs.
+        Options, row order and status as find_smems_long; clipped as match_stats_contigs.  If the rows outnumber rows_hint
+        the call is made again with room for all."""
+        if split_breaks and mode != "bwa":
+            raise ValueError("split_breaks needs mode 'bwa' (genie_find_smems_split has no other traversal)")
+        off, table = self._contig_table(contigs)
+        bases, read_offsets, n_reads, total, max_len, flags, strands = self._csr_call(bases, read_offsets, both_strands, split_breaks)
+        totals = torch.zeros(1, dtype=torch.int64, device=self.device)
+        ws, ws_bytes = self._workspace("genie_find_smems_contigs_workspace_bytes", n_reads, total, max_len, flags, table[1])
+        offsets, rows, status = self._run_csr("genie_find_smems_contigs", (*table, N.MODES[mode], flags, _ptr(bases), _ptr(read_offsets),
+                                                                           n_reads, total, max_len, int(min_len)),
+                                              strands * n_reads, int(rows_hint) if rows_hint else strands * max(8 * n_reads, total // 6),
+                                              (_ptr(totals), _ptr(ws), ws_bytes))
+        return offsets, rows, status, int(totals.item())
+
     def locate_contigs(self, contigs, rows):
         """SMEM rows int32 [S, 4] (start, end, lo, hi) of any find_smems* call -> (hit_offsets int64[S+1], hits int32[T, 2]
         = (contig, 1-based offset inside it), dropped) (genie_locate_contigs).  The rows stay SMEMs of the concatenation;

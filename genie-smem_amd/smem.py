@@ -200,6 +200,33 @@ class SMEM:
         sequences are dropped."""
         return self.matcher.index(self.lut.lut_size).locate_contigs(contigs, rows)
 
+    def _csr_reads(self, reads, split_breaks):
+        """list[str] or (bases, read_offsets) -> (bases, read_offsets), strings encoded as match_stats encodes them."""
+        if isinstance(reads, tuple):
+            return reads
+        encode = self.matcher.encode_lenient if split_breaks else self.matcher.encode
+        enc = [encode(r) for r in reads]
+        read_offsets = np.zeros(len(enc) + 1, np.int64)
+        read_offsets[1:] = np.cumsum([len(e) for e in enc]) if enc else []
+        return (np.concatenate(enc).astype(np.uint8) if enc else np.zeros(0, np.uint8)), read_offsets
+
+    def match_stats_contigs(self, contigs, reads, intervals=True, both_strands=False, split_breaks=False):
+        """match_stats that is exact with respect to a reference of several sequences (genie_match_stats_contigs): contigs is
+        the ReferenceSet whose concatenation this matcher's reference is.  reads as match_stats.  -> (ms, lohi, status,
+        clipped): ms the longest match from each position that lies inside ONE contig, lohi its interval in the concatenation,
+        clipped the number of positions where that is shorter than match_stats's answer."""
+        bases, read_offsets = self._csr_reads(reads, split_breaks)
+        return self.matcher.index(self.lut.lut_size).match_stats_contigs(contigs, bases, read_offsets, intervals, both_strands,
+                                                                         split_breaks)
+
+    def find_smems_contigs(self, contigs, reads, minimum_length=1, mode="bwa", both_strands=False, split_breaks=False):
+        """find_smems_long whose rows are the SMEMs with respect to the SET of sequences (genie_find_smems_contigs): no row
+        relies on a match that bridges two contigs, so every row has a hit in locate_contigs.  reads and options as
+        find_smems_long.  -> (offsets, smems[S, 4], status, clipped)."""
+        bases, read_offsets = self._csr_reads(reads, split_breaks)
+        return self.matcher.index(self.lut.lut_size).find_smems_contigs(contigs, mode, bases, read_offsets, minimum_length,
+                                                                        both_strands=both_strands, split_breaks=split_breaks)
+
     def match_stats_text(self, data, fmt="lines", intervals=True, both_strands=False, split_breaks=True, fold_case=False):
         """match_stats of the reads in a text (find_smems_text's formats and translation) -> (ms, lohi, status,
         read_offsets): read_offsets int64[N+1] on the device, to index the flat arrays with."""

@@ -581,6 +581,78 @@ int genie_locate_contigs(const genie_index *ix, const int64_t *d_contig_offsets,
 int genie_contig_coords(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs, const int32_t *d_pos,
                         int32_t stride, int64_t count, int32_t *d_out /* 2 * count */, void *stream);
 
+/* Matching statistics and SMEMs that are EXACT WITH RESPECT TO THE SEQUENCE SET.  genie_match_stats and the SMEM calls on a
+ * reference of several sequences answer for the concatenation; genie_locate_contigs then drops the occurrences that bridge
+ * two sequences, and with them seeds.  Contigs ACGT | TTGA and the read CGTT: the concatenation holds CGTT once, across the
+ * boundary; the only SMEM is (0, 4), its only occurrence is dropped, the read has no hit.  Against the set the read has the
+ * SMEMs (0, 3) (CGT in contig 0) and (2, 4) (TT in contig 1).  These two calls give the second answer.
+ * Arguments: those of genie_match_stats / genie_find_smems_long_ex with the table (above) behind ix and d_totals behind
+ * d_status.  Reads, flags, strand-reads, virtual positions, breaks, the offset check and the statuses are the parents'.
+ * Definition.  ms_c[v], the contig-exact matching statistic, is the largest l >= 0 for which the l bases of the strand-read
+ * from p on hold no break and equal T[t .. t+l) for some t with l <= room(t): they occur inside one contig.  Equivalently
+ * the maximum over the contigs of the matching statistic against that contig alone.  Four facts:
+ *   1  ms_c[v] <= ms[v], and ms_c[v] >= 1 iff ms[v] >= 1, because an occurrence t < n has room(t) >= 1: GENIE_READ_ABSENT_BASE
+ *      and GENIE_READ_BAD_BASE are flagged exactly as by the parents.
+ *   2  ms_c[v+1] >= ms_c[v] - 1 inside a strand-read, so fwd_c[p] = p + ms_c[p] is non-decreasing: the BWA traversal applies
+ *      unchanged and yields the SMEMs with respect to the sequence set.
+ *   3  Let p0 be a run start of the concatenation's fwd[] (p0 = 0 or fwd[p0] != fwd[p0-1]).  If some occurrence t of
+ *      Q[p0 .. fwd[p0]) has room(t) >= fwd[p0] - p0, then ms_c = ms at every position of the run (occurrence t + k serves
+ *      position p0 + k): only run starts need an interval and a room test, a handful per 150-base read.
+ *   4  If no occurrence of the run start qualifies, the positions of the run are resolved one by one: "some t in the
+ *      interval of Q[p .. p+l) has room(t) >= l" is monotone in l, so ms_c[p] is the largest l in [largest room seen, ms[p])
+ *      for which it holds, found by bisection over l.
+ * genie_match_stats_contigs writes d_ms[v] = ms_c[v] and, unless d_lohi is NULL, d_lohi[v] = the inclusive interval IN THE
+ * CONCATENATION of those ms_c[v] bases, what genie_sa_interval returns for them: it may still hold bridging rows, at least
+ * one of its rows does not bridge, genie_locate_contigs drops the others; (-1, -1) where ms_c = 0.  Bad-base strand-reads
+ * get -1 and (-1, -1) as in the parent.
+ * genie_find_smems_contigs writes the rows (start, end, lo, hi) that the BWA traversal produces from fwd_c, min_len and mode
+ * as genie_find_smems_long_ex takes them (GENIE_READS_SPLIT_BREAKS needs GENIE_MODE_BWA); (lo, hi) is the interval of
+ * Q[start .. end) in the concatenation.  Row order, d_offsets, out_cap_rows, the sizing behaviour and the unit passes are
+ * the parent's.  Every row has at least one hit in genie_locate_contigs.
+ *   d_totals   (1 int64, 8-byte aligned, may be NULL) the number of virtual positions with ms_c < ms: the positions that were
+ *              clipped (genie_find_smems_contigs: those of the strand-reads that are not flagged, the only ones with rows).
+ *              It stays on the device; no synchronisation is added for it.
+ * With n_contigs == 1 both calls give the outputs of genie_match_stats and genie_find_smems_long_ex byte for byte.
+ * Against genie_find_mems_contigs (same flags, min_len m): no row is longer than ms_c at its start, and at a run start of
+ * fwd_c (p == 0 or fwd_c[p] != fwd_c[p-1]) with ms_c >= m the longest row that starts there is ms_c long.  At other
+ * positions the longest contig-exact match can be extended to the left and need not be a row: MEMs are left-maximal.
+ * Checks, all before the device check: the parent's, in its order (GENIE_E_INVALID; an unknown flag bit included), then a
+ * misaligned d_totals and the table's (GENIE_E_INVALID, GENIE_E_TOO_LONG for n_contigs above 2^31 - 2), then for N > 0 a
+ * workspace that is null, not 256-byte aligned or smaller than the size function's value (GENIE_E_CAPACITY), then
+ * GENIE_E_NO_DEVICE on a host-only handle.  The table is NOT validated; the calls are memory-safe on any table contents.
+ * The workspace functions return GENIE_E_INVALID for what the call refuses, are multiples of 256, monotone in every argument
+ * and at least the parent's size for the same batch: the parent's plus 8 S bytes per base (the slow list's slots), 6 per
+ * window of 256 positions and per unit (the flagged run starts per window and per four windows) and 8 KB (clip counts).  The parent's part is
+ * used at its declared size: a larger workspace does not widen the unit passes.
+ * Kernels: the parent's pack and forward stages give fwd[] of the concatenation; one kernel tests every run start (its
+ * interval, then SaRec.s of its rows with early exit, one lane up to 32 rows and the whole wave beyond, room through the
+ * staged table) and appends the failing ones to a slow list placed by window counts and a scan; a second, rare, kernel
+ * resolves the positions of those runs by fact 4 and rewrites their fwd[]; then the parent's statistics kernel, or a small
+ * kernel that rebuilds the window maxima and marks followed by the parent's traversal, run over the corrected fwd[].  No
+ * atomic decides a value.  Synchronisations of `stream`: the parents' and no more.
+ * Cost: the parent's plus, per run start, one interval and its rows up to the first that has room; a flagged run costs per
+ * position a few interval searches (one at ms, a gallop up from the largest room seen, at most log2(ms) more), each
+ * followed by a walk of that interval's rows -- all of them where none has room, so a reference of very many very short contigs under long matches is the expensive case. */
+int64_t genie_match_stats_contigs_workspace_bytes(int64_t N, int64_t total_bases, int64_t max_len, int32_t flags, int64_t n_contigs);
+int genie_match_stats_contigs(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs, int32_t flags,
+                              const uint8_t *d_bases, const int64_t *d_read_offsets, int64_t N, int64_t total_bases,
+                              int64_t max_len,
+                              int32_t *d_ms,           /* S * total_bases */
+                              int32_t *d_lohi,         /* 2 * S * total_bases, may be NULL */
+                              int32_t *d_status,       /* S * N, may be NULL */
+                              int64_t *d_totals,       /* 1, may be NULL: positions clipped */
+                              void *d_workspace, int64_t workspace_bytes, void *stream);
+int64_t genie_find_smems_contigs_workspace_bytes(int64_t N, int64_t total_bases, int64_t max_len, int32_t flags, int64_t n_contigs);
+int genie_find_smems_contigs(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs, int32_t mode,
+                             int32_t flags, const uint8_t *d_bases, const int64_t *d_read_offsets, int64_t N,
+                             int64_t total_bases, int64_t max_len, int32_t min_len,
+                             int64_t *d_offsets,      /* S * N + 1 */
+                             int32_t *d_rows,         /* 4 * out_cap_rows, 16-byte aligned */
+                             int64_t out_cap_rows,
+                             int32_t *d_status,       /* S * N, may be NULL */
+                             int64_t *d_totals,       /* 1, may be NULL: positions clipped */
+                             void *d_workspace, int64_t workspace_bytes, void *stream);
+
 /* Reads from TEXT, on the device: the bytes of a file of reads -> the d_bases / d_read_offsets that genie_find_smems_long_ex
  * takes.  The reference has no counterpart (its reads are Python strings); this replaces encoding every string on the host.
  * Lines.  A line ends at a '\n' (0x0A), which is not part of it; if the line is then not empty and its last byte is '\r',
