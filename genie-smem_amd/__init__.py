@@ -12,8 +12,8 @@ from .lut import LUT
 from .rmi import RMI
 from .rmi_lut import RMI_LUT
 from .smem import SMEM, create_query_from_ref, create_random_query
-from .contigs import ReferenceSet
+from .contigs import ReferenceSet, SegmentedReferenceSet, reference_segments
 from . import packing, parallel, text_reads
 
-__all__ = ["ExactMatch", "LUT", "RMI", "RMI_LUT", "SMEM", "GenieIndex", "ReferenceSet", "parallel", "packing", "text_reads", "_native",
-           "create_query_from_ref", "create_random_query"]
+__all__ = ["ExactMatch", "LUT", "RMI", "RMI_LUT", "SMEM", "GenieIndex", "ReferenceSet", "SegmentedReferenceSet", "reference_segments",
+           "parallel", "packing", "text_reads", "_native", "create_query_from_ref", "create_random_query"]

@@ -34,6 +34,8 @@ READS_BOTH_STRANDS, READS_SPLIT_BREAKS = 1, 2       # flags of genie_find_smems_
 TEXT_LINES, TEXT_FASTQ = 0, 1                       # formats of genie_reads_from_text
 TEXT_FORMATS = {"lines": TEXT_LINES, "fastq": TEXT_FASTQ}
 TEXT_PARTIAL = 1                                    # its flag
+SEG_POSITIONS, SEG_HITS = 0, 1                      # forms of genie_segment_coords
+SEG_FORMS = {"positions": SEG_POSITIONS, "hits": SEG_HITS}
 
 # every symbol include/genie_smem.h declares (tests check the library exports all of them)
 SYMBOLS = [
@@ -55,6 +57,7 @@ SYMBOLS = [
     "genie_find_smems_contigs", "genie_find_smems_contigs_workspace_bytes",
     "genie_reads_from_text", "genie_reads_from_text_tmp_bytes",
     "genie_reads_from_fasta", "genie_reads_from_fasta_tmp_bytes",
+    "genie_reference_segments", "genie_reference_segments_tmp_bytes", "genie_segment_coords",
     "genie_compact_tmp_bytes",
     "genie_compact_smems", "genie_locate_tmp_bytes", "genie_locate", "genie_index_train_rmi", "genie_index_rmi_models", "genie_launch_info", "genie_search_kernel_name", "genie_index_set_option", "genie_index_set_stage_events", "genie_strerror", "genie_last_hip_error",
 ]
@@ -77,7 +80,7 @@ class GenieError(RuntimeError):
 
 def build(force=False):
     """Compile libgenie_smem.so for gfx950 with hipcc (csrc/Makefile), in-tree."""
-    srcs = [os.path.join(CSRC, f) for f in ("kernels.hip", "index_build.hip", "short_read_kernel.inc", "match_table_kernel.inc", "match_table_body.inc", "match_table_long_body.inc", "split_reads.inc", "long_reads.inc", "long_units.inc", "exact_match.inc", "contigs.inc", "contig_stats.inc", "mems.inc", "text_reads.inc", "fasta_reads.inc", "capi.cpp", "index_host.cpp", "genie_internal.h", "Makefile")]
+    srcs = [os.path.join(CSRC, f) for f in ("kernels.hip", "index_build.hip", "short_read_kernel.inc", "match_table_kernel.inc", "match_table_body.inc", "match_table_long_body.inc", "split_reads.inc", "long_reads.inc", "long_units.inc", "exact_match.inc", "contigs.inc", "contig_stats.inc", "mems.inc", "text_reads.inc", "fasta_reads.inc", "segments.inc", "capi.cpp", "index_host.cpp", "genie_internal.h", "Makefile")]
     srcs.append(os.path.join(os.path.dirname(_PKG), "include", "genie_smem.h"))
     newest = max(os.path.getmtime(s) for s in srcs)
     if force or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < newest:
@@ -158,6 +161,9 @@ def lib():
         "genie_reads_from_text": (C.c_int, [vp, i64, i32, i32, vp, vp, i64, vp, i64, vp, vp, i64, vp]),
         "genie_reads_from_fasta_tmp_bytes": (i64, [i64, i64]),
         "genie_reads_from_fasta": (C.c_int, [vp, i64, i32, vp, vp, i64, vp, vp, i64, vp, vp, i64, vp]),
+        "genie_reference_segments_tmp_bytes": (i64, [i64, i64]),
+        "genie_reference_segments": (C.c_int, [vp, i64, vp, i64, vp, i64, vp, vp, vp, i64, vp, vp, i64, vp]),
+        "genie_segment_coords": (C.c_int, [vp, vp, vp, vp, i64, i32, vp, i32, i64, vp, vp]),
         "genie_compact_tmp_bytes": (i64, [i64]),
         "genie_compact_smems": (C.c_int, [vp, vp, i64, i32, vp, vp, i64, vp, vp]),
         "genie_index_train_rmi": (C.c_int, [vp, i32, vp, vp, vp]),

@@ -736,6 +736,48 @@ int genie_reads_from_fasta(const uint8_t *d_text, int64_t text_bytes, int32_t fl
                                    out5, d_tmp, stream);
 }
 
+int64_t genie_reference_segments_tmp_bytes(int64_t n_given, int64_t n_records)
+{
+    if (n_given < 0 || n_records < 0) return (int64_t)GENIE_E_INVALID;
+    return reference_segments_tmp_bytes(n_given, n_records);
+}
+
+int genie_reference_segments(const uint8_t *d_codes, int64_t n_given, const int64_t *d_record_offsets, int64_t n_records,
+                             uint8_t *d_bases, int64_t cap_bases, int64_t *d_seg_offsets, int32_t *d_seg_record, int64_t *d_seg_origin,
+                             int64_t cap_segs, int64_t *out4, void *d_tmp, int64_t tmp_bytes, void *stream)
+{
+    // argument checks first: they need no device
+    if (n_given < 0 || tmp_bytes < 0 || n_records < 1 || !out4 || (n_given > 0 && !d_codes)) return GENIE_E_INVALID;
+    if (!d_record_offsets && n_records != 1) return GENIE_E_INVALID;
+    const int outputs = (d_bases != nullptr) + (d_seg_offsets != nullptr) + (d_seg_record != nullptr) + (d_seg_origin != nullptr);
+    if (outputs != 0 && outputs != 4) return GENIE_E_INVALID;
+    if (outputs && (cap_bases < 0 || cap_segs < 0)) return GENIE_E_INVALID;      // the sizing call does not look at them
+    if (((reinterpret_cast<uintptr_t>(d_record_offsets) | reinterpret_cast<uintptr_t>(d_seg_offsets) |
+          reinterpret_cast<uintptr_t>(d_seg_origin)) & 7) != 0 || (reinterpret_cast<uintptr_t>(d_seg_record) & 3) != 0)
+        return GENIE_E_INVALID;
+    if (n_records > 0x7fffffffll) return GENIE_E_TOO_LONG;             // d_seg_record is int32
+    if (!d_tmp || (reinterpret_cast<uintptr_t>(d_tmp) & 255) != 0 || tmp_bytes < reference_segments_tmp_bytes(n_given, n_records))
+        return GENIE_E_CAPACITY;
+    return launch_reference_segments(d_codes, n_given, d_record_offsets, n_records, d_bases, cap_bases, d_seg_offsets, d_seg_record,
+                                     d_seg_origin, cap_segs, out4, d_tmp, stream);
+}
+
+int genie_segment_coords(const genie_index *ix, const int64_t *d_seg_offsets, const int32_t *d_seg_record, const int64_t *d_seg_origin,
+                         int64_t n_segs, int32_t form, const int32_t *d_in, int32_t stride, int64_t count, int64_t *d_out, void *stream)
+{
+    // argument checks first: they need no device image
+    if (!ix) return GENIE_E_INVALID;
+    if (form != GENIE_SEG_POSITIONS && form != GENIE_SEG_HITS) return GENIE_E_INVALID;
+    if (count < 0 || stride < (form == GENIE_SEG_HITS ? 2 : 1) || (count > 0 && (!d_in || !d_out))) return GENIE_E_INVALID;
+    if ((reinterpret_cast<uintptr_t>(d_in) & 3) != 0 || (reinterpret_cast<uintptr_t>(d_out) & 15) != 0) return GENIE_E_INVALID;
+    if (!d_seg_record || !d_seg_origin || (reinterpret_cast<uintptr_t>(d_seg_record) & 3) != 0 ||
+        (reinterpret_cast<uintptr_t>(d_seg_origin) & 7) != 0)
+        return GENIE_E_INVALID;
+    int rc = contig_args(d_seg_offsets, n_segs);
+    if (rc || (rc = ready(ix))) return rc;
+    return launch_segment_coords(ix, d_seg_offsets, d_seg_record, d_seg_origin, n_segs, form, d_in, stride, count, d_out, stream);
+}
+
 static int find_smems_packed_any(const genie_index *ix, int32_t mode, const uint8_t *d_reads2bit, const int32_t *d_lens, int64_t N,
                                  int32_t stride_bytes, int32_t fixed_len, int32_t min_len, uint8_t *d_counts8, uint8_t *d_status8,
                                  void *d_rows, int64_t out_cap_rows, int64_t *d_totals, int64_t *d_escapes, int64_t cap_escapes,

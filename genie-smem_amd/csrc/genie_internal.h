@@ -430,6 +430,13 @@ int64_t reads_from_fasta_tmp_bytes(int64_t text_bytes, int64_t cap_reads);
 int launch_reads_from_fasta(const uint8_t *d_text, int64_t text_bytes, int32_t flags, const uint8_t *code_of_byte, uint8_t *d_bases,
                             int64_t cap_bases, int64_t *d_read_offsets, int64_t *d_record_starts, int64_t cap_reads, int64_t *out5,
                             void *d_tmp, void *stream);
+// segments.inc: a reference with ambiguous bases, cut into segments
+int64_t reference_segments_tmp_bytes(int64_t n_given, int64_t n_records);
+int launch_reference_segments(const uint8_t *d_codes, int64_t n_given, const int64_t *d_record_offsets, int64_t n_records,
+                              uint8_t *d_bases, int64_t cap_bases, int64_t *d_seg_offsets, int32_t *d_seg_record, int64_t *d_seg_origin,
+                              int64_t cap_segs, int64_t *out4, void *d_tmp, void *stream);
+int launch_segment_coords(const genie_index *ix, const int64_t *d_seg_offsets, const int32_t *d_seg_record, const int64_t *d_seg_origin,
+                          int64_t n_segs, int32_t form, const int32_t *d_in, int32_t stride, int64_t count, int64_t *d_out, void *stream);
 int launch_find_smems_packed(const genie_index *ix, int32_t mode, const FindBatch &b, uint8_t *d_counts8, uint8_t *d_status8,
                              void *d_rows8, int64_t out_cap_rows, int64_t *d_totals, int64_t *d_escapes, int64_t cap_escapes,
                              void *stream, int row_bytes = 8);

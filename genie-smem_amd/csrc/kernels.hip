@@ -1428,5 +1428,6 @@ int launch_locate(const genie_index *ix, const int32_t *d_lohi, int32_t stride, 
 #include "mems.inc"
 #include "text_reads.inc"
 #include "fasta_reads.inc"
+#include "segments.inc"
 
 }  // namespace genie

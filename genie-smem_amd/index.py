@@ -599,6 +599,28 @@ class GenieIndex:
         self._run("genie_contig_coords", *table, _ptr(pos), stride, count, _ptr(out))
         return out
 
+    def segment_coords(self, segments, values, form="positions", stride=None):
+        """Squeezed coordinates -> int64 [count, 2] = (record, 1-based offset inside the GIVEN record, breaks counted) on
+        the device (genie_segment_coords; segments: the SegmentedReferenceSet this index was built from).  form
+        "positions": values are 1-based positions in the squeezed concatenation, int32, flat, every stride-th taken
+        (default 1); form "hits": values are locate_contigs hits [T, 2] = (segment, 1-based offset inside it), stride
+        (default 2) int32 values apart.  (-1, -1) for a position outside [1, n], a segment outside the table or an offset
+        outside its segment."""
+        off, table = self._contig_table(segments)
+        if form not in N.SEG_FORMS:
+            raise ValueError(f"form must be one of {sorted(N.SEG_FORMS)}, got {form!r}")
+        least = 2 if form == "hits" else 1
+        stride = least if stride is None else int(stride)
+        if stride < least:
+            raise ValueError(f"stride must be at least {least}")
+        values = self._as_dev(values, torch.int32).reshape(-1)
+        count = (values.numel() + stride - 1) // stride if form == "positions" else (values.numel() + stride - 2) // stride
+        rec, org = segments.device_segments(self.device)
+        out = torch.empty((count, 2), dtype=torch.int64, device=self.device)
+        self._run("genie_segment_coords", table[0], _ptr(rec), _ptr(org), table[1], N.SEG_FORMS[form], _ptr(values), stride, count,
+                  _ptr(out))
+        return out
+
     def exact_match(self, bases, pattern_offsets, both_strands=False, counts=False):
         """Suffix-array interval of every pattern of a CSR batch (genie_exact_match) -> (lohi int32[S*N, 2], counts
         int32[S*N] or None without counts=True, status int32[S*N]) on the device, S = 2 with both_strands, else 1.  bases:

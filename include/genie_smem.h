@@ -728,6 +728,71 @@ int genie_reads_from_fasta(const uint8_t *d_text, int64_t text_bytes, int32_t fl
                            int64_t *out5 /* host */,
                            void *d_tmp, int64_t tmp_bytes, void *stream);
 
+/* A reference with AMBIGUOUS BASES (N runs, IUPAC codes), cut into segments on the device.  genie_index_create* refuses a
+ * code > 3 (GENIE_E_ALPHABET) and keeps doing so.  Instead every break is removed, the index is built over what is left,
+ * the SQUEEZED concatenation, the maximal A/C/G/T runs go to the *_contigs calls as the contig table -- no match covers a
+ * break or runs from one side of it to the other, which is what those calls guarantee for contig boundaries -- and
+ * genie_segment_coords names every position in the coordinates of the reference as it was given, breaks counted.
+ * Definitions.  The GIVEN reference is d_codes[0 .. n_given) (uint8, any alignment) with a record table d_record_offsets:
+ *   n_records + 1 int64 values on the device, 8-byte aligned, by the contig-table convention (off[0] = 0, non-decreasing,
+ *   off[n_records] = n_given; record r is [off[r], off[r+1]), empty records allowed; the record of position i is the last
+ *   r with off[r] <= i).  d_record_offsets == NULL is allowed with n_records == 1 and means one record [0, n_given).
+ * A BREAK is a position whose code is > 3 (any byte 4 .. 255): the convention of the read calls and of what
+ *   genie_reads_from_fasta's translation leaves for a letter that is no base.
+ * A SEGMENT is a maximal run of non-break positions inside one record: it ends at a break, at its record's end or at
+ *   n_given.  Segments are numbered in the order of their positions.  A record without a kept base has no segment; the
+ *   other segments still carry their record's number.
+ * Outputs:
+ *   d_bases            the stream compaction of the non-break bytes: the squeezed concatenation (n_kept bytes);
+ *   d_seg_offsets[s]   the kept bytes in front of segment s, [n_seg] = n_kept: a valid contig table of d_bases;
+ *   d_seg_record[s]    the record of segment s;  d_seg_origin[s]  the 0-based offset of its first base INSIDE that record;
+ *   out4 (host)        {n_seg, n_kept, longest segment, table error mask}: the mask is 0 for a valid table, else bit 1 for
+ *                      off[0] != 0, 2 for a decrease, 4 for off[n_records] != n_given (genie_contigs_validate's conditions).
+ * Sizing: with all four output pointers NULL only out4 is produced and the capacities are not looked at.  Otherwise
+ *   n_seg > cap_segs or n_kept > cap_bases gives GENIE_E_CAPACITY: out4 holds the true values and nothing is stored
+ *   (d_seg_offsets holds cap_segs + 1 values).  cap_bases = n_given and cap_segs = (n_given + 1) / 2 suffice for ONE record;
+ *   a record boundary without a break on it starts a segment too, so with records cap_segs = n_given always suffices.
+ * A bad table gives GENIE_E_INVALID, found on the device and reported before a capacity, with its bits in out4[3] and
+ *   out4[0 .. 2] = 0; nothing is stored, and no load leaves d_codes or the table whatever the table holds.
+ * Checked before any device work, GENIE_E_INVALID: a null d_codes with n_given > 0, a null out4, a negative n_given,
+ *   tmp_bytes or (unless sizing) capacity, n_records < 1, a NULL table with n_records != 1, some but not all output
+ *   pointers NULL, a table, d_seg_offsets or d_seg_origin that is not 8-byte or a d_seg_record that is not 4-byte aligned;
+ *   GENIE_E_TOO_LONG for n_records above 2^31 - 1 (d_seg_record is int32); then GENIE_E_CAPACITY for a d_tmp that is null,
+ *   not 256-byte aligned or smaller than genie_reference_segments_tmp_bytes(n_given, n_records): 32 bytes per 4096 of given
+ *   reference, nothing per record; GENIE_E_INVALID for a negative argument, a multiple of 256, monotone in both.
+ * Every position, n_given included, is 64-bit; n_kept >= 2^31 is reported as it is (the index builder refuses it, not the
+ *   squeeze).  `stream` is synchronised once, at the end.  Two streaming passes over the given codes in tiles of 4096
+ *   bytes; the record boundaries inside a tile are resolved once per tile (two bisections of the table, then one bit per
+ *   boundary in LDS), nothing per byte.  No atomic decides a value: the outputs are a function of the inputs alone. */
+int64_t genie_reference_segments_tmp_bytes(int64_t n_given, int64_t n_records);
+int genie_reference_segments(const uint8_t *d_codes, int64_t n_given,
+                             const int64_t *d_record_offsets /* may be NULL */, int64_t n_records,
+                             uint8_t *d_bases, int64_t cap_bases,
+                             int64_t *d_seg_offsets /* cap_segs + 1 */, int32_t *d_seg_record, int64_t *d_seg_origin,
+                             int64_t cap_segs,
+                             int64_t *out4 /* host */,
+                             void *d_tmp, int64_t tmp_bytes, void *stream);
+
+/* Squeezed coordinates -> coordinates in the GIVEN reference.  ix: the index over d_bases; the three segment arrays as
+ * genie_reference_segments wrote them, n_segs = n_seg.  Input, int32, element i at d_in[i * stride]:
+ *   GENIE_SEG_POSITIONS  a 1-based position in the squeezed concatenation (MEM rows' pos with stride 4, genie_locate);
+ *   GENIE_SEG_HITS       d_in[i*stride], d_in[i*stride + 1] = (segment, 1-based offset inside it): the hits of
+ *                        genie_locate_contigs with the segment table; stride >= 2.
+ * Output d_out[2 i], d_out[2 i + 1] (int64, 16-byte aligned) = (record, 1-based offset inside the GIVEN record, breaks
+ * counted) = (d_seg_record[s], d_seg_origin[s] + offset in segment s); (-1, -1) for a position outside [1, n], a segment
+ * outside [0, n_segs) or an offset outside its segment.  The positions form finds s with the LDS-staged bisection of the
+ * contig calls; the hits form is a gather.  One lane per element, no synchronisation of `stream`.
+ * Checks, before the device check: a null ix, an unknown form, count < 0, stride < 1 (< 2 for hits), a null d_in or
+ * d_out with count > 0, a d_in that is not 4-byte or a d_out that is not 16-byte aligned, a null or misaligned segment
+ * array or n_segs < 1 give GENIE_E_INVALID, n_segs above 2^31 - 2 GENIE_E_TOO_LONG.  d_seg_record is only copied, never
+ * followed; the call is memory-safe on any table contents (undefined values for a table genie_contigs_validate refuses). */
+#define GENIE_SEG_POSITIONS 0
+#define GENIE_SEG_HITS 1
+int genie_segment_coords(const genie_index *ix, const int64_t *d_seg_offsets, const int32_t *d_seg_record,
+                         const int64_t *d_seg_origin, int64_t n_segs, int32_t form,
+                         const int32_t *d_in, int32_t stride, int64_t count,
+                         int64_t *d_out /* 2 * count, 16-byte aligned */, void *stream);
+
 /* The same discovery for callers on the far side of a host link (SMEM.find_smems_* on host arrays): 2-bit packed reads in,
  * 8-byte rows out -- 40 instead of 150 bytes per 150-base read over PCIe, 8 instead of 16 per SMEM.  Reads of at most 255
  * bases.  Row r of d_reads2bit = stride_bytes bytes (a multiple of 4, >= 4 * ceil(max length / 16)): byte i holds bases
