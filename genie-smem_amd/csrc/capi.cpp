@@ -439,10 +439,43 @@ int genie_find_smems_long(const genie_index *ix, int32_t mode, const uint8_t *d_
                                     out_cap_rows, d_status, d_workspace, workspace_bytes, stream);
 }
 
+// ---- The CSR calls: a batch of reads as one buffer of bases and 64-bit offsets (CsrBatch).  What they check alike is written
+// once, below; what a call checks on its own stands in the call.  Everywhere a bad argument (GENIE_E_INVALID, and for a
+// contig table GENIE_E_TOO_LONG) comes before a capacity, and the device image and the tables of a mode are looked at last.
+constexpr int32_t kReadFlags = GENIE_READS_BOTH_STRANDS | GENIE_READS_SPLIT_BREAKS;
+
+static bool misaligned(const void *p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
+
+// The sizes and flags of a batch, which the sizing functions take too: no negative count, no read longer than an int
+// counts, no flag outside `allowed`
+static bool bad_batch(int64_t N, int64_t total_bases, int64_t max_len, int32_t flags, int32_t allowed)
+{
+    return N < 0 || total_bases < 0 || max_len < 0 || max_len > 0x7fffffffll || (flags & ~allowed) != 0;
+}
+
+// ... and the bases and read offsets of a call, where there are any to read
+static bool bad_batch(const CsrBatch &b, int32_t allowed)
+{
+    return bad_batch(b.N, b.total_bases, b.max_len, b.flags, allowed) || (b.N > 0 && !b.read_offsets) || (b.total_bases > 0 && !b.bases);
+}
+
+// an SMEM call's traversal: one of the three, and with GENIE_READS_SPLIT_BREAKS the BWA one
+static bool bad_smem_mode(int32_t mode, int32_t flags)
+{
+    return mode < GENIE_MODE_BWA || mode > GENIE_MODE_RMI || ((flags & GENIE_READS_SPLIT_BREAKS) && mode != GENIE_MODE_BWA);
+}
+
+// Reads need their workspace: present, 256-byte aligned and of `need` bytes
+static int workspace_args(const CsrBatch &b, int64_t need)
+{
+    return b.N > 0 && (!b.ws || misaligned(b.ws, 255) || b.ws_bytes < need) ? GENIE_E_CAPACITY : GENIE_OK;
+}
+
+static bool bad_contig_count(int64_t n_contigs) { return n_contigs < 1 || n_contigs > 0x7ffffffell; }
+
 int64_t genie_find_smems_long_ex_workspace_bytes(int64_t N, int64_t total_bases, int64_t max_len, int32_t flags)
 {
-    if (N < 0 || total_bases < 0 || max_len < 0 || max_len > 0x7fffffffll) return (int64_t)GENIE_E_INVALID;
-    if (flags & ~(GENIE_READS_BOTH_STRANDS | GENIE_READS_SPLIT_BREAKS)) return (int64_t)GENIE_E_INVALID;
+    if (bad_batch(N, total_bases, max_len, flags, kReadFlags)) return (int64_t)GENIE_E_INVALID;
     return find_smems_long_ex_workspace_bytes(N, total_bases, flags);
 }
 
@@ -450,54 +483,54 @@ int genie_find_smems_long_ex(const genie_index *ix, int32_t mode, int32_t flags,
                              int64_t N, int64_t total_bases, int64_t max_len, int32_t min_len, int64_t *d_offsets, int32_t *d_rows,
                              int64_t out_cap_rows, int32_t *d_status, void *d_workspace, int64_t workspace_bytes, void *stream)
 {
-    // argument checks first: they need no device image
-    if (!ix) return GENIE_E_INVALID;
-    if (N < 0 || total_bases < 0 || max_len < 0 || max_len > 0x7fffffffll || out_cap_rows < 0 || !d_offsets ||
-        (N > 0 && (!d_read_offsets || !d_rows || !d_workspace)) || (total_bases > 0 && !d_bases))
+    const CsrBatch b{flags, d_bases, d_read_offsets, N, total_bases, max_len, d_status, d_workspace, workspace_bytes};
+    // argument checks first: they need no device image.  Here a missing or misaligned workspace is a bad argument, and only
+    // a small one a capacity: the sign of workspace_bytes is not looked at
+    if (!ix || bad_batch(b, kReadFlags) || bad_smem_mode(mode, flags) || out_cap_rows < 0 || !d_offsets ||
+        (N > 0 && (!d_rows || !d_workspace)) || misaligned(d_rows, 15) || misaligned(d_workspace, 255))
         return GENIE_E_INVALID;
-    if (mode < GENIE_MODE_BWA || mode > GENIE_MODE_RMI) return GENIE_E_INVALID;
-    if (flags & ~(GENIE_READS_BOTH_STRANDS | GENIE_READS_SPLIT_BREAKS)) return GENIE_E_INVALID;
-    if ((flags & GENIE_READS_SPLIT_BREAKS) && mode != GENIE_MODE_BWA) return GENIE_E_INVALID;
-    if ((reinterpret_cast<uintptr_t>(d_rows) & 15) != 0 || (reinterpret_cast<uintptr_t>(d_workspace) & 255) != 0) return GENIE_E_INVALID;
-    if (N > 0 && workspace_bytes < find_smems_long_ex_workspace_bytes(N, total_bases, flags)) return GENIE_E_CAPACITY;
-    int rc = ready(ix);
-    if (rc || (rc = mode_tables(ix, mode))) return rc;
-    return launch_find_smems_long_ex(ix, mode, flags, d_bases, d_read_offsets, N, total_bases, max_len, min_len, d_offsets, d_rows,
-                                     out_cap_rows, d_status, d_workspace, workspace_bytes, stream);
+    int rc = workspace_args(b, find_smems_long_ex_workspace_bytes(N, total_bases, flags));
+    if (rc || (rc = ready(ix)) || (rc = mode_tables(ix, mode))) return rc;
+    return launch_find_smems_long_ex(ix, mode, min_len, b, {d_offsets, d_rows, out_cap_rows, nullptr}, stream);
 }
 
 int64_t genie_match_stats_workspace_bytes(int64_t N, int64_t total_bases, int64_t max_len, int32_t flags)
 {
-    if (N < 0 || total_bases < 0 || max_len < 0 || max_len > 0x7fffffffll) return (int64_t)GENIE_E_INVALID;
-    if (flags & ~(GENIE_READS_BOTH_STRANDS | GENIE_READS_SPLIT_BREAKS)) return (int64_t)GENIE_E_INVALID;
+    if (bad_batch(N, total_bases, max_len, flags, kReadFlags)) return (int64_t)GENIE_E_INVALID;
     return match_stats_workspace_bytes(N, total_bases, flags);
+}
+
+// genie_match_stats and genie_match_stats_contigs
+static bool bad_stats_args(const CsrBatch &b, const int32_t *d_ms, const int32_t *d_lohi)
+{
+    return bad_batch(b, kReadFlags) || b.ws_bytes < 0 || (b.total_bases > 0 && !d_ms) || misaligned(d_ms, 3) || misaligned(d_lohi, 7);
 }
 
 int genie_match_stats(const genie_index *ix, int32_t flags, const uint8_t *d_bases, const int64_t *d_read_offsets, int64_t N,
                       int64_t total_bases, int64_t max_len, int32_t *d_ms, int32_t *d_lohi, int32_t *d_status, void *d_workspace,
                       int64_t workspace_bytes, void *stream)
 {
+    const CsrBatch b{flags, d_bases, d_read_offsets, N, total_bases, max_len, d_status, d_workspace, workspace_bytes};
     // argument checks first: they need no device image
-    if (!ix) return GENIE_E_INVALID;
-    if (N < 0 || total_bases < 0 || max_len < 0 || max_len > 0x7fffffffll || workspace_bytes < 0 || (N > 0 && !d_read_offsets) ||
-        (total_bases > 0 && (!d_bases || !d_ms)))
-        return GENIE_E_INVALID;
-    if (flags & ~(GENIE_READS_BOTH_STRANDS | GENIE_READS_SPLIT_BREAKS)) return GENIE_E_INVALID;
-    if ((reinterpret_cast<uintptr_t>(d_ms) & 3) != 0 || (reinterpret_cast<uintptr_t>(d_lohi) & 7) != 0) return GENIE_E_INVALID;
-    if (N > 0 && (!d_workspace || (reinterpret_cast<uintptr_t>(d_workspace) & 255) != 0 ||
-                  workspace_bytes < match_stats_workspace_bytes(N, total_bases, flags)))
-        return GENIE_E_CAPACITY;
-    int rc = ready(ix);
-    if (rc) return rc;
-    return launch_match_stats(ix, flags, d_bases, d_read_offsets, N, total_bases, max_len, d_ms, d_lohi, d_status, d_workspace,
-                              workspace_bytes, stream);
+    if (!ix || bad_stats_args(b, d_ms, d_lohi)) return GENIE_E_INVALID;
+    int rc = workspace_args(b, match_stats_workspace_bytes(N, total_bases, flags));
+    if (rc || (rc = ready(ix))) return rc;
+    return launch_match_stats(ix, b, d_ms, d_lohi, stream);
 }
 
 int64_t genie_find_mems_workspace_bytes(int64_t N, int64_t total_bases, int64_t max_len, int32_t flags)
 {
-    if (N < 0 || total_bases < 0 || max_len < 0 || max_len > 0x7fffffffll) return (int64_t)GENIE_E_INVALID;
-    if (flags & ~(GENIE_READS_BOTH_STRANDS | GENIE_READS_SPLIT_BREAKS)) return (int64_t)GENIE_E_INVALID;
+    if (bad_batch(N, total_bases, max_len, flags, kReadFlags)) return (int64_t)GENIE_E_INVALID;
     return find_mems_workspace_bytes(N, total_bases, flags);
+}
+
+// genie_find_mems and genie_find_mems_contigs: both offset arrays hold N + 1 entries, one at least, and are wanted even
+// without reads
+static bool bad_mems_args(const CsrBatch &b, int32_t min_len, int32_t max_occ, const CsrRows &out)
+{
+    return bad_batch(b, kReadFlags) || b.ws_bytes < 0 || out.cap_rows < 0 || min_len < 1 || max_occ < 0 || !out.offsets ||
+           !b.read_offsets || misaligned(out.rows, 15) || misaligned(out.offsets, 7) || misaligned(out.totals, 7) ||
+           misaligned(b.status, 3);
 }
 
 int genie_find_mems(const genie_index *ix, int32_t flags, const uint8_t *d_bases, const int64_t *d_read_offsets, int64_t N,
@@ -505,22 +538,13 @@ int genie_find_mems(const genie_index *ix, int32_t flags, const uint8_t *d_bases
                     int64_t out_cap_rows, int32_t *d_status, int64_t *d_totals, void *d_workspace, int64_t workspace_bytes,
                     void *stream)
 {
+    const CsrBatch b{flags, d_bases, d_read_offsets, N, total_bases, max_len, d_status, d_workspace, workspace_bytes};
+    const CsrRows out{d_offsets, d_rows, out_cap_rows, d_totals};
     // argument checks first: they need no device image
-    if (!ix) return GENIE_E_INVALID;
-    if (N < 0 || total_bases < 0 || max_len < 0 || max_len > 0x7fffffffll || out_cap_rows < 0 || workspace_bytes < 0 ||
-        min_len < 1 || max_occ < 0 || !d_offsets || !d_read_offsets || (total_bases > 0 && !d_bases))
-        return GENIE_E_INVALID;
-    if (flags & ~(GENIE_READS_BOTH_STRANDS | GENIE_READS_SPLIT_BREAKS)) return GENIE_E_INVALID;
-    if ((reinterpret_cast<uintptr_t>(d_rows) & 15) != 0 || (reinterpret_cast<uintptr_t>(d_offsets) & 7) != 0 ||
-        (reinterpret_cast<uintptr_t>(d_totals) & 7) != 0 || (reinterpret_cast<uintptr_t>(d_status) & 3) != 0)
-        return GENIE_E_INVALID;
-    if (N > 0 && (!d_workspace || (reinterpret_cast<uintptr_t>(d_workspace) & 255) != 0 ||
-                  workspace_bytes < find_mems_workspace_bytes(N, total_bases, flags)))
-        return GENIE_E_CAPACITY;
-    int rc = ready(ix);
-    if (rc) return rc;
-    return launch_find_mems(ix, flags, d_bases, d_read_offsets, N, total_bases, max_len, min_len, max_occ, d_offsets, d_rows,
-                            out_cap_rows, d_status, d_totals, d_workspace, workspace_bytes, stream);
+    if (!ix || bad_mems_args(b, min_len, max_occ, out)) return GENIE_E_INVALID;
+    int rc = workspace_args(b, find_mems_workspace_bytes(N, total_bases, flags));
+    if (rc || (rc = ready(ix))) return rc;
+    return launch_find_mems(ix, b, min_len, max_occ, out, stream);
 }
 
 // A contig table as an argument: present, 8-byte aligned, at least one contig and no more than an int counts
@@ -540,33 +564,23 @@ int genie_contigs_validate(const genie_index *ix, const int64_t *d_contig_offset
 
 int64_t genie_find_mems_contigs_workspace_bytes(int64_t N, int64_t total_bases, int64_t max_len, int32_t flags, int64_t n_contigs)
 {
-    if (n_contigs < 1 || n_contigs > 0x7ffffffell) return (int64_t)GENIE_E_INVALID;
-    const int64_t parent = genie_find_mems_workspace_bytes(N, total_bases, max_len, flags);
-    return parent < 0 ? parent : find_mems_contigs_workspace_bytes(N, total_bases, flags, n_contigs);
+    if (bad_contig_count(n_contigs) || bad_batch(N, total_bases, max_len, flags, kReadFlags)) return (int64_t)GENIE_E_INVALID;
+    return find_mems_contigs_workspace_bytes(N, total_bases, flags);
 }
 
+// The contig calls: the table's own checks come behind the other arguments' and before the capacity
 int genie_find_mems_contigs(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs, int32_t flags,
                             const uint8_t *d_bases, const int64_t *d_read_offsets, int64_t N, int64_t total_bases, int64_t max_len,
                             int32_t min_len, int32_t max_occ, int64_t *d_offsets, int32_t *d_rows, int64_t out_cap_rows,
                             int32_t *d_status, int64_t *d_totals, void *d_workspace, int64_t workspace_bytes, void *stream)
 {
+    const CsrBatch b{flags, d_bases, d_read_offsets, N, total_bases, max_len, d_status, d_workspace, workspace_bytes};
+    const CsrRows out{d_offsets, d_rows, out_cap_rows, d_totals};
     // argument checks first: they need no device image
-    if (!ix) return GENIE_E_INVALID;
-    if (N < 0 || total_bases < 0 || max_len < 0 || max_len > 0x7fffffffll || out_cap_rows < 0 || workspace_bytes < 0 ||
-        min_len < 1 || max_occ < 0 || !d_offsets || !d_read_offsets || (total_bases > 0 && !d_bases))
-        return GENIE_E_INVALID;
-    if (flags & ~(GENIE_READS_BOTH_STRANDS | GENIE_READS_SPLIT_BREAKS)) return GENIE_E_INVALID;
-    if ((reinterpret_cast<uintptr_t>(d_rows) & 15) != 0 || (reinterpret_cast<uintptr_t>(d_offsets) & 7) != 0 ||
-        (reinterpret_cast<uintptr_t>(d_totals) & 7) != 0 || (reinterpret_cast<uintptr_t>(d_status) & 3) != 0)
-        return GENIE_E_INVALID;
+    if (!ix || bad_mems_args(b, min_len, max_occ, out)) return GENIE_E_INVALID;
     int rc = contig_args(d_contig_offsets, n_contigs);
-    if (rc) return rc;
-    if (N > 0 && (!d_workspace || (reinterpret_cast<uintptr_t>(d_workspace) & 255) != 0 ||
-                  workspace_bytes < find_mems_contigs_workspace_bytes(N, total_bases, flags, n_contigs)))
-        return GENIE_E_CAPACITY;
-    if ((rc = ready(ix))) return rc;
-    return launch_find_mems_contigs(ix, d_contig_offsets, n_contigs, flags, d_bases, d_read_offsets, N, total_bases, max_len, min_len,
-                                    max_occ, d_offsets, d_rows, out_cap_rows, d_status, d_totals, d_workspace, workspace_bytes, stream);
+    if (rc || (rc = workspace_args(b, find_mems_contigs_workspace_bytes(N, total_bases, flags))) || (rc = ready(ix))) return rc;
+    return launch_find_mems_contigs(ix, {d_contig_offsets, n_contigs}, b, min_len, max_occ, out, stream);
 }
 
 int64_t genie_locate_contigs_tmp_bytes(int64_t S) { return S < 0 ? (int64_t)GENIE_E_INVALID : locate_contigs_tmp_bytes(S); }
@@ -603,9 +617,8 @@ int genie_contig_coords(const genie_index *ix, const int64_t *d_contig_offsets, 
 
 int64_t genie_match_stats_contigs_workspace_bytes(int64_t N, int64_t total_bases, int64_t max_len, int32_t flags, int64_t n_contigs)
 {
-    if (n_contigs < 1 || n_contigs > 0x7ffffffell) return (int64_t)GENIE_E_INVALID;
-    const int64_t parent = genie_match_stats_workspace_bytes(N, total_bases, max_len, flags);
-    return parent < 0 ? parent : match_stats_contigs_workspace_bytes(N, total_bases, flags, n_contigs);
+    if (bad_contig_count(n_contigs) || bad_batch(N, total_bases, max_len, flags, kReadFlags)) return (int64_t)GENIE_E_INVALID;
+    return match_stats_contigs_workspace_bytes(N, total_bases, flags);
 }
 
 int genie_match_stats_contigs(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs, int32_t flags,
@@ -613,30 +626,18 @@ int genie_match_stats_contigs(const genie_index *ix, const int64_t *d_contig_off
                               int32_t *d_ms, int32_t *d_lohi, int32_t *d_status, int64_t *d_totals, void *d_workspace,
                               int64_t workspace_bytes, void *stream)
 {
+    const CsrBatch b{flags, d_bases, d_read_offsets, N, total_bases, max_len, d_status, d_workspace, workspace_bytes};
     // argument checks first: they need no device image
-    if (!ix) return GENIE_E_INVALID;
-    if (N < 0 || total_bases < 0 || max_len < 0 || max_len > 0x7fffffffll || workspace_bytes < 0 || (N > 0 && !d_read_offsets) ||
-        (total_bases > 0 && (!d_bases || !d_ms)))
-        return GENIE_E_INVALID;
-    if (flags & ~(GENIE_READS_BOTH_STRANDS | GENIE_READS_SPLIT_BREAKS)) return GENIE_E_INVALID;
-    if ((reinterpret_cast<uintptr_t>(d_ms) & 3) != 0 || (reinterpret_cast<uintptr_t>(d_lohi) & 7) != 0 ||
-        (reinterpret_cast<uintptr_t>(d_totals) & 7) != 0)
-        return GENIE_E_INVALID;
+    if (!ix || bad_stats_args(b, d_ms, d_lohi) || misaligned(d_totals, 7)) return GENIE_E_INVALID;
     int rc = contig_args(d_contig_offsets, n_contigs);
-    if (rc) return rc;
-    if (N > 0 && (!d_workspace || (reinterpret_cast<uintptr_t>(d_workspace) & 255) != 0 ||
-                  workspace_bytes < match_stats_contigs_workspace_bytes(N, total_bases, flags, n_contigs)))
-        return GENIE_E_CAPACITY;
-    if ((rc = ready(ix))) return rc;
-    return launch_match_stats_contigs(ix, d_contig_offsets, n_contigs, flags, d_bases, d_read_offsets, N, total_bases, max_len, d_ms,
-                                      d_lohi, d_status, d_totals, d_workspace, workspace_bytes, stream);
+    if (rc || (rc = workspace_args(b, match_stats_contigs_workspace_bytes(N, total_bases, flags))) || (rc = ready(ix))) return rc;
+    return launch_match_stats_contigs(ix, {d_contig_offsets, n_contigs}, b, d_ms, d_lohi, d_totals, stream);
 }
 
 int64_t genie_find_smems_contigs_workspace_bytes(int64_t N, int64_t total_bases, int64_t max_len, int32_t flags, int64_t n_contigs)
 {
-    if (n_contigs < 1 || n_contigs > 0x7ffffffell) return (int64_t)GENIE_E_INVALID;
-    const int64_t parent = genie_find_smems_long_ex_workspace_bytes(N, total_bases, max_len, flags);
-    return parent < 0 ? parent : find_smems_contigs_workspace_bytes(N, total_bases, flags, n_contigs);
+    if (bad_contig_count(n_contigs) || bad_batch(N, total_bases, max_len, flags, kReadFlags)) return (int64_t)GENIE_E_INVALID;
+    return find_smems_contigs_workspace_bytes(N, total_bases, flags);
 }
 
 int genie_find_smems_contigs(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs, int32_t mode, int32_t flags,
@@ -644,29 +645,21 @@ int genie_find_smems_contigs(const genie_index *ix, const int64_t *d_contig_offs
                              int32_t min_len, int64_t *d_offsets, int32_t *d_rows, int64_t out_cap_rows, int32_t *d_status,
                              int64_t *d_totals, void *d_workspace, int64_t workspace_bytes, void *stream)
 {
+    const CsrBatch b{flags, d_bases, d_read_offsets, N, total_bases, max_len, d_status, d_workspace, workspace_bytes};
     // argument checks first: they need no device image
-    if (!ix) return GENIE_E_INVALID;
-    if (N < 0 || total_bases < 0 || max_len < 0 || max_len > 0x7fffffffll || out_cap_rows < 0 || workspace_bytes < 0 || !d_offsets ||
-        (N > 0 && (!d_read_offsets || !d_rows)) || (total_bases > 0 && !d_bases))
+    if (!ix || bad_batch(b, kReadFlags) || bad_smem_mode(mode, flags) || workspace_bytes < 0 || out_cap_rows < 0 || !d_offsets ||
+        (N > 0 && !d_rows) || misaligned(d_rows, 15) || misaligned(d_totals, 7))
         return GENIE_E_INVALID;
-    if (mode < GENIE_MODE_BWA || mode > GENIE_MODE_RMI) return GENIE_E_INVALID;
-    if (flags & ~(GENIE_READS_BOTH_STRANDS | GENIE_READS_SPLIT_BREAKS)) return GENIE_E_INVALID;
-    if ((flags & GENIE_READS_SPLIT_BREAKS) && mode != GENIE_MODE_BWA) return GENIE_E_INVALID;
-    if ((reinterpret_cast<uintptr_t>(d_rows) & 15) != 0 || (reinterpret_cast<uintptr_t>(d_totals) & 7) != 0) return GENIE_E_INVALID;
     int rc = contig_args(d_contig_offsets, n_contigs);
-    if (rc) return rc;
-    if (N > 0 && (!d_workspace || (reinterpret_cast<uintptr_t>(d_workspace) & 255) != 0 ||
-                  workspace_bytes < find_smems_contigs_workspace_bytes(N, total_bases, flags, n_contigs)))
-        return GENIE_E_CAPACITY;
-    if ((rc = ready(ix)) || (rc = mode_tables(ix, mode))) return rc;
-    return launch_find_smems_contigs(ix, d_contig_offsets, n_contigs, mode, flags, d_bases, d_read_offsets, N, total_bases, max_len,
-                                     min_len, d_offsets, d_rows, out_cap_rows, d_status, d_totals, d_workspace, workspace_bytes, stream);
+    if (rc || (rc = workspace_args(b, find_smems_contigs_workspace_bytes(N, total_bases, flags))) || (rc = ready(ix)) ||
+        (rc = mode_tables(ix, mode)))
+        return rc;
+    return launch_find_smems_contigs(ix, {d_contig_offsets, n_contigs}, mode, min_len, b, {d_offsets, d_rows, out_cap_rows, d_totals}, stream);
 }
 
 int64_t genie_exact_match_workspace_bytes(int64_t N, int64_t total_bases, int64_t max_len, int32_t flags)
 {
-    if (N < 0 || total_bases < 0 || max_len < 0 || max_len > 0x7fffffffll) return (int64_t)GENIE_E_INVALID;
-    if (flags & ~GENIE_READS_BOTH_STRANDS) return (int64_t)GENIE_E_INVALID;
+    if (bad_batch(N, total_bases, max_len, flags, GENIE_READS_BOTH_STRANDS)) return (int64_t)GENIE_E_INVALID;
     return exact_match_workspace_bytes(N, total_bases, flags);
 }
 
@@ -674,22 +667,15 @@ int genie_exact_match(const genie_index *ix, int32_t flags, const uint8_t *d_bas
                       int64_t total_bases, int64_t max_len, int32_t *d_lohi, int32_t *d_counts, int32_t *d_status, void *d_workspace,
                       int64_t workspace_bytes, void *stream)
 {
-    // argument checks first: they need no device image
-    if (!ix) return GENIE_E_INVALID;
-    if (N < 0 || total_bases < 0 || max_len < 0 || max_len > 0x7fffffffll || workspace_bytes < 0 ||
-        (N > 0 && (!d_pat_offsets || !d_lohi)) || (total_bases > 0 && !d_bases))
+    const CsrBatch b{flags, d_bases, d_pat_offsets, N, total_bases, max_len, d_status, d_workspace, workspace_bytes};
+    // argument checks first: they need no device image.  GENIE_READS_SPLIT_BREAKS is refused too: a pattern with a break
+    // has no interval
+    if (!ix || bad_batch(b, GENIE_READS_BOTH_STRANDS) || workspace_bytes < 0 || (N > 0 && !d_lohi) || misaligned(d_lohi, 7) ||
+        misaligned(d_counts, 3) || misaligned(d_status, 3))
         return GENIE_E_INVALID;
-    if (flags & ~GENIE_READS_BOTH_STRANDS) return GENIE_E_INVALID;       // SPLIT_BREAKS too: a pattern with a break has no interval
-    if ((reinterpret_cast<uintptr_t>(d_lohi) & 7) != 0 || (reinterpret_cast<uintptr_t>(d_counts) & 3) != 0 ||
-        (reinterpret_cast<uintptr_t>(d_status) & 3) != 0)
-        return GENIE_E_INVALID;
-    if (N > 0 && (!d_workspace || (reinterpret_cast<uintptr_t>(d_workspace) & 255) != 0 ||
-                  workspace_bytes < exact_match_workspace_bytes(N, total_bases, flags)))
-        return GENIE_E_CAPACITY;
-    int rc = ready(ix);
-    if (rc) return rc;
-    return launch_exact_match(ix, flags, d_bases, d_pat_offsets, N, total_bases, max_len, d_lohi, d_counts, d_status, d_workspace,
-                              workspace_bytes, stream);
+    int rc = workspace_args(b, exact_match_workspace_bytes(N, total_bases, flags));
+    if (rc || (rc = ready(ix))) return rc;
+    return launch_exact_match(ix, b, d_lohi, d_counts, stream);
 }
 
 int64_t genie_reads_from_text_tmp_bytes(int64_t text_bytes, int64_t cap_reads)

@@ -11,8 +11,8 @@
 //      room(t) >= fwd[p0] - p0, then ms_c = ms on the whole run (t + k serves p0 + k): only run starts need a room test.
 //   4  "some t in the interval of Q[p .. p+l) has room(t) >= l" is monotone in l: where the run start fails, ms_c[p] of every
 //      position of the run is found by bisection over l, from the largest room seen upward.
-// Both calls run the front of their parents (lu_run) with tails of their own, which put three kernels between LR2 and what
-// reads fwd[]:
+// Both calls are their parents -- lu_run, the parents' tails, lr_match_stats / lr_pipeline -- with the step of long_reads.inc
+// set, which puts three kernels between LR2 and what reads fwd[]:
 //   LR1, LR2 (MS instance)   fwd[] of the concatenation, nothing else (LUT / RMI mode: the SMEM instance, for its statuses;
 //                            its marks are cleared again)
 //   CS1 cs_start_kernel      one wave per window, four windows per block, four positions per lane (lr_fwd_kernel's shape;
@@ -66,7 +66,7 @@ inline int64_t cs_layout(uint8_t *p, int64_t positions, int64_t units, CsArea *a
     return c.at;
 }
 
-// What the tails need beside their parents' members
+// What the step of a call needs
 struct CsCall {
     CtgTab g;
     CsArea a;
@@ -382,107 +382,13 @@ int cs_correct(const genie_index *ix, const CsCall &cs, bool skip_flagged, const
     return GENIE_OK;
 }
 
-// lr_match_stats with the correction between LR2 and LRM
-int cs_match_stats(const genie_index *ix, const CsCall &cs, const uint8_t *d_bases, const LongArea &a, const long long *uoff,
-                   long long U, const long long *usrc, const long long *uvirt, int32_t *d_ms, int32_t *d_lohi, hipStream_t s)
+// CS3 over the units of `uoff`: LR3 finds in a.wmax and a.mark what LR2's SMEM instance would have left there
+int cs_marks(const LongArea &a, const long long *uoff, long long U, hipStream_t s)
 {
-    LAUNCH_BLOCKS(lr_pack_kernel, (a.nwords + 255) / 256, 256, 0, s, d_bases, uoff, U, usrc, a.nwords, a.packed, a.st);
-    const bool c16 = (ix->dev.flags & kFlagCompactTable) != 0;
-    const auto fwd_kernel = c16 ? lr_fwd_kernel<true, true> : lr_fwd_kernel<false, true>;
-    const auto fwd_sliced = c16 ? lr_fwd_kernel<true, true, true> : lr_fwd_kernel<false, true, true>;
-    LAUNCH_SLICED(fwd_kernel, fwd_sliced, (a.nwin + kLrFwdWaves - 1) / kLrFwdWaves, kLrFwdWaves * 64, 0, s, ix->dev, (int)GENIE_MODE_BWA, uoff, U,
-                  a.nwin, static_cast<const uint64_t *>(a.packed), a.st, a.fwd, static_cast<int2 *>(nullptr),
-                  static_cast<uint8_t *>(nullptr), table_bytes(ix));
-    if (int rc = cs_correct(ix, cs, false, a, uoff, U, s)) return rc;
-    const auto ms_kernel = c16 ? lr_ms_kernel<true> : lr_ms_kernel<false>;
-    const auto ms_sliced = c16 ? lr_ms_kernel<true, true> : lr_ms_kernel<false, true>;
-    LAUNCH_SLICED(ms_kernel, ms_sliced, a.nwin, kLrWin, 0, s, ix->dev, uoff, U, static_cast<const uint64_t *>(a.packed),
-                  static_cast<const int32_t *>(a.st), static_cast<const int32_t *>(a.fwd), uvirt, d_ms, reinterpret_cast<int2 *>(d_lohi));
+    LAUNCH_SLICED(cs_marks_kernel<false>, cs_marks_kernel<true>, (a.nwin + kLrFwdWaves - 1) / kLrFwdWaves, kLrFwdWaves * 64, 0, s, uoff, U,
+                  a.nwin, static_cast<const int32_t *>(a.st), static_cast<const int32_t *>(a.fwd), a.wmax, a.mark);
     return GENIE_OK;
 }
-
-// lr_pipeline with the correction and CS3 between LR2 and LR3
-int cs_pipeline(const genie_index *ix, const CsCall &cs, int mode, int min_len, const uint8_t *d_bases, const LongArea &a,
-                const long long *uoff, long long U, const long long *usrc, const int32_t *ushift, int64_t *offsets, int32_t *d_rows,
-                long long cap, hipStream_t s)
-{
-    HIP_TRY(hipMemsetAsync(a.entry, 0xFF, a.nwin * 4, s));
-    LAUNCH_BLOCKS(lr_pack_kernel, (a.nwords + 255) / 256, 256, 0, s, d_bases, uoff, U, usrc, a.nwords, a.packed, a.st);
-    const bool c16 = (ix->dev.flags & kFlagCompactTable) != 0;
-    const long long fwd_blocks = (a.nwin + kLrFwdWaves - 1) / kLrFwdWaves;
-    if (mode == GENIE_MODE_BWA) {
-        const auto fwd_kernel = c16 ? lr_fwd_kernel<true, true> : lr_fwd_kernel<false, true>;
-        const auto fwd_sliced = c16 ? lr_fwd_kernel<true, true, true> : lr_fwd_kernel<false, true, true>;
-        LAUNCH_SLICED(fwd_kernel, fwd_sliced, fwd_blocks, kLrFwdWaves * 64, 0, s, ix->dev, mode, uoff, U, a.nwin,
-                      static_cast<const uint64_t *>(a.packed), a.st, a.fwd, static_cast<int2 *>(nullptr),
-                      static_cast<uint8_t *>(nullptr), table_bytes(ix));
-    } else {
-        // LUT / RMI: a read shorter than K keeps its status only in the SMEM instance, which skips it; its marks go again
-        const auto fwd_one = c16 ? lr_fwd_kernel<true> : lr_fwd_kernel<false>;
-        const auto fwd_sliced = c16 ? lr_fwd_kernel<true, false, true> : lr_fwd_kernel<false, false, true>;
-        LAUNCH_SLICED(fwd_one, fwd_sliced, fwd_blocks, kLrFwdWaves * 64, 0, s, ix->dev, mode, uoff, U, a.nwin,
-                      static_cast<const uint64_t *>(a.packed), a.st, a.fwd, a.wmax, a.mark, table_bytes(ix));
-    }
-    if (a.total > 0) HIP_TRY(hipMemsetAsync(a.mark, 0, a.total, s));
-    if (int rc = cs_correct(ix, cs, true, a, uoff, U, s)) return rc;
-    LAUNCH_SLICED(cs_marks_kernel<false>, cs_marks_kernel<true>, fwd_blocks, kLrFwdWaves * 64, 0, s, uoff, U, a.nwin,
-                  static_cast<const int32_t *>(a.st), static_cast<const int32_t *>(a.fwd), a.wmax, a.mark);
-    LAUNCH_SLICED(lr_walk_kernel<false>, lr_walk_kernel<true>, a.nwin, kLrWin, 0, s, mode, min_len, uoff, U,
-                  static_cast<const int32_t *>(a.st), static_cast<const int32_t *>(a.fwd), static_cast<const int2 *>(a.wmax),
-                  static_cast<const uint8_t *>(a.mark), a.bst, a.jc);
-    LAUNCH_BLOCKS(lr_chain_kernel, (U + 255) / 256, 256, 0, s, uoff, U, a.st, a.jc, a.entry, a.base, a.cnt);
-    int rc = launch_compact(a.cnt, nullptr, U, 0x7fffffff, offsets, nullptr, 0, a.sums, s);
-    if (rc) return rc;
-    LAUNCH_BLOCKS(lr_emit_kernel, (a.nwin + 255) / 256, 256, 0, s, ix->dev, mode, min_len, uoff, U, a.nwin, a.packed, a.fwd, a.bst,
-                  a.entry, a.base, reinterpret_cast<const long long *>(offsets), ushift, reinterpret_cast<int4 *>(d_rows), cap);
-    return GENIE_OK;
-}
-
-// The tails: their parents', with cs_match_stats / cs_pipeline where those run lr_match_stats / lr_pipeline
-struct LuMsCtgTail {
-    static constexpr bool kSmems = false, kFwd = true;
-    LuMsTail t;
-    CsCall cs;
-
-    int empty() { return t.empty(); }
-    int whole(const LongArea &lr, const long long *uoff, const long long *usrc)
-    {
-        LAUNCH(lr_ms_edges_kernel, dim3(64), dim3(256), 0, t.s, t.off, t.N, t.S, t.positions, t.d_ms, reinterpret_cast<int2 *>(t.d_lohi));
-        int rc = cs_match_stats(t.ix, cs, t.d_bases, lr, uoff, t.S * t.N, usrc, nullptr, t.d_ms, t.d_lohi, t.s);
-        if (rc) return rc;
-        if (t.d_status) HIP_TRY(hipMemcpyAsync(t.d_status, lr.st, t.S * t.N * 4, hipMemcpyDeviceToDevice, t.s));
-        return GENIE_OK;
-    }
-    int broken(long long U) { return t.broken(U); }
-    int pass(const LuPass &p)
-    {
-        return cs_match_stats(t.ix, cs, t.d_bases, p.a.lr, p.a.uoff, p.p1 - p.p0, p.a.ub, p.a.ua, t.d_ms, t.d_lohi, t.s);
-    }
-};
-
-struct LuSmemCtgTail {
-    static constexpr bool kSmems = true, kFwd = true;
-    LuSmemTail t;
-    CsCall cs;
-
-    int empty() { return t.empty(); }
-    int whole(const LongArea &lr, const long long *uoff, const long long *usrc)
-    {
-        int rc = cs_pipeline(t.ix, cs, t.mode, t.min_len, t.d_bases, lr, uoff, t.SN, usrc, nullptr, t.d_offsets, t.d_rows,
-                             t.out_cap_rows, t.s);
-        if (rc) return rc;
-        if (t.d_status) HIP_TRY(hipMemcpyAsync(t.d_status, lr.st, t.SN * 4, hipMemcpyDeviceToDevice, t.s));
-        return GENIE_OK;
-    }
-    int broken(long long U) { return t.broken(U); }
-    int pass(const LuPass &p)
-    {
-        return t.pass_with(p, [&](const LongExPass &a, long long Cp, int32_t *rows, long long cap_left) {
-            return cs_pipeline(t.ix, cs, t.mode, t.min_len, t.d_bases, a.lr, a.uoff, Cp, a.ub, a.ushift,
-                               reinterpret_cast<int64_t *>(a.loff), rows, cap_left, t.s);
-        });
-    }
-};
 
 // The most units a pass of lu_run takes when the parent's part of the workspace has exactly its declared size: the
 // strand-reads without SPLIT_BREAKS, else what long_ex_pass_units, which lu_run asks too, finds for any number of units
@@ -507,49 +413,45 @@ inline int64_t cs_bytes(int64_t N, int64_t total, int32_t flags, bool smems, uin
 
 }  // namespace
 
-int64_t match_stats_contigs_workspace_bytes(int64_t N, int64_t total_bases, int32_t flags, int64_t n_contigs)
+int64_t match_stats_contigs_workspace_bytes(int64_t N, int64_t total_bases, int32_t flags)
 {
-    (void)n_contigs;                                             // the table is the caller's and its samples live in LDS
     CsArea a;
     return cs_bytes(N, total_bases, flags, false, nullptr, &a);
 }
 
-int launch_match_stats_contigs(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs, int32_t flags,
-                               const uint8_t *d_bases, const int64_t *d_read_offsets, int64_t N, int64_t total_bases, int64_t max_len,
-                               int32_t *d_ms, int32_t *d_lohi, int32_t *d_status, int64_t *d_totals, void *d_ws, int64_t ws_bytes,
-                               void *stream)
+// Both calls are their parents with the step set, on the parent's part of the workspace at exactly its declared size
+int launch_match_stats_contigs(const genie_index *ix, const ContigTable &ctg, const CsrBatch &b, int32_t *d_ms, int32_t *d_lohi,
+                               int64_t *d_totals, void *stream)
 {
-    (void)ws_bytes;
     hipStream_t s = (hipStream_t)stream;
-    const int S = (flags & GENIE_READS_BOTH_STRANDS) ? 2 : 1;
     if (d_totals) HIP_TRY(hipMemsetAsync(d_totals, 0, 8, s));
-    LuMsCtgTail tail{{ix, d_bases, reinterpret_cast<const long long *>(d_read_offsets), (long long)N, S, (long long)S * total_bases,
-                      d_ms, d_lohi, d_status, s},
-                     {ctg_tab(d_contig_offsets, n_contigs), {}, reinterpret_cast<long long *>(d_totals)}};
-    if (N > 0) cs_bytes(N, total_bases, flags, false, static_cast<uint8_t *>(d_ws), &tail.cs.a);
-    return lu_run(ix, GENIE_MODE_BWA, flags, d_bases, d_read_offsets, N, total_bases, max_len, d_ws,
-                  long_ex_bytes(N, total_bases, flags, false), s, tail);
+    CsCall cs{ctg_tab(ctg.offsets, ctg.n_contigs), {}, reinterpret_cast<long long *>(d_totals)};
+    if (b.N > 0) cs_bytes(b.N, b.total_bases, b.flags, false, static_cast<uint8_t *>(b.ws), &cs.a);
+    CsrBatch parent = b;
+    parent.ws_bytes = long_ex_bytes(b.N, b.total_bases, b.flags, false);
+    LuMsTail tail{ix, parent, d_ms, d_lohi, s,
+                  [&](const LongArea &a, const long long *uoff, long long U) { return cs_correct(ix, cs, false, a, uoff, U, s); }};
+    return lu_run(ix, GENIE_MODE_BWA, parent, s, tail);
 }
 
-int64_t find_smems_contigs_workspace_bytes(int64_t N, int64_t total_bases, int32_t flags, int64_t n_contigs)
+int64_t find_smems_contigs_workspace_bytes(int64_t N, int64_t total_bases, int32_t flags)
 {
-    (void)n_contigs;
     CsArea a;
     return cs_bytes(N, total_bases, flags, true, nullptr, &a);
 }
 
-int launch_find_smems_contigs(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs, int32_t mode, int32_t flags,
-                              const uint8_t *d_bases, const int64_t *d_read_offsets, int64_t N, int64_t total_bases, int64_t max_len,
-                              int32_t min_len, int64_t *d_offsets, int32_t *d_rows, int64_t out_cap_rows, int32_t *d_status,
-                              int64_t *d_totals, void *d_ws, int64_t ws_bytes, void *stream)
+int launch_find_smems_contigs(const genie_index *ix, const ContigTable &ctg, int32_t mode, int32_t min_len, const CsrBatch &b,
+                              const CsrRows &out, void *stream)
 {
-    (void)ws_bytes;
     hipStream_t s = (hipStream_t)stream;
-    const int S = (flags & GENIE_READS_BOTH_STRANDS) ? 2 : 1;
-    if (d_totals) HIP_TRY(hipMemsetAsync(d_totals, 0, 8, s));
-    LuSmemCtgTail tail{{ix, mode, min_len, d_bases, (long long)S * N, d_offsets, d_rows, out_cap_rows, d_status, s},
-                       {ctg_tab(d_contig_offsets, n_contigs), {}, reinterpret_cast<long long *>(d_totals)}};
-    if (N > 0) cs_bytes(N, total_bases, flags, true, static_cast<uint8_t *>(d_ws), &tail.cs.a);
-    return lu_run(ix, mode, flags, d_bases, d_read_offsets, N, total_bases, max_len, d_ws, long_ex_bytes(N, total_bases, flags, true), s,
-                  tail);
+    if (out.totals) HIP_TRY(hipMemsetAsync(out.totals, 0, 8, s));
+    CsCall cs{ctg_tab(ctg.offsets, ctg.n_contigs), {}, reinterpret_cast<long long *>(out.totals)};
+    if (b.N > 0) cs_bytes(b.N, b.total_bases, b.flags, true, static_cast<uint8_t *>(b.ws), &cs.a);
+    CsrBatch parent = b;
+    parent.ws_bytes = long_ex_bytes(b.N, b.total_bases, b.flags, true);
+    LuSmemTail tail{ix, mode, min_len, parent, out, s, [&](const LongArea &a, const long long *uoff, long long U) {
+                        const int rc = cs_correct(ix, cs, true, a, uoff, U, s);
+                        return rc ? rc : cs_marks(a, uoff, U, s);
+                    }};
+    return lu_run(ix, mode, parent, s, tail);
 }

@@ -72,22 +72,22 @@ __global__ void __launch_bounds__(kEmBlock) exact_match_kernel(DevIndex ix, cons
 struct LuExactTail {
     static constexpr bool kSmems = false, kFwd = false;
     const genie_index *ix;
-    const uint8_t *d_bases;
-    long long SN, max_len;
-    int32_t *d_lohi, *d_counts, *d_status;
+    const CsrBatch &b;
+    int32_t *d_lohi, *d_counts;
     hipStream_t s;
 
     int empty() { return GENIE_OK; }
     int whole(const LongArea &lr, const long long *uoff, const long long *usrc)
     {
-        const bool direct = max_len <= kEmDirect;
+        const long long SN = b.strand_reads();
+        const bool direct = b.max_len <= kEmDirect;
         if (!direct)
-            LAUNCH_BLOCKS(lr_pack_kernel, (lr.nwords + 255) / 256, 256, 0, s, d_bases, uoff, SN, usrc, lr.nwords,
+            LAUNCH_BLOCKS(lr_pack_kernel, (lr.nwords + 255) / 256, 256, 0, s, b.bases, uoff, SN, usrc, lr.nwords,
                    lr.packed, lr.st);
         const auto kernel = direct ? exact_match_kernel<true> : exact_match_kernel<false>;
-        LAUNCH_BLOCKS(kernel, (SN + kEmBlock - 1) / kEmBlock, kEmBlock, 0, s, ix->dev, d_bases, uoff, usrc, SN,
+        LAUNCH_BLOCKS(kernel, (SN + kEmBlock - 1) / kEmBlock, kEmBlock, 0, s, ix->dev, b.bases, uoff, usrc, SN,
                static_cast<const uint64_t *>(lr.packed), static_cast<const int32_t *>(lr.st), reinterpret_cast<int2 *>(d_lohi),
-               d_counts, d_status);
+               d_counts, b.status);
         return GENIE_OK;
     }
     int broken(long long) { return GENIE_E_INVALID; }            // not reached: SPLIT_BREAKS is refused by the C ABI
@@ -101,12 +101,9 @@ int64_t exact_match_workspace_bytes(int64_t N, int64_t total_bases, int32_t flag
     return long_ex_bytes(N, total_bases, flags, false, false);
 }
 
-int launch_exact_match(const genie_index *ix, int32_t flags, const uint8_t *d_bases, const int64_t *d_pat_offsets, int64_t N,
-                       int64_t total_bases, int64_t max_len, int32_t *d_lohi, int32_t *d_counts, int32_t *d_status, void *d_ws,
-                       int64_t ws_bytes, void *stream)
+int launch_exact_match(const genie_index *ix, const CsrBatch &b, int32_t *d_lohi, int32_t *d_counts, void *stream)
 {
     hipStream_t s = (hipStream_t)stream;
-    const int S = (flags & GENIE_READS_BOTH_STRANDS) ? 2 : 1;
-    LuExactTail tail{ix, d_bases, (long long)S * N, (long long)max_len, d_lohi, d_counts, d_status, s};
-    return lu_run(ix, GENIE_MODE_BWA, flags, d_bases, d_pat_offsets, N, total_bases, max_len, d_ws, ws_bytes, s, tail);
+    LuExactTail tail{ix, b, d_lohi, d_counts, s};
+    return lu_run(ix, GENIE_MODE_BWA, b, s, tail);
 }

@@ -382,23 +382,42 @@ int64_t find_smems_split_workspace_bytes(int64_t N, int32_t max_len);
 int launch_find_smems_split(const genie_index *ix, const uint8_t *d_reads, const int32_t *d_lens, int64_t N, int32_t stride,
                             int32_t fixed_len, int32_t min_len, int64_t *d_offsets, int32_t *d_rows, int64_t out_cap_rows,
                             int32_t *d_status, void *d_ws, int64_t ws_bytes, void *stream);
+// The batch of a CSR call: every read's bases in one buffer and N + 1 64-bit offsets into it, the GENIE_READS_* flags, a
+// status per strand-read or null, and the caller's workspace.  max_len bounds the longest read.
+struct CsrBatch {
+    int32_t flags;
+    const uint8_t *bases;
+    const int64_t *read_offsets;
+    int64_t N, total_bases, max_len;
+    int32_t *status;
+    void *ws;
+    int64_t ws_bytes;
+    int strands() const { return (flags & GENIE_READS_BOTH_STRANDS) ? 2 : 1; }
+    bool split() const { return (flags & GENIE_READS_SPLIT_BREAKS) != 0; }
+    long long strand_reads() const { return (long long)strands() * N; }
+    long long positions() const { return (long long)strands() * total_bases; }       // virtual positions (long_units.inc)
+};
+// Rows as CSR: N + 1 (S N + 1) offsets, 16-byte rows and how many fit, the call's totals or null
+struct CsrRows {
+    int64_t *offsets;
+    int32_t *rows;
+    int64_t cap_rows;
+    int64_t *totals;
+};
+// The contig table of a reference of several sequences: n_contigs + 1 offsets
+struct ContigTable {
+    const int64_t *offsets;
+    int64_t n_contigs;
+};
 // flags == 0: genie_find_smems_long
 int64_t find_smems_long_ex_workspace_bytes(int64_t N, int64_t total_bases, int32_t flags);
-int launch_find_smems_long_ex(const genie_index *ix, int32_t mode, int32_t flags, const uint8_t *d_bases, const int64_t *d_read_offsets,
-                              int64_t N, int64_t total_bases, int64_t max_len, int32_t min_len, int64_t *d_offsets, int32_t *d_rows,
-                              int64_t out_cap_rows, int32_t *d_status, void *d_ws, int64_t ws_bytes, void *stream);
+int launch_find_smems_long_ex(const genie_index *ix, int32_t mode, int32_t min_len, const CsrBatch &b, const CsrRows &out, void *stream);
 int64_t match_stats_workspace_bytes(int64_t N, int64_t total_bases, int32_t flags);
-int launch_match_stats(const genie_index *ix, int32_t flags, const uint8_t *d_bases, const int64_t *d_read_offsets, int64_t N,
-                       int64_t total_bases, int64_t max_len, int32_t *d_ms, int32_t *d_lohi, int32_t *d_status, void *d_ws,
-                       int64_t ws_bytes, void *stream);
+int launch_match_stats(const genie_index *ix, const CsrBatch &b, int32_t *d_ms, int32_t *d_lohi, void *stream);
 int64_t exact_match_workspace_bytes(int64_t N, int64_t total_bases, int32_t flags);
-int launch_exact_match(const genie_index *ix, int32_t flags, const uint8_t *d_bases, const int64_t *d_pat_offsets, int64_t N,
-                       int64_t total_bases, int64_t max_len, int32_t *d_lohi, int32_t *d_counts, int32_t *d_status, void *d_ws,
-                       int64_t ws_bytes, void *stream);
+int launch_exact_match(const genie_index *ix, const CsrBatch &b, int32_t *d_lohi, int32_t *d_counts, void *stream);
 int64_t find_mems_workspace_bytes(int64_t N, int64_t total_bases, int32_t flags);
-int launch_find_mems(const genie_index *ix, int32_t flags, const uint8_t *d_bases, const int64_t *d_read_offsets, int64_t N,
-                     int64_t total_bases, int64_t max_len, int32_t min_len, int32_t max_occ, int64_t *d_offsets, int32_t *d_rows,
-                     int64_t out_cap_rows, int32_t *d_status, int64_t *d_totals, void *d_ws, int64_t ws_bytes, void *stream);
+int launch_find_mems(const genie_index *ix, const CsrBatch &b, int32_t min_len, int32_t max_occ, const CsrRows &out, void *stream);
 // contigs.inc, mems.inc: a reference of several sequences
 int contigs_validate(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs, void *stream);
 int launch_contig_coords(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs, const int32_t *d_pos, int32_t stride,
@@ -406,22 +425,17 @@ int launch_contig_coords(const genie_index *ix, const int64_t *d_contig_offsets,
 int64_t locate_contigs_tmp_bytes(int64_t S);
 int launch_locate_contigs(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs, const int32_t *d_rows, int64_t S,
                           int64_t *d_hit_offsets, int32_t *d_hits, int64_t cap_hits, int64_t *d_totals, void *d_tmp, void *stream);
-int64_t find_mems_contigs_workspace_bytes(int64_t N, int64_t total_bases, int32_t flags, int64_t n_contigs);
-int launch_find_mems_contigs(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs, int32_t flags,
-                             const uint8_t *d_bases, const int64_t *d_read_offsets, int64_t N, int64_t total_bases, int64_t max_len,
-                             int32_t min_len, int32_t max_occ, int64_t *d_offsets, int32_t *d_rows, int64_t out_cap_rows,
-                             int32_t *d_status, int64_t *d_totals, void *d_ws, int64_t ws_bytes, void *stream);
+// the table is the caller's and its samples live in LDS: no size depends on n_contigs
+int64_t find_mems_contigs_workspace_bytes(int64_t N, int64_t total_bases, int32_t flags);
+int launch_find_mems_contigs(const genie_index *ix, const ContigTable &ctg, const CsrBatch &b, int32_t min_len, int32_t max_occ,
+                             const CsrRows &out, void *stream);
 // contig_stats.inc: matching statistics and SMEMs that are exact with respect to the sequence set
-int64_t match_stats_contigs_workspace_bytes(int64_t N, int64_t total_bases, int32_t flags, int64_t n_contigs);
-int launch_match_stats_contigs(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs, int32_t flags,
-                               const uint8_t *d_bases, const int64_t *d_read_offsets, int64_t N, int64_t total_bases, int64_t max_len,
-                               int32_t *d_ms, int32_t *d_lohi, int32_t *d_status, int64_t *d_totals, void *d_ws, int64_t ws_bytes,
-                               void *stream);
-int64_t find_smems_contigs_workspace_bytes(int64_t N, int64_t total_bases, int32_t flags, int64_t n_contigs);
-int launch_find_smems_contigs(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs, int32_t mode, int32_t flags,
-                              const uint8_t *d_bases, const int64_t *d_read_offsets, int64_t N, int64_t total_bases, int64_t max_len,
-                              int32_t min_len, int64_t *d_offsets, int32_t *d_rows, int64_t out_cap_rows, int32_t *d_status,
-                              int64_t *d_totals, void *d_ws, int64_t ws_bytes, void *stream);
+int64_t match_stats_contigs_workspace_bytes(int64_t N, int64_t total_bases, int32_t flags);
+int launch_match_stats_contigs(const genie_index *ix, const ContigTable &ctg, const CsrBatch &b, int32_t *d_ms, int32_t *d_lohi,
+                               int64_t *d_totals, void *stream);
+int64_t find_smems_contigs_workspace_bytes(int64_t N, int64_t total_bases, int32_t flags);
+int launch_find_smems_contigs(const genie_index *ix, const ContigTable &ctg, int32_t mode, int32_t min_len, const CsrBatch &b,
+                              const CsrRows &out, void *stream);
 int64_t reads_from_text_tmp_bytes(int64_t text_bytes, int64_t cap_reads);
 int launch_reads_from_text(const uint8_t *d_text, int64_t text_bytes, int32_t format, int32_t flags, const uint8_t *code_of_byte,
                            uint8_t *d_bases, int64_t cap_bases, int64_t *d_read_offsets, int64_t cap_reads, int64_t *out5,

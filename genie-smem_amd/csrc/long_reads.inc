@@ -40,6 +40,8 @@
 //                         array, and the SA interval of [a, fwd[a]) from the match-table entry of the position's P2-mer where
 //                         that decides (interval_from_window, as K_C), else from sa_interval over the packed unit -- those
 //                         positions are gathered per block so that the search runs on full waves.
+// Both sequences take an optional step (LrStep) that runs behind LR2 and corrects fwd[] before anything reads it: the
+// contig-exact calls (contig_stats.inc) are their parents with that step set.
 namespace {
 
 constexpr int kLrWin = 256;               // positions per window (a multiple of 64: one per lane of LR3's block)
@@ -422,42 +424,68 @@ inline int64_t long_layout(uint8_t *p, int64_t N, int64_t total, LongArea *a, bo
     return c.at;
 }
 
-// LR1 .. LR5 over the U units of `uoff`, the row counts to `offsets`: the one launch sequence of the long calls
+// What a call may put between LR2 and whatever reads fwd[]: step(a, uoff, U) rewrites fwd[] of the U units in place
+// (contig_stats.inc).  Empty: nothing.
+using LrStep = std::function<int(const LongArea &, const long long *, long long)>;
+
+// LR2's match-statistics instance over the U units of `uoff`: fwd[] alone, a.wmax and a.mark are not touched (below)
+int lr_fwd_plain(const genie_index *ix, const LongArea &a, const long long *uoff, long long U, hipStream_t s);
+
+// LR1 .. LR5 over the U units of `uoff`, the row counts to `offsets`: the one launch sequence of the long calls.  A step
+// also rewrites a.wmax and a.mark from its fwd[], so the marks are cleared in front of it, not in front of LR2, and LR2
+// writes neither where it need not: in BWA mode.  In LUT / RMI mode a read shorter than K keeps its status only in the
+// SMEM instance, which skips it.
 int lr_pipeline(const genie_index *ix, int mode, int min_len, const uint8_t *d_bases, const LongArea &a, const long long *uoff,
                 long long U, const long long *usrc, const int32_t *ushift, int64_t *offsets, int32_t *d_rows, long long cap,
-                hipStream_t s)
+                const LrStep &step, hipStream_t s)
 {
     HIP_TRY(hipMemsetAsync(a.entry, 0xFF, a.nwin * 4, s));
-    if (a.total > 0) HIP_TRY(hipMemsetAsync(a.mark, 0, a.total, s));
+    if (a.total > 0 && !step) HIP_TRY(hipMemsetAsync(a.mark, 0, a.total, s));
     LAUNCH_BLOCKS(lr_pack_kernel, (a.nwords + 255) / 256, 256, 0, s, d_bases, uoff, U, usrc, a.nwords, a.packed, a.st);
-    const bool c16 = (ix->dev.flags & kFlagCompactTable) != 0;
-    const auto fwd_one = c16 ? lr_fwd_kernel<true> : lr_fwd_kernel<false>;
-    const auto fwd_sliced = c16 ? lr_fwd_kernel<true, false, true> : lr_fwd_kernel<false, false, true>;
-    LAUNCH_SLICED(fwd_one, fwd_sliced, (a.nwin + kLrFwdWaves - 1) / kLrFwdWaves, kLrFwdWaves * 64, 0, s, ix->dev, mode, uoff, U, a.nwin,
-                  static_cast<const uint64_t *>(a.packed), a.st, a.fwd, a.wmax, a.mark, table_bytes(ix));
+    int rc = GENIE_OK;
+    if (step && mode == GENIE_MODE_BWA) {
+        if ((rc = lr_fwd_plain(ix, a, uoff, U, s))) return rc;
+    } else {
+        const bool c16 = (ix->dev.flags & kFlagCompactTable) != 0;
+        const auto fwd_one = c16 ? lr_fwd_kernel<true> : lr_fwd_kernel<false>;
+        const auto fwd_sliced = c16 ? lr_fwd_kernel<true, false, true> : lr_fwd_kernel<false, false, true>;
+        LAUNCH_SLICED(fwd_one, fwd_sliced, (a.nwin + kLrFwdWaves - 1) / kLrFwdWaves, kLrFwdWaves * 64, 0, s, ix->dev, mode, uoff, U, a.nwin,
+                      static_cast<const uint64_t *>(a.packed), a.st, a.fwd, a.wmax, a.mark, table_bytes(ix));
+    }
+    if (step) {
+        if (a.total > 0) HIP_TRY(hipMemsetAsync(a.mark, 0, a.total, s));
+        if ((rc = step(a, uoff, U))) return rc;
+    }
     LAUNCH_SLICED(lr_walk_kernel<false>, lr_walk_kernel<true>, a.nwin, kLrWin, 0, s, mode, min_len, uoff, U,
                   static_cast<const int32_t *>(a.st), static_cast<const int32_t *>(a.fwd), static_cast<const int2 *>(a.wmax),
                   static_cast<const uint8_t *>(a.mark), a.bst, a.jc);
     LAUNCH_BLOCKS(lr_chain_kernel, (U + 255) / 256, 256, 0, s, uoff, U, a.st, a.jc, a.entry, a.base, a.cnt);
-    int rc = launch_compact(a.cnt, nullptr, U, 0x7fffffff, offsets, nullptr, 0, a.sums, s);
-    if (rc) return rc;
+    if ((rc = launch_compact(a.cnt, nullptr, U, 0x7fffffff, offsets, nullptr, 0, a.sums, s))) return rc;
     LAUNCH_BLOCKS(lr_emit_kernel, (a.nwin + 255) / 256, 256, 0, s, ix->dev, mode, min_len, uoff, U, a.nwin, a.packed, a.fwd, a.bst,
                   a.entry, a.base, reinterpret_cast<const long long *>(offsets), ushift, reinterpret_cast<int4 *>(d_rows), cap);
     return GENIE_OK;
 }
 
-// LR1, LR2 and LRM over the U units of `uoff`: the matching statistics of every position of every unit to its place in
-// ms / lohi (lohi may be null), the units' statuses to a.st
-int lr_match_stats(const genie_index *ix, const uint8_t *d_bases, const LongArea &a, const long long *uoff, long long U,
-                   const long long *usrc, const long long *uvirt, int32_t *d_ms, int32_t *d_lohi, hipStream_t s)
+int lr_fwd_plain(const genie_index *ix, const LongArea &a, const long long *uoff, long long U, hipStream_t s)
 {
-    LAUNCH_BLOCKS(lr_pack_kernel, (a.nwords + 255) / 256, 256, 0, s, d_bases, uoff, U, usrc, a.nwords, a.packed, a.st);
     const bool c16 = (ix->dev.flags & kFlagCompactTable) != 0;
     const auto fwd_kernel = c16 ? lr_fwd_kernel<true, true> : lr_fwd_kernel<false, true>;
     const auto fwd_sliced = c16 ? lr_fwd_kernel<true, true, true> : lr_fwd_kernel<false, true, true>;
     LAUNCH_SLICED(fwd_kernel, fwd_sliced, (a.nwin + kLrFwdWaves - 1) / kLrFwdWaves, kLrFwdWaves * 64, 0, s, ix->dev, (int)GENIE_MODE_BWA, uoff, U,
                   a.nwin, static_cast<const uint64_t *>(a.packed), a.st, a.fwd, static_cast<int2 *>(nullptr),
                   static_cast<uint8_t *>(nullptr), table_bytes(ix));
+    return GENIE_OK;
+}
+
+// LR1, LR2, the step and LRM over the U units of `uoff`: the matching statistics of every position of every unit to its
+// place in ms / lohi (lohi may be null), the units' statuses to a.st
+int lr_match_stats(const genie_index *ix, const uint8_t *d_bases, const LongArea &a, const long long *uoff, long long U,
+                   const long long *usrc, const long long *uvirt, int32_t *d_ms, int32_t *d_lohi, const LrStep &step, hipStream_t s)
+{
+    LAUNCH_BLOCKS(lr_pack_kernel, (a.nwords + 255) / 256, 256, 0, s, d_bases, uoff, U, usrc, a.nwords, a.packed, a.st);
+    int rc = lr_fwd_plain(ix, a, uoff, U, s);
+    if (rc || (step && (rc = step(a, uoff, U)))) return rc;
+    const bool c16 = (ix->dev.flags & kFlagCompactTable) != 0;
     const auto ms_kernel = c16 ? lr_ms_kernel<true> : lr_ms_kernel<false>;
     const auto ms_sliced = c16 ? lr_ms_kernel<true, true> : lr_ms_kernel<false, true>;
     LAUNCH_SLICED(ms_kernel, ms_sliced, a.nwin, kLrWin, 0, s, ix->dev, uoff, U, static_cast<const uint64_t *>(a.packed),

@@ -350,17 +350,17 @@ struct LuPass {
 //   tail.broken(U)                   breaks exist and cut the strand-reads into U units (U may be 0): once, before the passes
 //   tail.pass(p)                     the units [p0, p1): table in p.a (ua virtual begin, ub source key, ushift, uoff), p.a.lr.st zeroed
 template <class Tail>
-int lu_run(const genie_index *ix, int32_t mode, int32_t flags, const uint8_t *d_bases, const int64_t *d_read_offsets, int64_t N,
-           int64_t total_bases, int64_t max_len, void *d_ws, int64_t ws_bytes, hipStream_t s, Tail &tail)
+int lu_run(const genie_index *ix, int32_t mode, const CsrBatch &b, hipStream_t s, Tail &tail)
 {
-    if (N == 0) return tail.empty();
-    const int S = (flags & GENIE_READS_BOTH_STRANDS) ? 2 : 1;
-    const bool split = (flags & GENIE_READS_SPLIT_BREAKS) != 0;
-    const long long SN = (long long)S * N;
-    const long long *off = reinterpret_cast<const long long *>(d_read_offsets);
+    if (b.N == 0) return tail.empty();
+    const int64_t N = b.N, total_bases = b.total_bases;
+    const int S = b.strands();
+    const bool split = b.split();
+    const long long SN = b.strand_reads();
+    const long long *off = reinterpret_cast<const long long *>(b.read_offsets);
     LongExFixed f;
-    const int64_t fixed = long_ex_fixed_layout(static_cast<uint8_t *>(d_ws), N, total_bases, S, split, &f);
-    uint8_t *pass = static_cast<uint8_t *>(d_ws) + fixed;
+    const int64_t fixed = long_ex_fixed_layout(static_cast<uint8_t *>(b.ws), N, total_bases, S, split, &f);
+    uint8_t *pass = static_cast<uint8_t *>(b.ws) + fixed;
     // The strand-reads as units.  On one strand the caller's offsets are the unit offsets and there is no table.
     LongExPass whole;
     long_ex_pass_layout(pass, SN, total_bases, S, false, &whole, Tail::kSmems, Tail::kFwd);
@@ -368,14 +368,14 @@ int lu_run(const genie_index *ix, int32_t mode, int32_t flags, const uint8_t *d_
     long long *const tsrc = S == 2 ? whole.ub : nullptr, *const toff = S == 2 ? whole.uoff : nullptr;
     HIP_TRY(hipMemsetAsync(flag, 0, 8, s));
     LAUNCH_BLOCKS(lu_check_kernel, (N + 1 + 255) / 256, 256, 0, s, off, (long long)N, (long long)total_bases,
-           (long long)max_len, mode, ix->dev.K, S, flag, whole.lr.st, tsrc, toff);
+           (long long)b.max_len, mode, ix->dev.K, S, flag, whole.lr.st, tsrc, toff);
     int bad = 0;
     HIP_TRY(hipMemcpyAsync(&bad, flag, 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     if (bad) return GENIE_E_INVALID;
     if (!split) return tail.whole(whole.lr, toff ? toff : off, tsrc);
 
-    const LuReads R{d_bases, off, (long long)N, S};
+    const LuReads R{b.bases, off, (long long)N, S};
     int *anybreak = flag + 1;
     HIP_TRY(hipMemsetAsync(f.qloc, 0xFF, (SN + 1) * 4, s));
     if (f.nblk > 0)
@@ -392,7 +392,7 @@ int lu_run(const genie_index *ix, int32_t mode, int32_t flags, const uint8_t *d_
     int rc = tail.broken(U);
     if (rc || U == 0) return rc;
     LongExPass a;
-    const long long C = long_ex_pass_units(SN, U, total_bases, S, ws_bytes - fixed, Tail::kSmems, Tail::kFwd);
+    const long long C = long_ex_pass_units(SN, U, total_bases, S, b.ws_bytes - fixed, Tail::kSmems, Tail::kFwd);
     long_ex_pass_layout(pass, C, total_bases, S, true, &a, Tail::kSmems, Tail::kFwd);
     for (long long p0 = 0; p0 < U; p0 += C) {
         const long long p1 = std::min(U, p0 + C), Cp = p1 - p0;
@@ -412,52 +412,44 @@ struct LuSmemTail {
     static constexpr bool kSmems = true, kFwd = true;
     const genie_index *ix;
     int32_t mode, min_len;
-    const uint8_t *d_bases;
-    long long SN;
-    int64_t *d_offsets;
-    int32_t *d_rows;
-    int64_t out_cap_rows;
-    int32_t *d_status;
+    const CsrBatch &b;
+    const CsrRows &out;
     hipStream_t s;
+    LrStep step;                     // between LR2 and LR3 (long_reads.inc), or empty
     long long row0 = 0;              // rows of the passes before
 
     int empty()
     {
-        HIP_TRY(hipMemsetAsync(d_offsets, 0, 8, s));
+        HIP_TRY(hipMemsetAsync(out.offsets, 0, 8, s));
         return GENIE_OK;
     }
     int whole(const LongArea &lr, const long long *uoff, const long long *usrc)
     {
-        int rc = lr_pipeline(ix, mode, min_len, d_bases, lr, uoff, SN, usrc, nullptr, d_offsets, d_rows, out_cap_rows, s);
+        const long long SN = b.strand_reads();
+        int rc = lr_pipeline(ix, mode, min_len, b.bases, lr, uoff, SN, usrc, nullptr, out.offsets, out.rows, out.cap_rows, step, s);
         if (rc) return rc;
-        if (d_status) HIP_TRY(hipMemcpyAsync(d_status, lr.st, SN * 4, hipMemcpyDeviceToDevice, s));
+        if (b.status) HIP_TRY(hipMemcpyAsync(b.status, lr.st, SN * 4, hipMemcpyDeviceToDevice, s));
         return GENIE_OK;
     }
     int broken(long long U)
     {
-        if (d_status) HIP_TRY(hipMemsetAsync(d_status, 0, SN * 4, s));
-        if (U == 0) HIP_TRY(hipMemsetAsync(d_offsets, 0, (SN + 1) * 8, s));
+        const long long SN = b.strand_reads();
+        if (b.status) HIP_TRY(hipMemsetAsync(b.status, 0, SN * 4, s));
+        if (U == 0) HIP_TRY(hipMemsetAsync(out.offsets, 0, (SN + 1) * 8, s));
         return GENIE_OK;
     }
     int pass(const LuPass &p)
     {
-        return pass_with(p, [&](const LongExPass &a, long long Cp, int32_t *rows, long long cap_left) {
-            return lr_pipeline(ix, mode, min_len, d_bases, a.lr, a.uoff, Cp, a.ub, a.ushift, reinterpret_cast<int64_t *>(a.loff), rows,
-                               cap_left, s);
-        });
-    }
-    // a pass whose rows come from pipeline(a, units, rows, room for rows): lr_pipeline, or a tail's own launch sequence
-    template <class F> int pass_with(const LuPass &p, F pipeline)
-    {
         const LongExPass &a = p.a;
-        const long long Cp = p.p1 - p.p0;
+        const long long SN = b.strand_reads(), Cp = p.p1 - p.p0;
         const bool last = p.p1 == p.U;
-        const long long cap_left = std::max(0ll, (long long)out_cap_rows - row0);
-        int rc = pipeline(a, Cp, cap_left > 0 ? d_rows + 4 * row0 : d_rows, cap_left);
+        const long long cap_left = std::max(0ll, (long long)out.cap_rows - row0);
+        int rc = lr_pipeline(ix, mode, min_len, b.bases, a.lr, a.uoff, Cp, a.ub, a.ushift, reinterpret_cast<int64_t *>(a.loff),
+                             cap_left > 0 ? out.rows + 4 * row0 : out.rows, cap_left, step, s);
         if (rc) return rc;
         LAUNCH_BLOCKS(lu_offsets_kernel, (SN + 1 + 255) / 256, 256, 0, s, p.R, static_cast<const unsigned long long *>(p.f.bsum),
                static_cast<const int32_t *>(p.f.qloc), p.U, p.p0, p.p1, last, static_cast<const long long *>(a.loff), row0,
-               reinterpret_cast<long long *>(d_offsets));
+               reinterpret_cast<long long *>(out.offsets));
         if (!last) {
             long long pass_rows = 0;
             HIP_TRY(hipMemcpyAsync(&pass_rows, a.loff + Cp, 8, hipMemcpyDeviceToHost, s));
@@ -473,16 +465,14 @@ struct LuSmemTail {
 struct LuMsTail {
     static constexpr bool kSmems = false, kFwd = true;
     const genie_index *ix;
-    const uint8_t *d_bases;
-    const long long *off;
-    long long N;
-    int S;
-    long long positions;             // S total_bases
-    int32_t *d_ms, *d_lohi, *d_status;
+    const CsrBatch &b;
+    int32_t *d_ms, *d_lohi;
     hipStream_t s;
+    LrStep step;                     // between LR2 and LRM (long_reads.inc), or empty
 
     int fill()                       // no match anywhere
     {
+        const long long positions = b.positions();
         if (positions > 0) HIP_TRY(hipMemsetAsync(d_ms, 0, positions * 4, s));
         if (positions > 0 && d_lohi) HIP_TRY(hipMemsetAsync(d_lohi, 0xFF, positions * 8, s));
         return GENIE_OK;
@@ -490,18 +480,23 @@ struct LuMsTail {
     int empty() { return fill(); }
     int whole(const LongArea &lr, const long long *uoff, const long long *usrc)
     {
-        LAUNCH(lr_ms_edges_kernel, dim3(64), dim3(256), 0, s, off, N, S, positions, d_ms, reinterpret_cast<int2 *>(d_lohi));
-        int rc = lr_match_stats(ix, d_bases, lr, uoff, S * N, usrc, nullptr, d_ms, d_lohi, s);       // a strand-read's offset is its virtual position
+        const long long SN = b.strand_reads();
+        LAUNCH(lr_ms_edges_kernel, dim3(64), dim3(256), 0, s, reinterpret_cast<const long long *>(b.read_offsets), (long long)b.N,
+               b.strands(), b.positions(), d_ms, reinterpret_cast<int2 *>(d_lohi));
+        int rc = lr_match_stats(ix, b.bases, lr, uoff, SN, usrc, nullptr, d_ms, d_lohi, step, s);     // a strand-read's offset is its virtual position
         if (rc) return rc;
-        if (d_status) HIP_TRY(hipMemcpyAsync(d_status, lr.st, S * N * 4, hipMemcpyDeviceToDevice, s));
+        if (b.status) HIP_TRY(hipMemcpyAsync(b.status, lr.st, SN * 4, hipMemcpyDeviceToDevice, s));
         return GENIE_OK;
     }
     int broken(long long)
     {
-        if (d_status) HIP_TRY(hipMemsetAsync(d_status, 0, S * N * 4, s));
+        if (b.status) HIP_TRY(hipMemsetAsync(b.status, 0, b.strand_reads() * 4, s));
         return fill();
     }
-    int pass(const LuPass &p) { return lr_match_stats(ix, d_bases, p.a.lr, p.a.uoff, p.p1 - p.p0, p.a.ub, p.a.ua, d_ms, d_lohi, s); }
+    int pass(const LuPass &p)
+    {
+        return lr_match_stats(ix, b.bases, p.a.lr, p.a.uoff, p.p1 - p.p0, p.a.ub, p.a.ua, d_ms, d_lohi, step, s);
+    }
 };
 
 }  // namespace
@@ -511,14 +506,11 @@ int64_t find_smems_long_ex_workspace_bytes(int64_t N, int64_t total_bases, int32
     return long_ex_bytes(N, total_bases, flags, true);
 }
 
-int launch_find_smems_long_ex(const genie_index *ix, int32_t mode, int32_t flags, const uint8_t *d_bases, const int64_t *d_read_offsets,
-                              int64_t N, int64_t total_bases, int64_t max_len, int32_t min_len, int64_t *d_offsets, int32_t *d_rows,
-                              int64_t out_cap_rows, int32_t *d_status, void *d_ws, int64_t ws_bytes, void *stream)
+int launch_find_smems_long_ex(const genie_index *ix, int32_t mode, int32_t min_len, const CsrBatch &b, const CsrRows &out, void *stream)
 {
     hipStream_t s = (hipStream_t)stream;
-    const int S = (flags & GENIE_READS_BOTH_STRANDS) ? 2 : 1;
-    LuSmemTail tail{ix, mode, min_len, d_bases, (long long)S * N, d_offsets, d_rows, out_cap_rows, d_status, s};
-    return lu_run(ix, mode, flags, d_bases, d_read_offsets, N, total_bases, max_len, d_ws, ws_bytes, s, tail);
+    LuSmemTail tail{ix, mode, min_len, b, out, s};
+    return lu_run(ix, mode, b, s, tail);
 }
 
 int64_t match_stats_workspace_bytes(int64_t N, int64_t total_bases, int32_t flags)
@@ -526,13 +518,9 @@ int64_t match_stats_workspace_bytes(int64_t N, int64_t total_bases, int32_t flag
     return long_ex_bytes(N, total_bases, flags, false);
 }
 
-int launch_match_stats(const genie_index *ix, int32_t flags, const uint8_t *d_bases, const int64_t *d_read_offsets, int64_t N,
-                       int64_t total_bases, int64_t max_len, int32_t *d_ms, int32_t *d_lohi, int32_t *d_status, void *d_ws,
-                       int64_t ws_bytes, void *stream)
+int launch_match_stats(const genie_index *ix, const CsrBatch &b, int32_t *d_ms, int32_t *d_lohi, void *stream)
 {
     hipStream_t s = (hipStream_t)stream;
-    const int S = (flags & GENIE_READS_BOTH_STRANDS) ? 2 : 1;
-    LuMsTail tail{ix, d_bases, reinterpret_cast<const long long *>(d_read_offsets), (long long)N, S, (long long)S * total_bases,
-                  d_ms, d_lohi, d_status, s};
-    return lu_run(ix, GENIE_MODE_BWA, flags, d_bases, d_read_offsets, N, total_bases, max_len, d_ws, ws_bytes, s, tail);
+    LuMsTail tail{ix, b, d_ms, d_lohi, s};
+    return lu_run(ix, GENIE_MODE_BWA, b, s, tail);
 }

@@ -404,26 +404,25 @@ int64_t find_mems_workspace_bytes(int64_t N, int64_t total_bases, int32_t flags)
 }
 
 // cg == nullptr: genie_find_mems; else genie_find_mems_contigs, whose walks run the CONTIGS instances
-static int find_mems_any(const genie_index *ix, const CtgPair *cg, int32_t flags, const uint8_t *d_bases, const int64_t *d_read_offsets,
-                         int64_t N, int64_t total_bases, int64_t max_len, int32_t min_len, int32_t max_occ, int64_t *d_offsets,
-                         int32_t *d_rows, int64_t out_cap_rows, int32_t *d_status, int64_t *d_totals, void *d_ws, int64_t ws_bytes,
+static int find_mems_any(const genie_index *ix, const CtgPair *cg, const CsrBatch &b, int32_t min_len, int32_t max_occ, const CsrRows &out,
                          void *stream)
 {
     hipStream_t s = (hipStream_t)stream;
-    if (N == 0) {
-        HIP_TRY(hipMemsetAsync(d_offsets, 0, 8, s));
-        if (d_totals) HIP_TRY(hipMemsetAsync(d_totals, 0, 16, s));
+    if (b.N == 0) {
+        HIP_TRY(hipMemsetAsync(out.offsets, 0, 8, s));
+        if (out.totals) HIP_TRY(hipMemsetAsync(out.totals, 0, 16, s));
         return GENIE_OK;
     }
-    const int S = (flags & GENIE_READS_BOTH_STRANDS) ? 2 : 1;
-    const long long positions = (long long)S * total_bases;
+    const long long positions = b.positions();
     MemArea a;
-    const int64_t used = mem_layout(static_cast<uint8_t *>(d_ws), N, total_bases, flags, &a);
-    const int64_t stats_bytes = ws_bytes - (used - ws_align(match_stats_workspace_bytes(N, total_bases, flags)));
-    int rc = launch_match_stats(ix, flags, d_bases, d_read_offsets, N, total_bases, max_len, a.ms, reinterpret_cast<int32_t *>(a.lohi),
-                                d_status, a.stats, stats_bytes, stream);
+    const int64_t used = mem_layout(static_cast<uint8_t *>(b.ws), b.N, b.total_bases, b.flags, &a);
+    // the matching statistics of the same batch into this call's workspace; what the caller gave beyond `used` is theirs too
+    CsrBatch stats = b;
+    stats.ws = a.stats;
+    stats.ws_bytes = b.ws_bytes - (used - ws_align(match_stats_workspace_bytes(b.N, b.total_bases, b.flags)));
+    int rc = launch_match_stats(ix, stats, a.ms, reinterpret_cast<int32_t *>(a.lohi), stream);
     if (rc) return rc;
-    const LuReads R{d_bases, reinterpret_cast<const long long *>(d_read_offsets), (long long)N, S};
+    const LuReads R{b.bases, reinterpret_cast<const long long *>(b.read_offsets), (long long)b.N, b.strands()};
     const CtgPair tab = cg ? *cg : CtgPair{{nullptr, 0, 0, 0}, {nullptr, 0, 0, 0}};
     const size_t lds = cg ? ctg_lds_bytes(tab.big) : 0;
     auto count_k = cg ? mem_walk_kernel<false, true> : mem_walk_kernel<false, false>;
@@ -438,39 +437,31 @@ static int find_mems_any(const genie_index *ix, const CtgPair *cg, int32_t flags
                       static_cast<int4 *>(nullptr), 0ll);
     }
     LAUNCH(scan_block_sums_kernel, dim3(1), dim3(kScanBlock), 0, s, a.bsum, a.nwalk);
-    LAUNCH_BLOCKS(mem_offsets_kernel, ((long long)S * N + 1 + 255) / 256, 256, 0, s, R, positions, a.nwalk,
+    LAUNCH_BLOCKS(mem_offsets_kernel, (b.strand_reads() + 1 + 255) / 256, 256, 0, s, R, positions, a.nwalk,
                   static_cast<const unsigned long long *>(a.kept), static_cast<const unsigned long long *>(a.pre), static_cast<const unsigned long long *>(a.bsum),
-                  static_cast<const unsigned long long *>(a.skipped), reinterpret_cast<long long *>(d_offsets),
-                  reinterpret_cast<long long *>(d_totals));
-    if (d_rows && out_cap_rows > 0 && a.nwin > 0)
+                  static_cast<const unsigned long long *>(a.skipped), reinterpret_cast<long long *>(out.offsets),
+                  reinterpret_cast<long long *>(out.totals));
+    if (out.rows && out.cap_rows > 0 && a.nwin > 0)
         LAUNCH_SLICED(fill_k, fill_k, a.nwalk, kMemWalk, lds, s, ix->dev, tab, positions, (int)min_len,
                       static_cast<const int32_t *>(a.ms), static_cast<const int2 *>(a.lohi), static_cast<const int2 *>(a.seed),
                       static_cast<const int32_t *>(a.pos), static_cast<const uint8_t *>(a.prev), a.pre, a.kept, a.bsum,
-                      reinterpret_cast<int4 *>(d_rows), (long long)out_cap_rows);
+                      reinterpret_cast<int4 *>(out.rows), (long long)out.cap_rows);
     return GENIE_OK;
 }
 
-int launch_find_mems(const genie_index *ix, int32_t flags, const uint8_t *d_bases, const int64_t *d_read_offsets, int64_t N,
-                     int64_t total_bases, int64_t max_len, int32_t min_len, int32_t max_occ, int64_t *d_offsets, int32_t *d_rows,
-                     int64_t out_cap_rows, int32_t *d_status, int64_t *d_totals, void *d_ws, int64_t ws_bytes, void *stream)
+int launch_find_mems(const genie_index *ix, const CsrBatch &b, int32_t min_len, int32_t max_occ, const CsrRows &out, void *stream)
 {
-    return find_mems_any(ix, nullptr, flags, d_bases, d_read_offsets, N, total_bases, max_len, min_len, max_occ, d_offsets, d_rows,
-                         out_cap_rows, d_status, d_totals, d_ws, ws_bytes, stream);
+    return find_mems_any(ix, nullptr, b, min_len, max_occ, out, stream);
 }
 
-// The table is the caller's and the samples live in LDS: the workspace is the parent's
-int64_t find_mems_contigs_workspace_bytes(int64_t N, int64_t total_bases, int32_t flags, int64_t n_contigs)
+int64_t find_mems_contigs_workspace_bytes(int64_t N, int64_t total_bases, int32_t flags)
 {
-    (void)n_contigs;
     return find_mems_workspace_bytes(N, total_bases, flags);
 }
 
-int launch_find_mems_contigs(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs, int32_t flags,
-                             const uint8_t *d_bases, const int64_t *d_read_offsets, int64_t N, int64_t total_bases, int64_t max_len,
-                             int32_t min_len, int32_t max_occ, int64_t *d_offsets, int32_t *d_rows, int64_t out_cap_rows,
-                             int32_t *d_status, int64_t *d_totals, void *d_ws, int64_t ws_bytes, void *stream)
+int launch_find_mems_contigs(const genie_index *ix, const ContigTable &ctg, const CsrBatch &b, int32_t min_len, int32_t max_occ,
+                             const CsrRows &out, void *stream)
 {
-    const CtgPair tab{ctg_tab(d_contig_offsets, n_contigs, kCtgWalkSamples), ctg_tab(d_contig_offsets, n_contigs, kCtgSamples)};
-    return find_mems_any(ix, &tab, flags, d_bases, d_read_offsets, N, total_bases, max_len, min_len, max_occ, d_offsets, d_rows,
-                         out_cap_rows, d_status, d_totals, d_ws, ws_bytes, stream);
+    const CtgPair tab{ctg_tab(ctg.offsets, ctg.n_contigs, kCtgWalkSamples), ctg_tab(ctg.offsets, ctg.n_contigs, kCtgSamples)};
+    return find_mems_any(ix, &tab, b, min_len, max_occ, out, stream);
 }

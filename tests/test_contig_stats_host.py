@@ -99,6 +99,9 @@ def test_argument_checks_before_device(pkg):
                 assert ms(**bad) == INVALID, bad
             assert ms(wsp=None) == CAPACITY and ms(wsp=C.c_void_p(al + 16)) == CAPACITY and ms(wsb=ms_ok - 1) == CAPACITY
             assert ms(tab=None, wsp=None) == INVALID                # a bad argument is reported before a capacity
+            assert ms(nc=2**31 - 1, wsp=None) == TOO_LONG           # ... the table's too; its own checks come behind the others
+            assert ms(nc=2**31 - 1, tt=odd8) == INVALID and ms(nc=2**31 - 1, wsb=-1) == INVALID
+            assert ms(n=0, offs=None, wsp=None, wsb=0) == NO_DEVICE
             assert ms(lohi=None) == NO_DEVICE and ms(st=None, tt=None) == NO_DEVICE
             assert ms(n=0, wsp=None, wsb=0, total=0, bases=None, out=None) == NO_DEVICE
 
@@ -119,6 +122,11 @@ def test_argument_checks_before_device(pkg):
                 assert sm(mode=1) == INVALID and sm(mode=2) == INVALID      # SPLIT_BREAKS has the BWA traversal alone
             assert sm(wsp=None) == CAPACITY and sm(wsp=C.c_void_p(al + 16)) == CAPACITY and sm(wsb=sm_ok - 1) == CAPACITY
             assert sm(tab=None, wsp=None) == INVALID
+            assert sm(nc=2**31 - 1, wsp=None) == TOO_LONG
+            assert sm(nc=2**31 - 1, tt=odd8) == INVALID and sm(nc=2**31 - 1, wsb=-1) == INVALID and sm(nc=2**31 - 1, mode=3) == INVALID
+            if not fl & SPLIT:
+                assert sm(mode=1) == NO_DEVICE and sm(mode=2) == NO_DEVICE      # the tables a mode needs are looked at last
+            assert sm(n=0, offs=None, rows=None, wsp=None, wsb=0) == NO_DEVICE and sm(n=0, out=None, wsp=None, wsb=0) == INVALID
             assert sm(st=None, tt=None) == NO_DEVICE and sm(cap=0) == NO_DEVICE
             assert sm(n=0, wsp=None, wsb=0, total=0, bases=None, rows=None) == NO_DEVICE
     finally:

@@ -103,6 +103,9 @@ def test_argument_checks_before_device(pkg):
                 assert mems(**bad) == INVALID, bad
             assert mems(wsp=None) == CAPACITY and mems(wsp=C.c_void_p(al + 16)) == CAPACITY and mems(wsb=bytes_ok - 1) == CAPACITY
             assert mems(tab=None, wsp=None) == INVALID              # a bad argument is reported before a capacity
+            assert mems(nc=2**31 - 1, wsp=None) == TOO_LONG         # ... the table's too; its own checks come behind the others
+            assert mems(nc=2**31 - 1, st=odd4) == INVALID and mems(nc=2**31 - 1, wsb=-1) == INVALID
+            assert mems(n=0, offs=None, wsp=None, wsb=0) == INVALID     # the offsets hold N + 1 entries: one at least
             assert mems(rows=None) == NO_DEVICE and mems(st=None, tt=None, rows=None, cap=0) == NO_DEVICE
             assert mems(n=0, wsp=None, wsb=0, total=0, bases=None) == NO_DEVICE
 

@@ -108,12 +108,17 @@ def test_long_ex_argument_checks_before_device(pkg):
             assert call(rows=C.c_void_p(al + 4)) == -1              # rows must be 16-byte aligned
             assert call(wsp=C.c_void_p(al + 16)) == -1              # workspace 256-byte aligned
             assert call(wsb=bytes_ok - 1) == -10                    # GENIE_E_CAPACITY
+            assert call(wsb=-1) == -10                              # this call does not look at the sign: just too small
+            assert call(wsp=None, wsb=0) == -1 and call(wsp=C.c_void_p(al + 16), wsb=0) == -1      # ... and a missing or
+            assert call(n=0, wsp=C.c_void_p(al + 16)) == -1         # misaligned workspace is a bad argument, reads or none
+            assert call(mode=3, wsb=0) == -1 and call(flags=fl | 4, wsb=0) == -1
             if fl & SPLIT:                                          # the split semantics have no LUT / RMI traversal
                 assert call(mode=1) == -1 and call(mode=2) == -1
             else:
                 assert call(mode=1) == -4
             assert call() == -4                                     # GENIE_E_NO_DEVICE: every argument was fine
             assert call(n=0, offs=None, rows=None, wsp=None, total=0, bases=None) == -4
+            assert call(n=0, offs=None, rows=None, wsp=None, total=0, bases=None, wsb=-1) == -4
     finally:
         lib.genie_index_destroy(h)
 
