@@ -55,6 +55,8 @@ SYMBOLS = [
     "genie_locate_contigs", "genie_locate_contigs_tmp_bytes", "genie_contig_coords",
     "genie_match_stats_contigs", "genie_match_stats_contigs_workspace_bytes",
     "genie_find_smems_contigs", "genie_find_smems_contigs_workspace_bytes",
+    "genie_match_stats_min_occ", "genie_match_stats_min_occ_workspace_bytes",
+    "genie_find_smems_min_occ", "genie_find_smems_min_occ_workspace_bytes",
     "genie_reads_from_text", "genie_reads_from_text_tmp_bytes",
     "genie_reads_from_fasta", "genie_reads_from_fasta_tmp_bytes",
     "genie_reference_segments", "genie_reference_segments_tmp_bytes", "genie_segment_coords",
@@ -80,7 +82,7 @@ class GenieError(RuntimeError):
 
 def build(force=False):
     """Compile libgenie_smem.so for gfx950 with hipcc (csrc/Makefile), in-tree."""
-    srcs = [os.path.join(CSRC, f) for f in ("kernels.hip", "index_build.hip", "short_read_kernel.inc", "match_table_kernel.inc", "match_table_body.inc", "match_table_long_body.inc", "split_reads.inc", "long_reads.inc", "long_units.inc", "exact_match.inc", "contigs.inc", "contig_stats.inc", "mems.inc", "text_reads.inc", "fasta_reads.inc", "segments.inc", "capi.cpp", "index_host.cpp", "genie_internal.h", "Makefile")]
+    srcs = [os.path.join(CSRC, f) for f in ("kernels.hip", "index_build.hip", "short_read_kernel.inc", "match_table_kernel.inc", "match_table_body.inc", "match_table_long_body.inc", "split_reads.inc", "long_reads.inc", "long_units.inc", "lu_seg_body.inc", "exact_match.inc", "contigs.inc", "contig_stats.inc", "min_occ.inc", "mems.inc", "text_reads.inc", "fasta_reads.inc", "segments.inc", "capi.cpp", "index_host.cpp", "genie_internal.h", "Makefile")]
     srcs.append(os.path.join(os.path.dirname(_PKG), "include", "genie_smem.h"))
     newest = max(os.path.getmtime(s) for s in srcs)
     if force or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < newest:
@@ -157,6 +159,10 @@ def lib():
         "genie_match_stats_contigs_workspace_bytes": (i64, [i64, i64, i64, i32, i64]),
         "genie_find_smems_contigs": (C.c_int, [vp, vp, i64, i32, i32, vp, vp, i64, i64, i64, i32, vp, vp, i64, vp, vp, vp, i64, vp]),
         "genie_find_smems_contigs_workspace_bytes": (i64, [i64, i64, i64, i32, i64]),
+        "genie_match_stats_min_occ": (C.c_int, [vp, i32, i32, vp, vp, i64, i64, i64, vp, vp, vp, vp, vp, i64, vp]),
+        "genie_match_stats_min_occ_workspace_bytes": (i64, [i64, i64, i64, i32]),
+        "genie_find_smems_min_occ": (C.c_int, [vp, i32, i32, vp, vp, i64, i64, i64, i32, i32, vp, vp, i64, vp, vp, vp, i64, vp]),
+        "genie_find_smems_min_occ_workspace_bytes": (i64, [i64, i64, i64, i32]),
         "genie_reads_from_text_tmp_bytes": (i64, [i64, i64]),
         "genie_reads_from_text": (C.c_int, [vp, i64, i32, i32, vp, vp, i64, vp, i64, vp, vp, i64, vp]),
         "genie_reads_from_fasta_tmp_bytes": (i64, [i64, i64]),

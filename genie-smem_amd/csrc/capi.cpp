@@ -657,6 +657,46 @@ int genie_find_smems_contigs(const genie_index *ix, const int64_t *d_contig_offs
     return launch_find_smems_contigs(ix, {d_contig_offsets, n_contigs}, mode, min_len, b, {d_offsets, d_rows, out_cap_rows, d_totals}, stream);
 }
 
+int64_t genie_match_stats_min_occ_workspace_bytes(int64_t N, int64_t total_bases, int64_t max_len, int32_t flags)
+{
+    if (bad_batch(N, total_bases, max_len, flags, kReadFlags)) return (int64_t)GENIE_E_INVALID;
+    return match_stats_min_occ_workspace_bytes(N, total_bases, flags);
+}
+
+int genie_match_stats_min_occ(const genie_index *ix, int32_t flags, int32_t min_occ, const uint8_t *d_bases, const int64_t *d_read_offsets,
+                              int64_t N, int64_t total_bases, int64_t max_len, int32_t *d_ms, int32_t *d_lohi, int32_t *d_status,
+                              int64_t *d_totals, void *d_workspace, int64_t workspace_bytes, void *stream)
+{
+    const CsrBatch b{flags, d_bases, d_read_offsets, N, total_bases, max_len, d_status, d_workspace, workspace_bytes};
+    // argument checks first: they need no device image
+    if (!ix || bad_stats_args(b, d_ms, d_lohi) || min_occ < 1 || misaligned(d_totals, 7)) return GENIE_E_INVALID;
+    int rc = workspace_args(b, match_stats_min_occ_workspace_bytes(N, total_bases, flags));
+    if (rc || (rc = ready(ix))) return rc;
+    return launch_match_stats_min_occ(ix, min_occ, b, d_ms, d_lohi, d_totals, stream);
+}
+
+int64_t genie_find_smems_min_occ_workspace_bytes(int64_t N, int64_t total_bases, int64_t max_len, int32_t flags)
+{
+    if (bad_batch(N, total_bases, max_len, flags, kReadFlags)) return (int64_t)GENIE_E_INVALID;
+    return find_smems_min_occ_workspace_bytes(N, total_bases, flags);
+}
+
+int genie_find_smems_min_occ(const genie_index *ix, int32_t mode, int32_t flags, const uint8_t *d_bases, const int64_t *d_read_offsets,
+                             int64_t N, int64_t total_bases, int64_t max_len, int32_t min_len, int32_t min_occ, int64_t *d_offsets,
+                             int32_t *d_rows, int64_t out_cap_rows, int32_t *d_status, int64_t *d_totals, void *d_workspace,
+                             int64_t workspace_bytes, void *stream)
+{
+    const CsrBatch b{flags, d_bases, d_read_offsets, N, total_bases, max_len, d_status, d_workspace, workspace_bytes};
+    // the checks of genie_find_smems_long_ex, in its order, then this call's own
+    if (!ix || bad_batch(b, kReadFlags) || bad_smem_mode(mode, flags) || out_cap_rows < 0 || !d_offsets ||
+        (N > 0 && (!d_rows || !d_workspace)) || misaligned(d_rows, 15) || misaligned(d_workspace, 255) || min_occ < 1 ||
+        misaligned(d_totals, 7))
+        return GENIE_E_INVALID;
+    int rc = workspace_args(b, find_smems_min_occ_workspace_bytes(N, total_bases, flags));
+    if (rc || (rc = ready(ix)) || (rc = mode_tables(ix, mode))) return rc;
+    return launch_find_smems_min_occ(ix, mode, min_len, min_occ, b, {d_offsets, d_rows, out_cap_rows, d_totals}, stream);
+}
+
 int64_t genie_exact_match_workspace_bytes(int64_t N, int64_t total_bases, int64_t max_len, int32_t flags)
 {
     if (bad_batch(N, total_bases, max_len, flags, GENIE_READS_BOTH_STRANDS)) return (int64_t)GENIE_E_INVALID;

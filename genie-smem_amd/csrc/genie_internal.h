@@ -436,6 +436,13 @@ int launch_match_stats_contigs(const genie_index *ix, const ContigTable &ctg, co
 int64_t find_smems_contigs_workspace_bytes(int64_t N, int64_t total_bases, int32_t flags);
 int launch_find_smems_contigs(const genie_index *ix, const ContigTable &ctg, int32_t mode, int32_t min_len, const CsrBatch &b,
                               const CsrRows &out, void *stream);
+// min_occ.inc: matching statistics and SMEMs of what occurs at least min_occ times
+int64_t match_stats_min_occ_workspace_bytes(int64_t N, int64_t total_bases, int32_t flags);
+int launch_match_stats_min_occ(const genie_index *ix, int32_t min_occ, const CsrBatch &b, int32_t *d_ms, int32_t *d_lohi,
+                               int64_t *d_totals, void *stream);
+int64_t find_smems_min_occ_workspace_bytes(int64_t N, int64_t total_bases, int32_t flags);
+int launch_find_smems_min_occ(const genie_index *ix, int32_t mode, int32_t min_len, int32_t min_occ, const CsrBatch &b,
+                              const CsrRows &out, void *stream);
 int64_t reads_from_text_tmp_bytes(int64_t text_bytes, int64_t cap_reads);
 int launch_reads_from_text(const uint8_t *d_text, int64_t text_bytes, int32_t format, int32_t flags, const uint8_t *code_of_byte,
                            uint8_t *d_bases, int64_t cap_bases, int64_t *d_read_offsets, int64_t cap_reads, int64_t *out5,

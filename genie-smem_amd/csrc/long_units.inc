@@ -132,103 +132,21 @@ __global__ void __launch_bounds__(256) lu_seg_kernel(DevIndex ix, LuReads R, uns
                                                      int32_t *__restrict__ qloc, int *__restrict__ anybreak, long long p0,
                                                      long long p1, long long *__restrict__ ua, long long *__restrict__ ub)
 {
-    __shared__ uint8_t sflag[kLuSub + 8];
-    __shared__ int wtot[4];
-    const int t = threadIdx.x, lane = t & (kWave - 1), wave = t >> 6;
-    const long long c0 = (long long)blockIdx.x * kLuChunk;
-    long long run = 0;                                           // starts in front of the current kLuSub positions
-    if (SCATTER) {
-        const long long a = (long long)bsum[blockIdx.x], b = (long long)bsum[blockIdx.x + 1];
-        if (b <= p0 || a > p1) return;                           // block-uniform: no unit of the pass begins or ends here
-        run = a;
-    }
-    const uint32_t present = split_present_bases(ix);
-    const long long vlo = R.at(0), vhi = R.at(R.count());
-    long long q0 = R.find(c0);
-    LuSr s0 = lu_sr(R, q0), s1 = lu_sr(R, q0 + 1 < R.count() ? q0 + 1 : q0);
-    bool brk = false;
-    for (int sub = 0; sub < kLuChunk / kLuSub; sub++) {
-        const long long cs = c0 + sub * kLuSub;
-        if (cs >= vhi) break;                                    // block-uniform
-        if (cs >= s0.at + (s0.o2 - s0.o)) {
-            q0 = R.find(cs);
-            s0 = lu_sr(R, q0);
-            s1 = lu_sr(R, q0 + 1 < R.count() ? q0 + 1 : q0);
-        }
-        const long long len0 = s0.o2 - s0.o, pb = cs - 1 - s0.at;
-        if (pb >= 0 && pb + kLuSub + 2 <= len0) {                // all inside one strand-read (block-uniform): 32-bit work only
-            const uint8_t *b0 = R.bases + (s0.rev ? s0.o2 - 1 - pb : s0.o + pb);
-            const int jf = pb == 0 ? 0 : -1, jl = len0 - 1 - pb <= kLuSub + 1 ? (int)(len0 - 1 - pb) : -1;
-            const uint32_t x = s0.rev ? 3u : 0u;
-            for (int j = t; j < kLuSub + 2; j += 256) {
-                const uint32_t c = s0.rev ? b0[-j] : b0[j];
-                const bool good = c < 4u && ((present >> (c ^ x)) & 1u);
-                sflag[j] = (uint8_t)((good ? 1u : 0u) | (j == jf ? 2u : 0u) | (j == jl ? 4u : 0u) | 8u);
-            }
-        } else {
-            for (int j = t; j < kLuSub + 2; j += 256) sflag[j] = (uint8_t)lu_flags(R, present, cs - 1 + j, vlo, vhi, s0, s1);
-        }
-        __syncthreads();
-        uint32_t f[kLuPer + 2];
-#pragma unroll
-        for (int i = 0; i < kLuPer + 2; i++) f[i] = sflag[kLuPer * t + i];
-        uint32_t sm = 0, em = 0;
-#pragma unroll
-        for (int i = 0; i < kLuPer; i++) {
-            const uint32_t cur = f[i + 1];
-            const bool g = cur & 1u;
-            if (g && ((cur & 2u) || !(f[i] & 1u))) sm |= 1u << i;
-            if (g && ((cur & 4u) || !(f[i + 2] & 1u))) em |= 1u << i;
-            brk = brk || (cur & 9u) == 8u;
-        }
-        const int cnt = __popc(sm);
-        int inc = cnt;
-#pragma unroll
-        for (int o = 1; o < kWave; o <<= 1) {
-            const int x = __shfl_up(inc, o, kWave);
-            if (lane >= o) inc += x;
-        }
-        if (lane == kWave - 1) wtot[wave] = inc;
-        __syncthreads();
-        int all = 0;
-        long long seen = run + inc - cnt;                        // starts in front of the thread's positions
-        for (int w = 0; w < 4; w++) {
-            const int x = wtot[w];
-            seen += w < wave ? x : 0;
-            all += x;
-        }
-        const long long v0 = cs + kLuPer * t;
-        if (!SCATTER) {
-#pragma unroll
-            for (int i = 0; i < kLuPer; i++) {
-                if (f[i + 1] & 2u) {                             // a strand-read begins: also the empty ones that sit here
-                    const long long v = v0 + i;
-                    const int32_t loc = (int32_t)(seen + __popc(sm & ((1u << i) - 1u)));
-                    const long long q = R.find(v);
-                    qloc[q] = loc;
-                    for (long long e = q - 1; e >= 0 && R.at(e) == v; e--) qloc[e] = loc;
-                }
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < kLuPer; i++) {
-                if ((sm >> i) & 1u) seen++;
-                const long long k = seen - 1;                    // the segment a good position belongs to
-                if (k >= p0 && k < p1) {
-                    if ((sm >> i) & 1u) ua[k - p0] = v0 + i;
-                    if ((em >> i) & 1u) ub[k - p0] = v0 + i + 1;
-                }
-            }
-        }
-        run += all;
-        __syncthreads();
-    }
-    if (!SCATTER) {
-        // one writer per block, and none once the flag is up
-        if (__syncthreads_or(brk) && t == 0 && __hip_atomic_load(anybreak, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0)
-            atomicOr(anybreak, 1);
-        if (t == 0) bsum[blockIdx.x] = (unsigned long long)run;
-    }
+#define LU_SEG_USABLE split_present_bases(ix)
+#include "lu_seg_body.inc"
+#undef LU_SEG_USABLE
+}
+
+// The same for a call with a minimum occurrence count (min_occ.inc): usable are the bases the reference holds that often
+template <bool SCATTER>
+__global__ void __launch_bounds__(256) lu_seg_occ_kernel(DevIndex ix, LuReads R, unsigned long long *__restrict__ bsum,
+                                                         int32_t *__restrict__ qloc, int *__restrict__ anybreak, long long p0,
+                                                         long long p1, long long *__restrict__ ua, long long *__restrict__ ub,
+                                                         int min_occ)
+{
+#define LU_SEG_USABLE split_usable_bases(ix, min_occ)
+#include "lu_seg_body.inc"
+#undef LU_SEG_USABLE
 }
 
 // ua / ub: virtual begin / end of the pass's units.  Afterwards ub holds the unit's source key.
@@ -349,8 +267,10 @@ struct LuPass {
 //                                    are in lr.st
 //   tail.broken(U)                   breaks exist and cut the strand-reads into U units (U may be 0): once, before the passes
 //   tail.pass(p)                     the units [p0, p1): table in p.a (ua virtual begin, ub source key, ushift, uoff), p.a.lr.st zeroed
+// min_occ: a base counts as usable (no break, with GENIE_READS_SPLIT_BREAKS) when the reference holds it that often; 1, the
+// default, is "present in the reference" and launches the kernels as ever.
 template <class Tail>
-int lu_run(const genie_index *ix, int32_t mode, const CsrBatch &b, hipStream_t s, Tail &tail)
+int lu_run(const genie_index *ix, int32_t mode, const CsrBatch &b, hipStream_t s, Tail &tail, int32_t min_occ = 1)
 {
     if (b.N == 0) return tail.empty();
     const int64_t N = b.N, total_bases = b.total_bases;
@@ -378,7 +298,10 @@ int lu_run(const genie_index *ix, int32_t mode, const CsrBatch &b, hipStream_t s
     const LuReads R{b.bases, off, (long long)N, S};
     int *anybreak = flag + 1;
     HIP_TRY(hipMemsetAsync(f.qloc, 0xFF, (SN + 1) * 4, s));
-    if (f.nblk > 0)
+    if (f.nblk > 0 && min_occ > 1)
+        LAUNCH_BLOCKS(lu_seg_occ_kernel<false>, f.nblk, 256, 0, s, ix->dev, R, f.bsum, f.qloc, anybreak, 0ll, 0ll,
+               static_cast<long long *>(nullptr), static_cast<long long *>(nullptr), (int)min_occ);
+    else if (f.nblk > 0)
         LAUNCH_BLOCKS(lu_seg_kernel<false>, f.nblk, 256, 0, s, ix->dev, R, f.bsum, f.qloc, anybreak, 0ll, 0ll,
                static_cast<long long *>(nullptr), static_cast<long long *>(nullptr));
     LAUNCH(scan_block_sums_kernel, dim3(1), dim3(kScanBlock), 0, s, f.bsum, f.nblk);
@@ -397,7 +320,11 @@ int lu_run(const genie_index *ix, int32_t mode, const CsrBatch &b, hipStream_t s
     for (long long p0 = 0; p0 < U; p0 += C) {
         const long long p1 = std::min(U, p0 + C), Cp = p1 - p0;
         HIP_TRY(hipMemsetAsync(a.lr.st, 0, Cp * 4, s));           // GENIE_READ_OK: a unit holds no break
-        LAUNCH_BLOCKS(lu_seg_kernel<true>, f.nblk, 256, 0, s, ix->dev, R, f.bsum, f.qloc, anybreak, p0, p1, a.ua, a.ub);
+        if (min_occ > 1)
+            LAUNCH_BLOCKS(lu_seg_occ_kernel<true>, f.nblk, 256, 0, s, ix->dev, R, f.bsum, f.qloc, anybreak, p0, p1, a.ua, a.ub,
+                          (int)min_occ);
+        else
+            LAUNCH_BLOCKS(lu_seg_kernel<true>, f.nblk, 256, 0, s, ix->dev, R, f.bsum, f.qloc, anybreak, p0, p1, a.ua, a.ub);
         LAUNCH_BLOCKS(lu_units_kernel, (Cp + 255) / 256, 256, 0, s, R, Cp, static_cast<const long long *>(a.ua), a.ub,
                a.ulen, a.ushift);
         rc = launch_compact(a.ulen, nullptr, Cp, 0x7fffffff, reinterpret_cast<int64_t *>(a.uoff), nullptr, 0, a.lr.sums, s);

@@ -50,6 +50,25 @@ __device__ __forceinline__ uint32_t split_present_bases(const DevIndex &ix)
     return m;
 }
 
+// Bit b set: base b occurs at least k times in the reference (min_occ.inc: a base that is not "rare at k").  The counts are
+// those split_present_bases tests against zero -- the suffixes of P or more bases from the directory, the last P-1 positions
+// from the tail -- so k == 1 gives its mask.
+__device__ __forceinline__ uint32_t split_usable_bases(const DevIndex &ix, int k)
+{
+    const int sh = 2 * (ix.P - 1);
+    const int L = ix.n < ix.P - 1 ? ix.n : ix.P - 1;
+    const uint32_t t = ix.padtail[L] >> (2 * (ix.P - L));
+    uint32_t m = 0;
+    for (int b = 0; b < 4; b++) {
+        const uint32_t x0 = (uint32_t)b << sh, x1 = (uint32_t)(b + 1) << sh;
+        long long cnt = (long long)ix.dir[x1] - (long long)ix.dir[x0];
+        for (int l = 0; l <= L; l++) cnt -= (ix.padtail[l] > x0 && ix.padtail[l] <= x1) ? 1 : 0;
+        for (int j = 0; j < L; j++) cnt += ((t >> (2 * j)) & 3u) == (uint32_t)b ? 1 : 0;
+        if (cnt >= k) m |= 1u << b;
+    }
+    return m;
+}
+
 // Walk one read with the calling wave, 64 bases per ballot (four loads in flight per lane).  For every position that is
 // not a break the lane holding it calls base(i, k, start) (k = its segment's index in the read, start = the segment's
 // first position); for every segment the lane holding its last base (lane 0 for one that ends at a 64-base boundary)

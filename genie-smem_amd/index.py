@@ -566,6 +566,40 @@ class GenieIndex:
                                               (_ptr(totals), _ptr(ws), ws_bytes))
         return offsets, rows, status, int(totals.item())
 
+    def match_stats_min_occ(self, bases, read_offsets, min_occ, intervals=True, both_strands=False, split_breaks=False):
+        """match_stats of what occurs at least min_occ times in the reference (genie_match_stats_min_occ) -> (ms, lohi,
+        status, shortened).  ms[v] is the length of the longest match from that position whose suffix-array interval has
+        at least min_occ rows, lohi that interval ((-1, -1) where ms is 0), shortened the number of positions where ms is
+        shorter than match_stats's.  A base that occurs fewer than min_occ times is "rare": it flags its strand-read
+        READ_ABSENT_BASE, or is a break with split_breaks.  min_occ = 1 is match_stats."""
+        bases, read_offsets, n_reads, total, max_len, flags, strands = self._csr_call(bases, read_offsets, both_strands, split_breaks)
+        ms = torch.empty(strands * total, dtype=torch.int32, device=self.device)
+        lohi = torch.empty((strands * total, 2), dtype=torch.int32, device=self.device) if intervals else None
+        status = torch.empty(strands * n_reads, dtype=torch.int32, device=self.device)
+        totals = torch.zeros(1, dtype=torch.int64, device=self.device)
+        ws, ws_bytes = self._workspace("genie_match_stats_min_occ_workspace_bytes", n_reads, total, max_len, flags)
+        self._run("genie_match_stats_min_occ", flags, int(min_occ), _ptr(bases), _ptr(read_offsets), n_reads, total, max_len,
+                  _ptr(ms), _ptr(lohi), _ptr(status), _ptr(totals), _ptr(ws), ws_bytes)
+        return ms, lohi, status, int(totals.item())
+
+    def find_smems_min_occ(self, mode, bases, read_offsets, min_occ, min_len=1, rows_hint=None, both_strands=False,
+                           split_breaks=False):
+        """find_smems_long under a minimum occurrence count, BWA-MEM's min_intv (genie_find_smems_min_occ) -> (offsets,
+        smems int32[S, 4], status, shortened).  The rows are the matches of at least min_occ occurrences that no other such
+        match contains: hi - lo + 1 >= min_occ on every row.  Options, row order and status as find_smems_long, rare bases
+        and shortened as match_stats_min_occ.  Re-seeding is a loop over min_occ = occ + 1 of this call that keeps the rows
+        covering the long SMEM's midpoint.  If the rows outnumber rows_hint the call is made again with room for all."""
+        if split_breaks and mode != "bwa":
+            raise ValueError("split_breaks needs mode 'bwa' (genie_find_smems_split has no other traversal)")
+        bases, read_offsets, n_reads, total, max_len, flags, strands = self._csr_call(bases, read_offsets, both_strands, split_breaks)
+        totals = torch.zeros(1, dtype=torch.int64, device=self.device)
+        ws, ws_bytes = self._workspace("genie_find_smems_min_occ_workspace_bytes", n_reads, total, max_len, flags)
+        offsets, rows, status = self._run_csr("genie_find_smems_min_occ", (N.MODES[mode], flags, _ptr(bases), _ptr(read_offsets),
+                                                                           n_reads, total, max_len, int(min_len), int(min_occ)),
+                                              strands * n_reads, int(rows_hint) if rows_hint else strands * max(8 * n_reads, total // 6),
+                                              (_ptr(totals), _ptr(ws), ws_bytes))
+        return offsets, rows, status, int(totals.item())
+
     def locate_contigs(self, contigs, rows):
         """SMEM rows int32 [S, 4] (start, end, lo, hi) of any find_smems* call -> (hit_offsets int64[S+1], hits int32[T, 2]
         = (contig, 1-based offset inside it), dropped) (genie_locate_contigs).  The rows stay SMEMs of the concatenation;

@@ -227,6 +227,24 @@ class SMEM:
         return self.matcher.index(self.lut.lut_size).find_smems_contigs(contigs, mode, bases, read_offsets, minimum_length,
                                                                         both_strands=both_strands, split_breaks=split_breaks)
 
+    def match_stats_min_occ(self, reads, min_occ, intervals=True, both_strands=False, split_breaks=False):
+        """match_stats of what occurs at least min_occ times in the reference (genie_match_stats_min_occ).  reads as
+        match_stats.  -> (ms, lohi, status, shortened): ms the longest match from each position whose interval lohi has at
+        least min_occ rows, shortened the number of positions where that is shorter than match_stats's answer."""
+        bases, read_offsets = self._csr_reads(reads, split_breaks)
+        return self.matcher.index(self.lut.lut_size).match_stats_min_occ(bases, read_offsets, min_occ, intervals, both_strands,
+                                                                         split_breaks)
+
+    def find_smems_min_occ(self, reads, min_occ, minimum_length=1, mode="bwa", both_strands=False, split_breaks=False,
+                           rows_hint=None):
+        """find_smems_long under a minimum occurrence count, BWA-MEM's min_intv (genie_find_smems_min_occ): the matches of
+        at least min_occ occurrences that no other such match contains.  reads and options as find_smems_long.
+        -> (offsets, smems[S, 4], status, shortened)."""
+        bases, read_offsets = self._csr_reads(reads, split_breaks)
+        return self.matcher.index(self.lut.lut_size).find_smems_min_occ(mode, bases, read_offsets, min_occ, minimum_length,
+                                                                        rows_hint=rows_hint, both_strands=both_strands,
+                                                                        split_breaks=split_breaks)
+
     def match_stats_text(self, data, fmt="lines", intervals=True, both_strands=False, split_breaks=True, fold_case=False):
         """match_stats of the reads in a text (find_smems_text's formats and translation) -> (ms, lohi, status,
         read_offsets): read_offsets int64[N+1] on the device, to index the flat arrays with."""

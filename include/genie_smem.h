@@ -653,6 +653,71 @@ int genie_find_smems_contigs(const genie_index *ix, const int64_t *d_contig_offs
                              int64_t *d_totals,       /* 1, may be NULL: positions clipped */
                              void *d_workspace, int64_t workspace_bytes, void *stream);
 
+/* Matching statistics and SMEMs under a MINIMUM OCCURRENCE COUNT: the longest match that occurs at least k = min_occ times in
+ * the reference (BWA-MEM's min_intv).  Every other seeding call answers "the longest match" whatever its number of
+ * occurrences; a read inside one copy of a diverged repeat then gets one seed and never sees the other copies.  Re-seeding is
+ * the caller's loop over this call: a long SMEM of occ occurrences is asked again with k = occ + 1 (k = 2 .. split_width + 1
+ * in BWA-MEM's terms), and the rows that cover the SMEM's midpoint are kept.  No policy is built in; k is one scalar.
+ * Arguments: those of genie_match_stats / genie_find_smems_long_ex with min_occ behind flags / min_len and d_totals behind
+ * d_status.  Reads (CSR, any length), flags, strand-reads, virtual positions v, the offset check and the synchronisations
+ * are the parents'.
+ * Definition.  occ(w) is the number of suffix-array rows whose suffix starts with w (the $ row never counts; hi - lo + 1 of
+ * genie_sa_interval for an occurring w).  ms_k[v] is the largest l >= 0 for which the l bases of the strand-read from p on
+ * hold no break and occur at least k times.  ms_1 = ms.  fwd_k[p] = p + ms_k[p].  Five facts:
+ *   1  ms_k <= ms, and ms_k is non-increasing in k.  ms_k[p] = 0 iff the base at p is a break or occurs fewer than k times in
+ *      the reference: a base RARE AT K ("the reference lacks it" is k = 1).
+ *   2  ms_k[v+1] >= ms_k[v] - 1 inside a strand-read (dropping the first base can only gain occurrences), so fwd_k is
+ *      non-decreasing; "Q[s..e) occurs >= k times" <=> fwd_k[s] >= e, because occ is monotone in the length.  So the BWA
+ *      traversal applied to fwd_k yields exactly the matches of >= k occurrences that no other such match contains: the
+ *      SMEMs under min_intv = k.
+ *   3  Let p0 be a run start of the parent's fwd[].  If the interval of Q[p0 .. fwd[p0]) has >= k rows, ms_k = ms on the
+ *      whole run: every position's match is a suffix of that string.  (The same holds from any position to the run's end.)
+ *   4  Otherwise each position is resolved on its own: occ(Q[p..p+l)) >= k is monotone in l, bisection over [0, ms[p]].
+ *   5  Without a search over l: with [lo, hi] the interval of the full match, hi - lo + 1 < k, and R = n + 1 rows,
+ *      ms_k[p] = max over a in [max(1, hi-k+1), min(lo, R-k)] of min(ms[p], lcp(T[SA[a]..], T[SA[a+k-1]..])), 0 when the
+ *      range is empty.  Equivalently the k-th largest of L_j = min(ms[p], lcp(Q[p..], T[SA[j]..])) over the rows j >= 1,
+ *      which is how the kernel takes it: rows from either side of [lo, hi], the larger L_j first, until k are together.
+ * Status and breaks.  Without GENIE_READS_SPLIT_BREAKS a strand-read that holds a base rare at k is flagged
+ * GENIE_READ_ABSENT_BASE and has no SMEM rows; its statistics are written and correct all the same.  GENIE_READ_BAD_BASE is
+ * the parent's.  With GENIE_READS_SPLIT_BREAKS a base rare at k is a break and every status is GENIE_READ_OK.  The four base
+ * counts are taken from the prefix directory on the device.
+ * genie_match_stats_min_occ writes d_ms[v] = ms_k[v] and, unless d_lohi is NULL, d_lohi[v] = the interval of those ms_k
+ * bases -- at least k rows wherever ms_k > 0, (-1, -1) where ms_k = 0.  Bad-base strand-reads get -1 and (-1, -1).
+ * genie_find_smems_min_occ writes the rows (start, end, lo, hi) the traversal produces from fwd_k, hi - lo + 1 >= k on every
+ * row; mode, min_len, row order, d_offsets, out_cap_rows, the sizing behaviour and the unit passes are the parent's
+ * (GENIE_READS_SPLIT_BREAKS needs GENIE_MODE_BWA).
+ *   d_totals   (1 int64, 8-byte aligned, may be NULL) the number of virtual positions with ms_k < ms
+ *              (genie_find_smems_min_occ: those of the strand-reads that are not flagged), ms taken under the call's own
+ *              breaks: with GENIE_READS_SPLIT_BREAKS a base rare at k ends the match of either.  It stays on the device.
+ * With min_occ == 1 both calls give the outputs of genie_match_stats / genie_find_smems_long_ex byte for byte.  With
+ * GENIE_READS_BOTH_STRANDS they give those of the call without the flag on the explicit interleaved batch.  No atomic
+ * decides a value; nothing outside the declared sizes is written.
+ * Checks, all before the device check: the parent's, in its order; then min_occ < 1 and a misaligned d_totals
+ * (GENIE_E_INVALID); then the workspace (GENIE_E_CAPACITY); then GENIE_E_NO_DEVICE on a host-only handle.
+ * The workspace functions take the parent's arguments, do not depend on k, return GENIE_E_INVALID for what the call refuses,
+ * are multiples of 256, monotone in every argument and at least the parent's value: the parent's plus 4 bytes per window
+ * of 256 positions and per unit and 8 bytes per 256 units.  The parent's part is used at its declared size.
+ * Not offered: a threshold per read or per position, re-seeding itself, min_occ together with a contig table, the padded
+ * and the packed host-link forms. */
+int64_t genie_match_stats_min_occ_workspace_bytes(int64_t N, int64_t total_bases, int64_t max_len, int32_t flags);
+int genie_match_stats_min_occ(const genie_index *ix, int32_t flags, int32_t min_occ, const uint8_t *d_bases,
+                              const int64_t *d_read_offsets, int64_t N, int64_t total_bases, int64_t max_len,
+                              int32_t *d_ms,           /* S * total_bases */
+                              int32_t *d_lohi,         /* 2 * S * total_bases, may be NULL */
+                              int32_t *d_status,       /* S * N, may be NULL */
+                              int64_t *d_totals,       /* 1, may be NULL: positions with ms_k < ms */
+                              void *d_workspace, int64_t workspace_bytes, void *stream);
+int64_t genie_find_smems_min_occ_workspace_bytes(int64_t N, int64_t total_bases, int64_t max_len, int32_t flags);
+int genie_find_smems_min_occ(const genie_index *ix, int32_t mode, int32_t flags, const uint8_t *d_bases,
+                             const int64_t *d_read_offsets, int64_t N, int64_t total_bases, int64_t max_len, int32_t min_len,
+                             int32_t min_occ,
+                             int64_t *d_offsets,      /* S * N + 1 */
+                             int32_t *d_rows,         /* 4 * out_cap_rows, 16-byte aligned */
+                             int64_t out_cap_rows,
+                             int32_t *d_status,       /* S * N, may be NULL */
+                             int64_t *d_totals,       /* 1, may be NULL: positions with ms_k < ms */
+                             void *d_workspace, int64_t workspace_bytes, void *stream);
+
 /* Reads from TEXT, on the device: the bytes of a file of reads -> the d_bases / d_read_offsets that genie_find_smems_long_ex
  * takes.  The reference has no counterpart (its reads are Python strings); this replaces encoding every string on the host.
  * Lines.  A line ends at a '\n' (0x0A), which is not part of it; if the line is then not empty and its last byte is '\r',
