@@ -603,6 +603,39 @@ int genie_locate_contigs(const genie_index *ix, const int64_t *d_contig_offsets,
     return launch_locate_contigs(ix, d_contig_offsets, n_contigs, d_rows, S, d_hit_offsets, d_hits, cap_hits, d_totals, d_tmp, stream);
 }
 
+int64_t genie_chain_mems_workspace_bytes(int64_t U, int64_t total_rows, int64_t n_contigs)
+{
+    if (U < 0 || total_rows < 0 || n_contigs < 0 || n_contigs > 0x7ffffffell) return (int64_t)GENIE_E_INVALID;
+    return chain_mems_workspace_bytes(U, total_rows, n_contigs);
+}
+
+int genie_chain_mems(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs, const int64_t *d_offsets,
+                     const int32_t *d_rows, int64_t U, int64_t total_rows, int32_t max_dist, int32_t bandwidth, int32_t gap_cost,
+                     int32_t max_pred, int32_t min_score, int64_t *d_chain_offsets, int32_t *d_chains, int64_t cap_chains,
+                     int32_t *d_anchor_chain, int32_t *d_anchor_pred, int32_t *d_anchor_score, int64_t *d_totals, void *d_workspace,
+                     int64_t workspace_bytes, void *stream)
+{
+    // argument checks first: they need no device image
+    if (!ix || !d_offsets || !d_chain_offsets || (total_rows > 0 && !d_rows)) return GENIE_E_INVALID;
+    if (U < 0 || total_rows < 0 || cap_chains < 0 || workspace_bytes < 0) return GENIE_E_INVALID;
+    if (max_dist < 1 || max_dist > (1 << 22) || bandwidth < 0 || bandwidth > max_dist || gap_cost < 0 || gap_cost > 255 ||
+        max_pred < 0 || min_score < 0)
+        return GENIE_E_INVALID;
+    if (misaligned(d_offsets, 7) || misaligned(d_rows, 15) || misaligned(d_chain_offsets, 7) || misaligned(d_chains, 15) ||
+        misaligned(d_anchor_chain, 3) || misaligned(d_anchor_pred, 3) || misaligned(d_anchor_score, 3) || misaligned(d_totals, 7))
+        return GENIE_E_INVALID;
+    // the table is optional: null with n_contigs == 0, or a table as every contig call takes it
+    if (!d_contig_offsets && n_contigs != 0) return GENIE_E_INVALID;
+    if (d_contig_offsets)
+        if (int rc = contig_args(d_contig_offsets, n_contigs)) return rc;
+    if (U > 0 && (!d_workspace || misaligned(d_workspace, 255) || workspace_bytes < chain_mems_workspace_bytes(U, total_rows, n_contigs)))
+        return GENIE_E_CAPACITY;
+    if (int rc = ready(ix)) return rc;
+    const ChainBatch b{d_offsets, d_rows, U, total_rows, max_dist, bandwidth, gap_cost, max_pred, min_score};
+    return launch_chain_mems(ix, {d_contig_offsets, n_contigs}, b, {d_chain_offsets, d_chains, cap_chains, d_totals},
+                             {d_anchor_chain, d_anchor_pred, d_anchor_score}, d_workspace, stream);
+}
+
 int genie_contig_coords(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs, const int32_t *d_pos, int32_t stride,
                         int64_t count, int32_t *d_out, void *stream)
 {

@@ -436,6 +436,19 @@ int launch_match_stats_contigs(const genie_index *ix, const ContigTable &ctg, co
 int64_t find_smems_contigs_workspace_bytes(int64_t N, int64_t total_bases, int32_t flags);
 int launch_find_smems_contigs(const genie_index *ix, const ContigTable &ctg, int32_t mode, int32_t min_len, const CsrBatch &b,
                               const CsrRows &out, void *stream);
+// chains.inc: the MEM rows of every unit (strand-read) chained; the contig table may be {null, 0}
+struct ChainBatch {
+    const int64_t *offsets;
+    const int32_t *rows;
+    int64_t U, total_rows;
+    int32_t max_dist, bandwidth, gap_cost, max_pred, min_score;
+};
+struct ChainAnchors {
+    int32_t *chain, *pred, *score;
+};
+int64_t chain_mems_workspace_bytes(int64_t U, int64_t total_rows, int64_t n_contigs);
+int launch_chain_mems(const genie_index *ix, const ContigTable &ctg, const ChainBatch &b, const CsrRows &out, const ChainAnchors &an,
+                      void *d_ws, void *stream);
 // min_occ.inc: matching statistics and SMEMs of what occurs at least min_occ times
 int64_t match_stats_min_occ_workspace_bytes(int64_t N, int64_t total_bases, int32_t flags);
 int launch_match_stats_min_occ(const genie_index *ix, int32_t min_occ, const CsrBatch &b, int32_t *d_ms, int32_t *d_lohi,

@@ -619,6 +619,59 @@ class GenieIndex:
         self._run("genie_locate_contigs", *table, _ptr(rows), S, _ptr(offsets), _ptr(hits), kept, _ptr(totals), _ptr(tmp), tmp_bytes)
         return offsets, hits[:kept], dropped
 
+    def chain_mems(self, offsets, rows, contigs=None, max_dist=5000, bandwidth=500, gap_cost=2, max_pred=5000, min_score=40,
+                   by_score=False):
+        """The MEM rows of find_mems / find_mems_contigs chained per strand-read (genie_chain_mems) -> (chain_offsets
+        int64[U+1], chains int32[C, 8] = (q_begin, q_end, r_begin, r_end, score, n_anchors, contig, last), anchor_chain,
+        anchor_pred, anchor_score int32[R], dropped) on the device.  offsets / rows: the first two results of find_mems*,
+        unchanged; contigs: the ReferenceSet of find_mems_contigs, or None (every anchor in contig 0).  An anchor j may
+        precede i when both lie on one contig, i starts 1 .. max_dist bases later in the read and in the reference, and
+        the two distances differ by at most bandwidth; the link adds min(length of i, the distances) - gap_cost / 16 per
+        base of that difference; max_pred > 0 looks at that many rows back at most.  A chain is kept when it scores at
+        least min_score; `dropped` counts the others.  The chains of a unit come ordered by `last` (the row of the
+        chain's top inside its unit); by_score=True reorders them by (score descending, last ascending) and renumbers
+        anchor_chain.  Anchors behind offsets[U] belong to no unit: -1.  The defaults are this wrapper's; the C call has
+        none."""
+        self._need_device()
+        offsets = self._as_dev(offsets, torch.int64).reshape(-1)
+        rows = self._as_dev(rows, torch.int32)
+        if offsets.numel() < 1:
+            raise ValueError("offsets needs U + 1 entries")
+        if rows.dim() != 2 or rows.shape[1] != 4:
+            raise ValueError("rows must be [R, 4] (start, end, pos, row)")
+        table = (C.c_void_p(0), 0)
+        if contigs is not None:
+            off, table = self._contig_table(contigs)
+        U, R = offsets.numel() - 1, rows.shape[0]
+        prm = (int(max_dist), int(bandwidth), int(gap_cost), int(max_pred), int(min_score))
+        chain_offsets = torch.empty(U + 1, dtype=torch.int64, device=self.device)
+        anchors = [torch.full((R,), -1, dtype=torch.int32, device=self.device) for _ in range(3)]
+        totals = torch.empty(2, dtype=torch.int64, device=self.device)
+        ws, ws_bytes = self._workspace("genie_chain_mems_workspace_bytes", U, R, table[1])
+        none = C.c_void_p(0)
+        head = (*table, _ptr(offsets), _ptr(rows) if R else none, U, R, *prm, _ptr(chain_offsets))
+        tail = (*[_ptr(t) if R else none for t in anchors], _ptr(totals), _ptr(ws), ws_bytes)
+        self._run("genie_chain_mems", *head, none, 0, none, none, none, *tail[3:])      # the sizing call
+        kept, dropped = (int(x) for x in totals.tolist())
+        chains = torch.empty((max(kept, 1), 8), dtype=torch.int32, device=self.device)
+        self._run("genie_chain_mems", *head, _ptr(chains), kept, *tail)
+        chains = chains[:kept]
+        if by_score and kept:
+            units = torch.arange(U, device=self.device)
+            unit = torch.repeat_interleave(units, chain_offsets[1:] - chain_offsets[:-1])
+            # stable sorts, least significant key first: last ascending, score descending, unit ascending
+            order = torch.argsort(chains[:, 7], stable=True)
+            order = order[torch.argsort(-chains[order, 4].long(), stable=True)]
+            order = order[torch.argsort(unit[order], stable=True)]
+            rank = torch.empty(kept, dtype=torch.int64, device=self.device)
+            rank[order] = torch.arange(kept, device=self.device) - chain_offsets[unit[order]]
+            a_unit = torch.repeat_interleave(units, offsets[1:] - offsets[:-1])
+            ac = anchors[0][:a_unit.numel()]
+            has = ac >= 0
+            ac[has] = rank[chain_offsets[a_unit[has]] + ac[has].long()].to(torch.int32)
+            chains = chains[order]
+        return chain_offsets, chains, anchors[0], anchors[1], anchors[2], dropped
+
     def contig_coords(self, contigs, pos, stride=1):
         """1-based concatenation positions -> int32 [count, 2] = (contig, 1-based offset inside it) on the device
         (genie_contig_coords); (-1, -1) for a position outside [1, n].  pos: int32, flat; with stride > 1 every stride-th

@@ -194,6 +194,23 @@ class SMEM:
             bases = np.concatenate(enc).astype(np.uint8) if enc else np.zeros(0, np.uint8)
         return ix.find_mems_contigs(contigs, bases, read_offsets, minimum_length, both_strands, split_breaks, max_occ)
 
+    def chain_mems(self, offsets, rows, contigs=None, **chain_options):
+        """The rows of find_mems / find_mems_contigs chained per strand-read (genie_chain_mems) -> (chain_offsets, chains
+        int32[C, 8] = (q_begin, q_end, r_begin, r_end, score, n_anchors, contig, last), anchor_chain, anchor_pred,
+        anchor_score, dropped): GenieIndex.chain_mems, which documents the options (max_dist, bandwidth, gap_cost, max_pred,
+        min_score, by_score) and their defaults."""
+        return self.matcher.index(self.lut.lut_size).chain_mems(offsets, rows, contigs, **chain_options)
+
+    def find_chains(self, reads, minimum_length, contigs=None, both_strands=False, split_breaks=False, max_occ=0, **chain_options):
+        """find_mems (find_mems_contigs with a ReferenceSet) followed by chain_mems on its rows -> (mems, chains): the two
+        calls' results as they return them.  Candidate mapping locations of every strand-read: chains[:, 2:4] in the
+        concatenation's 1-based coordinates, chains[:, 6] the contig, the strand the unit's parity with both_strands."""
+        if contigs is None:
+            mems = self.find_mems(reads, minimum_length, both_strands, split_breaks, max_occ)
+        else:
+            mems = self.find_mems_contigs(contigs, reads, minimum_length, both_strands, split_breaks, max_occ)
+        return mems, self.chain_mems(mems[0], mems[1], contigs, **chain_options)
+
     def locate_contigs(self, contigs, rows):
         """SMEM rows (start, end, lo, hi) of any find_smems* call -> (hit_offsets, hits int32[T, 2] = (contig, 1-based
         offset), dropped): GenieIndex.locate_contigs.  The rows stay SMEMs of the concatenation; occurrences that bridge two

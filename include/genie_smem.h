@@ -581,6 +581,70 @@ int genie_locate_contigs(const genie_index *ix, const int64_t *d_contig_offsets,
 int genie_contig_coords(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs, const int32_t *d_pos,
                         int32_t stride, int64_t count, int32_t *d_out /* 2 * count */, void *stream);
 
+/* Chain the MEM rows of every strand-read into collinear chains: candidate mapping locations with contig, strand (the unit)
+ * and score, where genie_find_mems* stop.  The call consumes the rows exactly as those calls write them, ordered by (start, row)
+ * within a strand-read: query order is a topological order of the recurrence, so nothing is sorted.  Everything is integer
+ * and deterministic: the outputs are a function of the inputs alone.
+ * Units.  A unit is one strand-read: the rows d_rows[4 off[u] .. 4 off[u+1]) of d_offsets[U + 1], as genie_find_mems* write
+ * them.  Anchor i of a unit is the row (s_i, e_i, pos_i, row_i): l_i = e_i - s_i >= 1, t_i = pos_i - 1 with 0 <= t_i < n, s
+ * non-decreasing in i; column 3 (row) is never read.  With a contig table (as genie_contigs_validate takes it) c_i is the
+ * contig of t_i by that comment's rule; with d_contig_offsets == NULL and n_contigs == 0 every c_i is 0.  Rows that break
+ * these assumptions give undefined values, but no load or store outside the declared sizes and no unbounded loop.
+ * Parameters (int32): max_dist in [1, 2^22]; bandwidth in [0, max_dist]; gap_cost in [0, 255], in sixteenths of a base;
+ * max_pred >= 0, 0 = no limit; min_score >= 0.  The call has no defaults.
+ * Link.  j may precede i iff j < i; j >= i - max_pred when max_pred > 0; c_j == c_i; dq = s_i - s_j and dr = t_i - t_j both in
+ * [1, max_dist]; g = |dr - dq| <= bandwidth; gain(j, i) = min(l_i, dq, dr) - ((g * gap_cost) >> 4) >= 1.
+ * Recurrence.  f(i) = max(l_i, max over linkable j of f(j) + gain(j, i)); p(i) is the largest j that attains that maximum
+ * if the maximum is strictly greater than l_i, else -1.  f rises strictly along every link.
+ * Chains.  The p links form a forest.  top(i) is the node of i's subtree, i included, with the largest (f, then smallest
+ * index); one chain is the set of anchors with the same top: a path that ends in a leaf, and every leaf is the top of exactly
+ * one chain.  (minimap2's extraction: visit anchors by (f descending, index ascending), backtrack until a used anchor.)
+ * Score.  With v the chain's top and u its first anchor: f(v) - f(p(u)) if p(u) >= 0, else f(v).  A chain is kept iff its
+ * score >= min_score.
+ * Outputs, all in caller buffers:
+ *   d_chain_offsets  U + 1 int64, 8-byte aligned: the offsets of each unit's kept chains; [U] is the true total even when
+ *                    cap_chains is smaller
+ *   d_chains         8 int32 per chain, 16-byte aligned, may be NULL (the sizing call): (q_begin, q_end, r_begin, r_end, score,
+ *                    n_anchors, contig, last) with q_begin = s_u, r_begin = pos_u (1-based in the concatenation), q_end the
+ *                    largest e and r_end the largest pos + l over the members, last = v's row index inside its unit.  The
+ *                    chains of a unit are ordered by last ascending; chains past cap_chains are dropped.
+ *   d_anchor_chain   total_rows int32, may be NULL: the index of the anchor's chain inside its unit (whether or not that chain
+ *                    fits cap_chains), -1 if that chain was not kept
+ *   d_anchor_pred    total_rows int32, may be NULL: p(i) inside the unit
+ *   d_anchor_score   total_rows int32, may be NULL: f(i)
+ *   d_totals         2 int64, 8-byte aligned, may be NULL: {chains kept, chains not kept}
+ * Anchors at or past off[U] are left untouched.  No atomic decides a value.
+ * total_rows is the host-side bound: the size of d_rows and of the anchor arrays.  The device checks off[0] == 0, off
+ * non-decreasing, off[U] <= total_rows and no unit above 2^31 - 1 rows: GENIE_E_INVALID, found on the device, at the cost of
+ * the call's only synchronisation of `stream`.
+ * Checked before that and before the device check, so on any handle, GENIE_E_INVALID: a null ix, d_offsets or
+ * d_chain_offsets; a null d_rows with total_rows > 0; a negative size; a parameter outside its range; d_rows or d_chains not
+ * 16-byte, d_offsets, d_chain_offsets, d_totals or the table not 8-byte, an anchor array not 4-byte aligned; a table with
+ * n_contigs < 1 or a null table with n_contigs != 0 (GENIE_E_TOO_LONG for n_contigs above 2^31 - 2).  Then, for U > 0, a
+ * d_workspace that is null, not 256-byte aligned or smaller than genie_chain_mems_workspace_bytes(U, total_rows, n_contigs)
+ * gives GENIE_E_CAPACITY.  U == 0 writes d_chain_offsets[0] = 0 and zero totals.
+ * The workspace function returns GENIE_E_INVALID for negative arguments, is a multiple of 256 and monotone in U and
+ * total_rows: 24 bytes per row (f 4, p 4, top 4, kept flag 4, the key handed up between chunks 8), 28 with more than one
+ * contig (the anchor's contig), 8 bytes per unit (chains kept, chains in all) and 8 per 1024 units (the scan).
+ * Kernels: one wave per unit, the unit's last kChainTile = 512 anchors as (s, t, c, f) in an LDS ring, 64 lanes over the
+ * window's candidates and a wave max-reduce per anchor; older candidates come from the workspace.  Cost: per anchor its
+ * window's candidates / 64 steps, so max_pred bounds the work on repeat-rich rows; a unit is not split, so one unit of very
+ * many rows runs on one wave. */
+int64_t genie_chain_mems_workspace_bytes(int64_t U, int64_t total_rows, int64_t n_contigs);
+int genie_chain_mems(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs,
+                     const int64_t *d_offsets,        /* U + 1 */
+                     const int32_t *d_rows,           /* 4 * total_rows, 16-byte aligned */
+                     int64_t U, int64_t total_rows,
+                     int32_t max_dist, int32_t bandwidth, int32_t gap_cost, int32_t max_pred, int32_t min_score,
+                     int64_t *d_chain_offsets,        /* U + 1 */
+                     int32_t *d_chains,               /* 8 * cap_chains, 16-byte aligned; may be NULL: sizing only */
+                     int64_t cap_chains,
+                     int32_t *d_anchor_chain,         /* total_rows, may be NULL */
+                     int32_t *d_anchor_pred,          /* total_rows, may be NULL */
+                     int32_t *d_anchor_score,         /* total_rows, may be NULL */
+                     int64_t *d_totals,               /* 2, may be NULL: {chains kept, chains not kept} */
+                     void *d_workspace, int64_t workspace_bytes, void *stream);
+
 /* Matching statistics and SMEMs that are EXACT WITH RESPECT TO THE SEQUENCE SET.  genie_match_stats and the SMEM calls on a
  * reference of several sequences answer for the concatenation; genie_locate_contigs then drops the occurrences that bridge
  * two sequences, and with them seeds.  Contigs ACGT | TTGA and the read CGTT: the concatenation holds CGTT once, across the
