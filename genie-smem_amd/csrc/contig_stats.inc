@@ -1,5 +1,5 @@
 // contig_stats.inc -- genie_match_stats_contigs and genie_find_smems_contigs: matching statistics and SMEMs that are exact
-// with respect to a reference of several sequences (included by kernels.hip behind contigs.inc, inside namespace genie).
+// with respect to a reference of several sequences (included by kernels.hip behind fwd_step.inc, inside namespace genie).
 //
 // ms_c[v], the contig-exact matching statistic of a virtual position (long_units.inc), is the largest l for which the l
 // bases from there on hold no break and equal T[t .. t+l) for some t with l <= room(t) (contigs.inc): they occur inside ONE
@@ -37,9 +37,12 @@
 //   then, SMEMs:             CS3 cs_marks_kernel, one wave per window: what LR2's SMEM instance writes beside fwd[] (the
 //                            first maximum of fwd[a] - a, the mark at fwd[a]) from the corrected fwd[]; LR3, LR4,
 //                            launch_compact and LR5 as in lr_pipeline.
+// What every call with a step shares is in fwd_step.inc: the window's front (fs_window), the intervals of the tested
+// positions (fs_intervals), the block totals, cs_totals_kernel, cs_marks_kernel, the sizing (fs_bytes) and the launch
+// (fs_match_stats / fs_find_smems).  Here: the area, cs_room, cs_walk, CS1, CS2 and cs_correct, which launches them.
 // Workspace: the parent's, then the slots (8 bytes per virtual position), the window and block counts and CS2's clip counts.  The
 // parent's part is handed to lu_run at exactly its declared size, so that the units of a pass, and with them the windows,
-// never exceed what the counts were sized for (cs_units_cap).
+// never exceed what the counts were sized for (fs_units_cap).
 // Memory safety on any table contents is ctg_find's; rows come from the index, positions from fwd[], which LR2 bounds.
 namespace {
 
@@ -115,16 +118,8 @@ __device__ __forceinline__ int cs_walk(const DevIndex &ix, const CtgTab &g, cons
     return best;
 }
 
-// rows of an inclusive interval that are followed: none for (-1, -1), none beyond the suffix array
-__device__ __forceinline__ int cs_rows(const DevIndex &ix, int2 iv)
-{
-    const int hi = iv.y < ix.n ? iv.y : ix.n;
-    return iv.x >= 0 && hi >= iv.x ? hi - iv.x + 1 : 0;
-}
-
 // CS1.  One wave per window, kLrFwdWaves windows per block (lr_fwd_kernel's shape: four positions per lane, no barrier between
-// the staging of the table and the block's count).  skip_flagged: the SMEM tail, where a unit with any status has no rows
-// (and, in LUT / RMI mode, no fwd[]); the match statistics want every unit but those with a bad base.
+// the staging of the table and the block's count).  The window, skip_flagged and the intervals of the run starts: fwd_step.inc.
 template <bool C16, bool SLICED = false>
 __global__ void __launch_bounds__(kLrFwdWaves * 64) cs_start_kernel(DevIndex ix, CtgTab cg, int skip_flagged, const long long *__restrict__ off,
                                                                     long long N, long long nwin, const uint64_t *__restrict__ packed,
@@ -142,60 +137,30 @@ __global__ void __launch_bounds__(kLrFwdWaves * 64) cs_start_kernel(DevIndex ix,
     const long long blk = SLICED ? block0 + blockIdx.x : (long long)blockIdx.x;
     const long long gw = blk * kLrFwdWaves + wave;
     ctg_stage(cg, ix.n, ctg_lds);
-    bool live = gw < nwin;                                       // wave-uniform, as everything that decides a branch below
-    long long r = 0, w = 0, o = 0, Ll = 0;
-    if (live) {
-        r = lr_find(N, gw, [&](long long x) { return lr_wb(off, x); });
-        w = gw - lr_wb(off, r);
-        o = off[r];
-        Ll = off[r + 1] - o;
-        live = w >= 0 && w * kLrWin < Ll;
-    }
-    if (live) {
-        const int32_t status = st[r];
-        live = skip_flagged ? status == GENIE_READ_OK : status != GENIE_READ_BAD_BASE;
-    }
+    const FsWin win = fs_window(off, N, gw, st, skip_flagged, gw < nwin);     // wave-uniform; no wave leaves before the barrier
     int nflag = 0;
-    if (live) {
-        const int L = (int)Ll, w0 = (int)(w * kLrWin);
-        const int nw = L - w0 < kLrWin ? L - w0 : kLrWin;
-        const QPlain Q{packed + lr_wd(off, r)};
-        uint16_t *sl = lists[wave];
-        int2 *sv = sivs[wave];
+    if (win.live) {
+        const long long o = win.o;
+        const int L = win.L, w0 = win.w0;
+        const QPlain Q{packed + lr_wd(off, win.r)};
         const unsigned long long below = (1ull << lane) - 1ull;
         int2 iv[kPer];
         int len[kPer], fv[kPer];
-        bool gen[kPer];
-        int ngen = 0;
+        bool start[kPer];
 #pragma unroll
-        for (int k = 0; k < kPer; k++) {
+        for (int k = 0; k < kPer; k++) {                         // the run starts that have a match
             const int t = k * kWave + lane, a = w0 + t;
-            const bool in = t < nw;
+            const bool in = t < win.nw;
             fv[k] = in ? fwd[o + a] : 0;
-            const bool start = in && (a == 0 || fwd[o + a - 1] != fv[k]);
-            len[k] = start ? fv[k] - a : 0;
-            const bool act = len[k] > 0;
-            const uint64_t x = act ? Q.win(a) : 0ull;
-            const bool fast = interval_from_window<C16>(ix, x, len[k], act, iv[k]);
-            gen[k] = act && !fast;
-            const unsigned long long gb = __ballot(gen[k]);
-            if (gen[k]) sl[ngen + __popcll(gb & below)] = (uint16_t)t;
-            ngen += __popcll(gb);
+            len[k] = in && (a == 0 || fwd[o + a - 1] != fv[k]) ? fv[k] - a : 0;
+            start[k] = len[k] > 0;
         }
-        wave_lds_fence();
-        for (int c0 = 0; c0 < ngen; c0 += kWave) {               // the general search on full waves
-            if (c0 + lane < ngen) {
-                const int g = sl[c0 + lane], ga = w0 + g;
-                sv[g] = sa_interval(ix, ix.dir, Q, ga, fwd[o + ga] - ga);
-            }
-        }
-        wave_lds_fence();
+        fs_intervals<C16>(ix, Q, fwd, win, lane, start, len, lists[wave], sivs[wave], iv);
 #pragma unroll
         for (int k = 0; k < kPer; k++) {
             const int t = k * kWave + lane, a = w0 + t;
-            const bool act = len[k] > 0;
-            if (gen[k]) iv[k] = sv[t];
-            const int best = cs_walk(ix, cg, ctg_lds, iv[k].x, act ? cs_rows(ix, iv[k]) : 0, len[k], lane);
+            const bool act = start[k];
+            const int best = cs_walk(ix, cg, ctg_lds, iv[k].x, act ? fs_rows(ix, iv[k]) : 0, len[k], lane);
             const bool flagged = act && best < len[k];
             int p1 = a + 1;
             if (flagged) {                                       // the run's end: the first position behind a whose fwd differs
@@ -232,7 +197,6 @@ __global__ void __launch_bounds__(256) cs_slow_kernel(DevIndex ix, CtgTab cg, co
                                                       const unsigned long long *__restrict__ bsum, unsigned long long *__restrict__ clip)
 {
     extern __shared__ int ctg_lds[];
-    __shared__ unsigned long long wclip[256 / kWave];
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
     const long long nblk = (nwin + kLrFwdWaves - 1) / kLrFwdWaves;
     const long long items = (long long)bsum[nblk];
@@ -246,11 +210,10 @@ __global__ void __launch_bounds__(256) cs_slow_kernel(DevIndex ix, CtgTab cg, co
         const long long blk = lr_find(nblk, j, [&](long long x) { return (long long)bsum[x]; });
         long long k = j - (long long)bsum[blk], gw = blk * kLrFwdWaves;
         for (int i = 0; i < kLrFwdWaves - 1 && gw + 1 < nwin && k >= wcnt[gw]; i++) k -= wcnt[gw++];      // the window inside its block
-        const long long r = lr_find(N, gw, [&](long long x) { return lr_wb(off, x); });
-        const long long w = gw - lr_wb(off, r);
-        const long long o = off[r], Ll = off[r + 1] - o;
-        if (w < 0 || w * kLrWin >= Ll || k < 0 || k >= kLrWin) continue;     // cannot happen: CS1 counted this window
-        const int L = (int)Ll, w0 = (int)(w * kLrWin);
+        const FsWin win = fs_window(off, N, gw);
+        if (!win.live || k < 0 || k >= kLrWin) continue;         // cannot happen: CS1 counted this window
+        const long long r = win.r, o = win.o;
+        const int L = win.L, w0 = win.w0;
         const uint2 sl = slot[o + w0 + k];
         const int p0 = w0 + (int)(sl.y >> 24), room0 = (int)(sl.y & kCsRoomCap);
         const int p1 = (int)sl.x < L ? (int)sl.x : L;
@@ -278,7 +241,7 @@ __global__ void __launch_bounds__(256) cs_slow_kernel(DevIndex ix, CtgTab cg, co
                 first = false;
                 int2 iv = make_int2(-1, -1);
                 if (open) iv = sa_interval(ix, ix.dir, Q, p, mid);
-                const int best = cs_walk(ix, cg, ctg_lds, iv.x, open ? cs_rows(ix, iv) : 0, mid, lane);
+                const int best = cs_walk(ix, cg, ctg_lds, iv.x, open ? fs_rows(ix, iv) : 0, mid, lane);
                 if (open) {
                     if (best >= mid) {
                         lo = mid;
@@ -296,74 +259,15 @@ __global__ void __launch_bounds__(256) cs_slow_kernel(DevIndex ix, CtgTab cg, co
             }
         }
     }
-    nclip = wave_sum64(nclip);
-    if (lane == 0) wclip[wave] = nclip;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long all = 0;
-        for (int k = 0; k < 256 / kWave; k++) all += wclip[k];
-        clip[blockIdx.x] = all;
-    }
-}
-
-// d_totals[0] += the blocks' clipped positions (one block; the passes of a call follow each other on the stream)
-__global__ void __launch_bounds__(256) cs_totals_kernel(const unsigned long long *__restrict__ clip, int blocks,
-                                                        long long *__restrict__ totals)
-{
-    __shared__ unsigned long long wsum[256 / kWave];
-    unsigned long long d = 0;
-    for (int b = threadIdx.x; b < blocks; b += 256) d += clip[b];
-    d = wave_sum64(d);
-    if ((threadIdx.x & (kWave - 1)) == 0) wsum[threadIdx.x / kWave] = d;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long all = 0;
-        for (int k = 0; k < 256 / kWave; k++) all += wsum[k];
-        totals[0] += (long long)all;
-    }
-}
-
-// CS3: the window maxima and the marks of LR2's SMEM instance, from fwd[] as it stands
-template <bool SLICED>
-__global__ void __launch_bounds__(kLrFwdWaves * 64) cs_marks_kernel(const long long *__restrict__ off, long long N, long long nwin,
-                                                                    const int32_t *__restrict__ st, const int32_t *__restrict__ fwd,
-                                                                    int2 *__restrict__ wmax, uint8_t *__restrict__ mark,
-                                                                    long long block0)
-{
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wave = rfl((int)(threadIdx.x >> 6));
-    const long long gw = (SLICED ? block0 + blockIdx.x : (long long)blockIdx.x) * kLrFwdWaves + wave;
-    if (gw >= nwin) return;                                      // wave-uniform; no block-wide barrier below
-    const long long r = lr_find(N, gw, [&](long long x) { return lr_wb(off, x); });
-    const long long w = gw - lr_wb(off, r);
-    const long long o = off[r], Ll = off[r + 1] - o;
-    if (w < 0 || w * kLrWin >= Ll || st[r] != GENIE_READ_OK) return;
-    const int L = (int)Ll, w0 = (int)(w * kLrWin);
-    const int nw = L - w0 < kLrWin ? L - w0 : kLrWin;
-    unsigned long long best = 0;                                 // (fwd[a] - a) << 8 | 255 - (a - w0): the first maximum
-#pragma unroll
-    for (int k = 0; k < kLrWin / kWave; k++) {
-        const int t = k * kWave + lane, a = w0 + t;
-        if (t < nw) {
-            const int v = fwd[o + a];
-            const unsigned long long key = ((unsigned long long)(uint32_t)(v - a) << kLrWinShift) | (unsigned)(kLrWin - 1 - t);
-            best = key > best ? key : best;
-            if (v >= 0 && v < L) mark[o + v] = 1;                // every writer stores the same value
-        }
-    }
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) {
-        const unsigned long long x = lr_shfl_xor64(best, m);
-        best = x > best ? x : best;
-    }
-    if (lane == 0) wmax[gw] = make_int2((int)(best >> kLrWinShift), w0 + kLrWin - 1 - (int)(best & (kLrWin - 1)));
+    const unsigned long long all = fs_block_total(nclip);
+    if (threadIdx.x == 0) clip[blockIdx.x] = all;
 }
 
 // CS1, the scan, CS2 and the total over the units of `uoff`, whose fwd[] LR2 has written
 int cs_correct(const genie_index *ix, const CsCall &cs, bool skip_flagged, const LongArea &a, const long long *uoff, long long U,
                hipStream_t s)
 {
-    if (a.nwin > cs.a.nwin_cap) return GENIE_E_CAPACITY;         // cannot happen: cs_units_cap
+    if (a.nwin > cs.a.nwin_cap) return GENIE_E_CAPACITY;         // cannot happen: fs_units_cap
     const size_t lds = ctg_lds_bytes(cs.g);
     const bool c16 = (ix->dev.flags & kFlagCompactTable) != 0;
     const long long nblk = (a.nwin + kLrFwdWaves - 1) / kLrFwdWaves;
@@ -377,81 +281,31 @@ int cs_correct(const genie_index *ix, const CsCall &cs, bool skip_flagged, const
     LAUNCH(cs_slow_kernel, dim3(blocks), dim3(256), lds, s, ix->dev, cs.g, uoff, U, a.nwin, static_cast<const uint64_t *>(a.packed),
            a.fwd, static_cast<const uint2 *>(cs.a.slot), static_cast<const int32_t *>(cs.a.wcnt),
            static_cast<const unsigned long long *>(cs.a.bsum), cs.a.clip);
-    if (cs.totals)
-        LAUNCH(cs_totals_kernel, dim3(1), dim3(256), 0, s, static_cast<const unsigned long long *>(cs.a.clip), blocks, cs.totals);
-    return GENIE_OK;
-}
-
-// CS3 over the units of `uoff`: LR3 finds in a.wmax and a.mark what LR2's SMEM instance would have left there
-int cs_marks(const LongArea &a, const long long *uoff, long long U, hipStream_t s)
-{
-    LAUNCH_SLICED(cs_marks_kernel<false>, cs_marks_kernel<true>, (a.nwin + kLrFwdWaves - 1) / kLrFwdWaves, kLrFwdWaves * 64, 0, s, uoff, U,
-                  a.nwin, static_cast<const int32_t *>(a.st), static_cast<const int32_t *>(a.fwd), a.wmax, a.mark);
-    return GENIE_OK;
-}
-
-// The most units a pass of lu_run takes when the parent's part of the workspace has exactly its declared size: the
-// strand-reads without SPLIT_BREAKS, else what long_ex_pass_units, which lu_run asks too, finds for any number of units
-// (the padding of the pieces can admit a few more than long_ex_units)
-inline int64_t cs_units_cap(int64_t N, int64_t total, int32_t flags, bool smems)
-{
-    const int S = (flags & GENIE_READS_BOTH_STRANDS) ? 2 : 1;
-    const bool split = (flags & GENIE_READS_SPLIT_BREAKS) != 0;
-    const int64_t SN = std::max<int64_t>(1, (int64_t)S * N);
-    if (!split) return SN;
-    LongExFixed f;
-    const int64_t avail = long_ex_bytes(N, total, flags, smems) - long_ex_fixed_layout(nullptr, N, total, S, split, &f);
-    return long_ex_pass_units(SN, SN + (int64_t)S * total + 1, total, S, avail, smems, true);
-}
-
-inline int64_t cs_bytes(int64_t N, int64_t total, int32_t flags, bool smems, uint8_t *base, CsArea *a)
-{
-    const int S = (flags & GENIE_READS_BOTH_STRANDS) ? 2 : 1;
-    const int64_t parent = long_ex_bytes(N, total, flags, smems);
-    return parent + cs_layout(base ? base + parent : nullptr, (int64_t)S * total, cs_units_cap(N, total, flags, smems), a);
+    return cs.totals ? fs_totals(cs.a.clip, blocks, cs.totals, s) : GENIE_OK;
 }
 
 }  // namespace
 
 int64_t match_stats_contigs_workspace_bytes(int64_t N, int64_t total_bases, int32_t flags)
 {
-    CsArea a;
-    return cs_bytes(N, total_bases, flags, false, nullptr, &a);
+    return fs_bytes(N, total_bases, flags, false, cs_layout);
 }
 
-// Both calls are their parents with the step set, on the parent's part of the workspace at exactly its declared size
 int launch_match_stats_contigs(const genie_index *ix, const ContigTable &ctg, const CsrBatch &b, int32_t *d_ms, int32_t *d_lohi,
                                int64_t *d_totals, void *stream)
 {
-    hipStream_t s = (hipStream_t)stream;
-    if (d_totals) HIP_TRY(hipMemsetAsync(d_totals, 0, 8, s));
     CsCall cs{ctg_tab(ctg.offsets, ctg.n_contigs), {}, reinterpret_cast<long long *>(d_totals)};
-    if (b.N > 0) cs_bytes(b.N, b.total_bases, b.flags, false, static_cast<uint8_t *>(b.ws), &cs.a);
-    CsrBatch parent = b;
-    parent.ws_bytes = long_ex_bytes(b.N, b.total_bases, b.flags, false);
-    LuMsTail tail{ix, parent, d_ms, d_lohi, s,
-                  [&](const LongArea &a, const long long *uoff, long long U) { return cs_correct(ix, cs, false, a, uoff, U, s); }};
-    return lu_run(ix, GENIE_MODE_BWA, parent, s, tail);
+    return fs_match_stats(ix, 1, b, d_ms, d_lohi, cs, cs_layout, cs_correct, (hipStream_t)stream);
 }
 
 int64_t find_smems_contigs_workspace_bytes(int64_t N, int64_t total_bases, int32_t flags)
 {
-    CsArea a;
-    return cs_bytes(N, total_bases, flags, true, nullptr, &a);
+    return fs_bytes(N, total_bases, flags, true, cs_layout);
 }
 
 int launch_find_smems_contigs(const genie_index *ix, const ContigTable &ctg, int32_t mode, int32_t min_len, const CsrBatch &b,
                               const CsrRows &out, void *stream)
 {
-    hipStream_t s = (hipStream_t)stream;
-    if (out.totals) HIP_TRY(hipMemsetAsync(out.totals, 0, 8, s));
     CsCall cs{ctg_tab(ctg.offsets, ctg.n_contigs), {}, reinterpret_cast<long long *>(out.totals)};
-    if (b.N > 0) cs_bytes(b.N, b.total_bases, b.flags, true, static_cast<uint8_t *>(b.ws), &cs.a);
-    CsrBatch parent = b;
-    parent.ws_bytes = long_ex_bytes(b.N, b.total_bases, b.flags, true);
-    LuSmemTail tail{ix, mode, min_len, parent, out, s, [&](const LongArea &a, const long long *uoff, long long U) {
-                        const int rc = cs_correct(ix, cs, true, a, uoff, U, s);
-                        return rc ? rc : cs_marks(a, uoff, U, s);
-                    }};
-    return lu_run(ix, mode, parent, s, tail);
+    return fs_find_smems(ix, mode, min_len, 1, b, out, cs, cs_layout, cs_correct, (hipStream_t)stream);
 }

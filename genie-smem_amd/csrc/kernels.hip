@@ -1425,6 +1425,7 @@ int launch_locate(const genie_index *ix, const int32_t *d_lohi, int32_t stride, 
 #include "long_units.inc"
 #include "exact_match.inc"
 #include "contigs.inc"
+#include "fwd_step.inc"
 #include "contig_stats.inc"
 #include "min_occ.inc"
 #include "mems.inc"

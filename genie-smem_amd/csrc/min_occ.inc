@@ -33,7 +33,9 @@
 //                            one word per block; cs_totals_kernel adds them to d_totals[0].  A position counts when ms_k is
 //                            shorter than fwd[] of ITS UNIT says: with SPLIT_BREAKS a rare base is a break for both.
 //   then lr_ms_kernel as it is, or cs_marks_kernel and LR3 .. LR5, over the corrected fwd[].
-// Workspace: the parent's at exactly its declared size (cs_units_cap), then the window words and MO2's block counts.
+// The window's front, the intervals of the tested positions, the block totals, cs_totals_kernel, cs_marks_kernel, the sizing
+// and the launch are the ones every call with a step uses: fwd_step.inc.
+// Workspace: the parent's at exactly its declared size (fs_units_cap), then the window words and MO2's block counts.
 // Memory safety: rows are clamped to [1, n], reference positions to [0, n); positions come from fwd[], which LR2 bounds.
 namespace {
 
@@ -82,7 +84,7 @@ __device__ __forceinline__ int mo_lcp(const DevIndex &ix, int s0, uint64_t w0, i
 template <class Q>
 __device__ __forceinline__ int mo_resolve(const DevIndex &ix, const Q qp, int a, int ms, int2 iv, int k)
 {
-    const int c = cs_rows(ix, iv);
+    const int c = fs_rows(ix, iv);
     if (k <= kMoMerge && c > 0) {                                // fact 5: the k-th largest L_j
         const int s0 = ix.sa[iv.x].s;
         if (s0 < 0 || s0 >= ix.n) return 0;
@@ -108,13 +110,12 @@ __device__ __forceinline__ int mo_resolve(const DevIndex &ix, const Q qp, int a,
     int lo = 0, hi = ms;                                         // fact 4: hi fails, lo holds or is the floor
     while (hi - lo > 1) {
         const int mid = lo + ((hi - lo) >> 1);
-        if (cs_rows(ix, sa_interval(ix, ix.dir, qp, a, mid)) >= k) lo = mid; else hi = mid;
+        if (fs_rows(ix, sa_interval(ix, ix.dir, qp, a, mid)) >= k) lo = mid; else hi = mid;
     }
     return lo;
 }
 
-// MO1.  skip_flagged: the SMEM tail, where a unit with any status has no rows; the match statistics want every unit but
-// those with a bad base.
+// MO1.  The window, skip_flagged and the intervals of the tested positions: fwd_step.inc.
 template <bool C16, bool SLICED = false>
 __global__ void __launch_bounds__(kLrFwdWaves * 64) mo_resolve_kernel(DevIndex ix, int kocc, int skip_flagged, const long long *__restrict__ off,
                                                                       long long N, long long nwin, const uint64_t *__restrict__ packed,
@@ -130,54 +131,29 @@ __global__ void __launch_bounds__(kLrFwdWaves * 64) mo_resolve_kernel(DevIndex i
     const long long blk = SLICED ? block0 + blockIdx.x : (long long)blockIdx.x;
     const long long gw = blk * kLrFwdWaves + wave;
     if (gw >= nwin) return;                                      // wave-uniform; no block-wide barrier below
-    bool live = true;
-    const long long r = lr_find(N, gw, [&](long long x) { return lr_wb(off, x); });
-    const long long w = gw - lr_wb(off, r);
-    const long long o = off[r], Ll = off[r + 1] - o;
-    live = w >= 0 && w * kLrWin < Ll;
-    if (live) {
-        const int32_t status = st[r];
-        live = skip_flagged ? status == GENIE_READ_OK : status != GENIE_READ_BAD_BASE;
-    }
+    const FsWin win = fs_window(off, N, gw, st, skip_flagged);
     int nclip = 0;
     bool rare = false;
-    if (live) {
-        const int L = (int)Ll, w0 = (int)(w * kLrWin);
-        const int nw = L - w0 < kLrWin ? L - w0 : kLrWin;
-        const QPlain Q{packed + lr_wd(off, r)};
+    if (win.live) {
+        const long long o = win.o;
+        const int w0 = win.w0;
+        const QPlain Q{packed + lr_wd(off, win.r)};
         uint16_t *sl = lists[wave];
         int2 *sv = sivs[wave];
         int32_t *sn = slen[wave];
         const unsigned long long below = (1ull << lane) - 1ull, upto = below | (1ull << lane);
         int2 iv[kPer];
         int len[kPer];
-        bool gen[kPer], tested[kPer];
-        int ngen = 0;
+        bool tested[kPer];
 #pragma unroll
-        for (int k = 0; k < kPer; k++) {
+        for (int k = 0; k < kPer; k++) {                         // the run starts and the window's first position
             const int t = k * kWave + lane, a = w0 + t;
-            const bool in = t < nw;
+            const bool in = t < win.nw;
             const int fv = in ? fwd[o + a] : 0;
             len[k] = in ? fv - a : 0;
             tested[k] = len[k] > 0 && (t == 0 || fwd[o + a - 1] != fv);
-            const uint64_t x = tested[k] ? Q.win(a) : 0ull;
-            const bool fast = interval_from_window<C16>(ix, x, len[k], tested[k], iv[k]);
-            gen[k] = tested[k] && !fast;
-            const unsigned long long gb = __ballot(gen[k]);
-            if (gen[k]) sl[ngen + __popcll(gb & below)] = (uint16_t)t;
-            ngen += __popcll(gb);
         }
-        wave_lds_fence();
-        for (int c0 = 0; c0 < ngen; c0 += kWave) {               // the general search on full waves
-            if (c0 + lane < ngen) {
-                const int g = sl[c0 + lane], ga = w0 + g;
-                sv[g] = sa_interval(ix, ix.dir, Q, ga, fwd[o + ga] - ga);
-            }
-        }
-        wave_lds_fence();
-#pragma unroll
-        for (int k = 0; k < kPer; k++)
-            if (gen[k]) iv[k] = sv[k * kWave + lane];
+        fs_intervals<C16>(ix, Q, fwd, win, lane, tested, len, sl, sv, iv);
         wave_lds_fence();                                        // the list and the intervals are taken: both are reused
         // the verdict of the last tested position at or in front of every position (fact 3), then the list of the others
         bool carry = true;                                       // wave-uniform: the verdict that enters the next 64 positions
@@ -185,7 +161,7 @@ __global__ void __launch_bounds__(kLrFwdWaves * 64) mo_resolve_kernel(DevIndex i
 #pragma unroll
         for (int k = 0; k < kPer; k++) {
             const int t = k * kWave + lane;
-            const bool pass = tested[k] && cs_rows(ix, iv[k]) >= kocc;
+            const bool pass = tested[k] && fs_rows(ix, iv[k]) >= kocc;
             const unsigned long long tb = __ballot(tested[k]), pb = __ballot(pass);
             const unsigned long long mine = tb & upto;
             const bool ok = mine ? ((pb >> (63 - __clzll((long long)mine))) & 1ull) != 0 : carry;
@@ -208,7 +184,7 @@ __global__ void __launch_bounds__(kLrFwdWaves * 64) mo_resolve_kernel(DevIndex i
             int2 e;
             const bool fast = interval_from_window<C16>(ix, take ? Q.win(a) : 0ull, ms, take, e);
             if (take) v = fast ? e : sa_interval(ix, ix.dir, Q, a, ms);
-            if (have && cs_rows(ix, v) < kocc) {
+            if (have && fs_rows(ix, v) < kocc) {
                 const int l = mo_resolve(ix, Q, a, ms, v, kocc);
                 if (l < ms) {
                     fwd[o + a] = a + l;
@@ -228,7 +204,6 @@ __global__ void __launch_bounds__(256) mo_units_kernel(const long long *__restri
                                                        int32_t *__restrict__ st, const int32_t *__restrict__ wcnt,
                                                        unsigned long long *__restrict__ clip)
 {
-    __shared__ unsigned long long wsum[256 / kWave];
     const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     unsigned long long d = 0;
     if (r < N) {
@@ -244,21 +219,15 @@ __global__ void __launch_bounds__(256) mo_units_kernel(const long long *__restri
         if (rare && status == GENIE_READ_OK) st[r] = status = GENIE_READ_ABSENT_BASE;
         if (skip_flagged ? status != GENIE_READ_OK : status == GENIE_READ_BAD_BASE) d = 0;
     }
-    d = wave_sum64(d);
-    if ((threadIdx.x & (kWave - 1)) == 0) wsum[threadIdx.x / kWave] = d;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long all = 0;
-        for (int k = 0; k < 256 / kWave; k++) all += wsum[k];
-        clip[blockIdx.x] = all;
-    }
+    const unsigned long long all = fs_block_total(d);
+    if (threadIdx.x == 0) clip[blockIdx.x] = all;
 }
 
 // MO1, MO2 and the total over the units of `uoff`, whose fwd[] LR2 has written
 int mo_correct(const genie_index *ix, const MoCall &mo, bool skip_flagged, const LongArea &a, const long long *uoff, long long U,
                hipStream_t s)
 {
-    if (a.nwin > mo.a.nwin_cap || U > mo.a.unit_cap) return GENIE_E_CAPACITY;     // cannot happen: cs_units_cap
+    if (a.nwin > mo.a.nwin_cap || U > mo.a.unit_cap) return GENIE_E_CAPACITY;     // cannot happen: fs_units_cap
     const bool c16 = (ix->dev.flags & kFlagCompactTable) != 0;
     const long long nblk = (a.nwin + kLrFwdWaves - 1) / kLrFwdWaves;
     const auto one = c16 ? mo_resolve_kernel<true> : mo_resolve_kernel<false>;
@@ -267,60 +236,32 @@ int mo_correct(const genie_index *ix, const MoCall &mo, bool skip_flagged, const
                   static_cast<const uint64_t *>(a.packed), static_cast<const int32_t *>(a.st), a.fwd, mo.a.wcnt);
     const long long ublk = (U + 255) / 256;
     LAUNCH_BLOCKS(mo_units_kernel, ublk, 256, 0, s, uoff, U, (int)skip_flagged, a.st, static_cast<const int32_t *>(mo.a.wcnt), mo.a.clip);
-    if (mo.totals)
-        LAUNCH(cs_totals_kernel, dim3(1), dim3(256), 0, s, static_cast<const unsigned long long *>(mo.a.clip), (int)ublk, mo.totals);
-    return GENIE_OK;
-}
-
-inline int64_t mo_bytes(int64_t N, int64_t total, int32_t flags, bool smems, uint8_t *base, MoArea *a)
-{
-    const int S = (flags & GENIE_READS_BOTH_STRANDS) ? 2 : 1;
-    const int64_t parent = long_ex_bytes(N, total, flags, smems);
-    return parent + mo_layout(base ? base + parent : nullptr, (int64_t)S * total, cs_units_cap(N, total, flags, smems), a);
+    return mo.totals ? fs_totals(mo.a.clip, (int)ublk, mo.totals, s) : GENIE_OK;
 }
 
 }  // namespace
 
 int64_t match_stats_min_occ_workspace_bytes(int64_t N, int64_t total_bases, int32_t flags)
 {
-    MoArea a;
-    return mo_bytes(N, total_bases, flags, false, nullptr, &a);
+    return fs_bytes(N, total_bases, flags, false, mo_layout);
 }
 
-// Both calls are their parents with the step set, on the parent's part of the workspace at exactly its declared size; the
-// front cuts at the bases rare at k
+// The front cuts at the bases rare at k
 int launch_match_stats_min_occ(const genie_index *ix, int32_t min_occ, const CsrBatch &b, int32_t *d_ms, int32_t *d_lohi,
                                int64_t *d_totals, void *stream)
 {
-    hipStream_t s = (hipStream_t)stream;
-    if (d_totals) HIP_TRY(hipMemsetAsync(d_totals, 0, 8, s));
     MoCall mo{min_occ, {}, reinterpret_cast<long long *>(d_totals)};
-    if (b.N > 0) mo_bytes(b.N, b.total_bases, b.flags, false, static_cast<uint8_t *>(b.ws), &mo.a);
-    CsrBatch parent = b;
-    parent.ws_bytes = long_ex_bytes(b.N, b.total_bases, b.flags, false);
-    LuMsTail tail{ix, parent, d_ms, d_lohi, s,
-                  [&](const LongArea &a, const long long *uoff, long long U) { return mo_correct(ix, mo, false, a, uoff, U, s); }};
-    return lu_run(ix, GENIE_MODE_BWA, parent, s, tail, min_occ);
+    return fs_match_stats(ix, min_occ, b, d_ms, d_lohi, mo, mo_layout, mo_correct, (hipStream_t)stream);
 }
 
 int64_t find_smems_min_occ_workspace_bytes(int64_t N, int64_t total_bases, int32_t flags)
 {
-    MoArea a;
-    return mo_bytes(N, total_bases, flags, true, nullptr, &a);
+    return fs_bytes(N, total_bases, flags, true, mo_layout);
 }
 
 int launch_find_smems_min_occ(const genie_index *ix, int32_t mode, int32_t min_len, int32_t min_occ, const CsrBatch &b,
                               const CsrRows &out, void *stream)
 {
-    hipStream_t s = (hipStream_t)stream;
-    if (out.totals) HIP_TRY(hipMemsetAsync(out.totals, 0, 8, s));
     MoCall mo{min_occ, {}, reinterpret_cast<long long *>(out.totals)};
-    if (b.N > 0) mo_bytes(b.N, b.total_bases, b.flags, true, static_cast<uint8_t *>(b.ws), &mo.a);
-    CsrBatch parent = b;
-    parent.ws_bytes = long_ex_bytes(b.N, b.total_bases, b.flags, true);
-    LuSmemTail tail{ix, mode, min_len, parent, out, s, [&](const LongArea &a, const long long *uoff, long long U) {
-                        const int rc = mo_correct(ix, mo, true, a, uoff, U, s);
-                        return rc ? rc : cs_marks(a, uoff, U, s);
-                    }};
-    return lu_run(ix, mode, parent, s, tail, min_occ);
+    return fs_find_smems(ix, mode, min_len, min_occ, b, out, mo, mo_layout, mo_correct, (hipStream_t)stream);
 }

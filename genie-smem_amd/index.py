@@ -242,6 +242,11 @@ class GenieIndex:
                 raise ValueError(f"{names[1]} length outside [0, stride]")
         return reads, lens, n, stride, fixed
 
+    @staticmethod
+    def _bwa_if_split(mode, split_breaks):
+        if split_breaks and mode != "bwa":
+            raise ValueError("split_breaks needs mode 'bwa' (genie_find_smems_split has no other traversal)")
+
     def _workspace(self, size_fn, *args):
         """(device buffer, bytes) of the workspace the C size function `size_fn` asks for."""
         nbytes = int(getattr(N.lib(), size_fn)(*args))
@@ -403,26 +408,13 @@ class GenieIndex:
         interleaved as find_smems_both (2i is read i, 2i + 1 its reverse complement, rows in its own coordinates); with
         split_breaks (mode "bwa" only) codes > 3 and bases the reference lacks cut a strand-read into segments, as
         find_smems_split."""
-        if split_breaks and mode != "bwa":
-            raise ValueError("split_breaks needs mode 'bwa' (genie_find_smems_split has no other traversal)")
-        self._need_device()
-        bases = self._as_dev(bases, torch.uint8).reshape(-1)
-        read_offsets = self._as_dev(read_offsets, torch.int64).reshape(-1)
-        if read_offsets.numel() < 1:
-            raise ValueError("read_offsets needs N + 1 entries")
-        n_reads = read_offsets.numel() - 1
-        total = bases.numel()
-        max_len = int((read_offsets[1:] - read_offsets[:-1]).max().item()) if n_reads else 0
-        max_len = min(max(max_len, 0), 2**31 - 1)
-        if total == 0:
-            bases = torch.zeros(1, dtype=torch.uint8, device=self.device)
-        if not both_strands and not split_breaks:
+        self._bwa_if_split(mode, split_breaks)
+        bases, read_offsets, n_reads, total, max_len, flags, strands = self._csr_call(bases, read_offsets, both_strands, split_breaks)
+        if not flags:
             ws, ws_bytes = self._workspace("genie_find_smems_long_workspace_bytes", n_reads, total, max_len)
             return self._run_csr("genie_find_smems_long", (N.MODES[mode], _ptr(bases), _ptr(read_offsets), n_reads, total,
                                                            max_len, int(min_len)),
                                  n_reads, int(rows_hint) if rows_hint else max(8 * n_reads, total // 6), (_ptr(ws), ws_bytes))
-        flags = (N.READS_BOTH_STRANDS if both_strands else 0) | (N.READS_SPLIT_BREAKS if split_breaks else 0)
-        strands = 2 if both_strands else 1
         ws, ws_bytes = self._workspace("genie_find_smems_long_ex_workspace_bytes", n_reads, total, max_len, flags)
         return self._run_csr("genie_find_smems_long_ex", (N.MODES[mode], flags, _ptr(bases), _ptr(read_offsets), n_reads, total,
                                                           max_len, int(min_len)),
@@ -436,18 +428,8 @@ class GenieIndex:
         longest match that starts there (0: none; -1 throughout a strand-read flagged READ_BAD_BASE), lohi its inclusive
         suffix-array interval ((-1, -1) where there is none; not computed with intervals=False).  With split_breaks codes
         > 3 and bases the reference lacks are breaks that no match covers, and every status is READ_OK."""
-        self._need_device()
-        bases = self._as_dev(bases, torch.uint8).reshape(-1)
-        read_offsets = self._as_dev(read_offsets, torch.int64).reshape(-1)
-        if read_offsets.numel() < 1:
-            raise ValueError("read_offsets needs N + 1 entries")
-        n_reads = read_offsets.numel() - 1
-        total = bases.numel()
-        max_len = int((read_offsets[1:] - read_offsets[:-1]).max().item()) if n_reads else 0
-        max_len = min(max(max_len, 0), 2**31 - 1)
-        flags = (N.READS_BOTH_STRANDS if both_strands else 0) | (N.READS_SPLIT_BREAKS if split_breaks else 0)
-        strands = 2 if both_strands else 1
-        ms = torch.empty(strands * total, dtype=torch.int32, device=self.device)
+        bases, read_offsets, n_reads, total, max_len, flags, strands = self._csr_call(bases, read_offsets, both_strands, split_breaks)
+        ms =torch.empty(strands * total, dtype=torch.int32, device=self.device)
         lohi = torch.empty((strands * total, 2), dtype=torch.int32, device=self.device) if intervals else None
         status = torch.empty(strands * n_reads, dtype=torch.int32, device=self.device)
         ws, ws_bytes = self._workspace("genie_match_stats_workspace_bytes", n_reads, total, max_len, flags)
@@ -468,18 +450,8 @@ class GenieIndex:
     def _find_mems(self, name, table, size_tail, bases, read_offsets, min_len, both_strands, split_breaks, max_occ, rows_hint):
         """genie_find_mems or genie_find_mems_contigs: `table` are the arguments between the handle and the flags,
         `size_tail` those the workspace function takes behind the flags."""
-        self._need_device()
-        bases = self._as_dev(bases, torch.uint8).reshape(-1)
-        read_offsets = self._as_dev(read_offsets, torch.int64).reshape(-1)
-        if read_offsets.numel() < 1:
-            raise ValueError("read_offsets needs N + 1 entries")
-        n_reads = read_offsets.numel() - 1
-        total = bases.numel()
-        max_len = int((read_offsets[1:] - read_offsets[:-1]).max().item()) if n_reads else 0
-        max_len = min(max(max_len, 0), 2**31 - 1)
-        flags = (N.READS_BOTH_STRANDS if both_strands else 0) | (N.READS_SPLIT_BREAKS if split_breaks else 0)
-        strands = 2 if both_strands else 1
-        offsets = torch.empty(strands * n_reads + 1, dtype=torch.int64, device=self.device)
+        bases, read_offsets, n_reads, total, max_len, flags, strands = self._csr_call(bases, read_offsets, both_strands, split_breaks)
+        offsets =torch.empty(strands * n_reads + 1, dtype=torch.int64, device=self.device)
         status = torch.empty(strands * n_reads, dtype=torch.int32, device=self.device)
         totals = torch.empty(2, dtype=torch.int64, device=self.device)
         ws, ws_bytes = self._workspace(name + "_workspace_bytes", n_reads, total, max_len, flags, *size_tail)
@@ -512,13 +484,14 @@ class GenieIndex:
         return self._find_mems("genie_find_mems_contigs", table, (table[1],), bases, read_offsets, min_len, both_strands,
                                split_breaks, max_occ, rows_hint)
 
-    def _csr_call(self, bases, read_offsets, both_strands, split_breaks):
-        """The CSR batch of the contig-exact calls on the device -> (bases, read_offsets, N, total, max_len, flags, S)."""
+    def _csr_call(self, bases, read_offsets, both_strands=False, split_breaks=False, name="read_offsets"):
+        """The CSR batch of a call on the device -> (bases, read_offsets, N, total, max_len, flags, S).  `name`: what the
+        offsets argument is called where it is too short."""
         self._need_device()
         bases = self._as_dev(bases, torch.uint8).reshape(-1)
         read_offsets = self._as_dev(read_offsets, torch.int64).reshape(-1)
         if read_offsets.numel() < 1:
-            raise ValueError("read_offsets needs N + 1 entries")
+            raise ValueError(f"{name} needs N + 1 entries")
         n_reads = read_offsets.numel() - 1
         total = bases.numel()
         max_len = int((read_offsets[1:] - read_offsets[:-1]).max().item()) if n_reads else 0
@@ -528,6 +501,32 @@ class GenieIndex:
         flags = (N.READS_BOTH_STRANDS if both_strands else 0) | (N.READS_SPLIT_BREAKS if split_breaks else 0)
         return bases, read_offsets, n_reads, total, max_len, flags, 2 if both_strands else 1
 
+    def _step_stats(self, name, head, extra, size_tail, bases, read_offsets, intervals, both_strands, split_breaks):
+        """A match-statistics call with a step, name(handle, *head, flags, *extra, batch, ms, lohi, status, totals, workspace)
+        -> (ms, lohi, status, total); `size_tail`: what the workspace function takes behind the flags."""
+        bases, read_offsets, n_reads, total, max_len, flags, strands = self._csr_call(bases, read_offsets, both_strands, split_breaks)
+        ms = torch.empty(strands * total, dtype=torch.int32, device=self.device)
+        lohi = torch.empty((strands * total, 2), dtype=torch.int32, device=self.device) if intervals else None
+        status = torch.empty(strands * n_reads, dtype=torch.int32, device=self.device)
+        totals = torch.zeros(1, dtype=torch.int64, device=self.device)
+        ws, ws_bytes = self._workspace(name + "_workspace_bytes", n_reads, total, max_len, flags, *size_tail)
+        self._run(name, *head, flags, *extra, _ptr(bases), _ptr(read_offsets), n_reads, total, max_len, _ptr(ms), _ptr(lohi),
+                  _ptr(status), _ptr(totals), _ptr(ws), ws_bytes)
+        return ms, lohi, status, int(totals.item())
+
+    def _step_smems(self, name, head, extra, size_tail, mode, bases, read_offsets, min_len, rows_hint, both_strands, split_breaks):
+        """An SMEM call with a step, name(handle, *head, mode, flags, batch, min_len, *extra, rows, status, totals, workspace)
+        -> (offsets, smems, status, total); `size_tail` as in _step_stats."""
+        self._bwa_if_split(mode, split_breaks)
+        bases, read_offsets, n_reads, total, max_len, flags, strands = self._csr_call(bases, read_offsets, both_strands, split_breaks)
+        totals = torch.zeros(1, dtype=torch.int64, device=self.device)
+        ws, ws_bytes = self._workspace(name + "_workspace_bytes", n_reads, total, max_len, flags, *size_tail)
+        offsets, rows, status = self._run_csr(name, (*head, N.MODES[mode], flags, _ptr(bases), _ptr(read_offsets), n_reads, total,
+                                                     max_len, int(min_len), *extra),
+                                              strands * n_reads, int(rows_hint) if rows_hint else strands * max(8 * n_reads, total // 6),
+                                              (_ptr(totals), _ptr(ws), ws_bytes))
+        return offsets, rows, status, int(totals.item())
+
     def match_stats_contigs(self, contigs, bases, read_offsets, intervals=True, both_strands=False, split_breaks=False):
         """match_stats that is exact with respect to a reference of several sequences (genie_match_stats_contigs; contigs:
         the ReferenceSet this index was built from) -> (ms, lohi, status, clipped).  ms[v] is the longest match from that
@@ -536,15 +535,8 @@ class GenieIndex:
         at least one that does not --, status as match_stats, clipped the number of positions where ms is shorter than
         match_stats's."""
         off, table = self._contig_table(contigs)
-        bases, read_offsets, n_reads, total, max_len, flags, strands = self._csr_call(bases, read_offsets, both_strands, split_breaks)
-        ms = torch.empty(strands * total, dtype=torch.int32, device=self.device)
-        lohi = torch.empty((strands * total, 2), dtype=torch.int32, device=self.device) if intervals else None
-        status = torch.empty(strands * n_reads, dtype=torch.int32, device=self.device)
-        totals = torch.zeros(1, dtype=torch.int64, device=self.device)
-        ws, ws_bytes = self._workspace("genie_match_stats_contigs_workspace_bytes", n_reads, total, max_len, flags, table[1])
-        self._run("genie_match_stats_contigs", *table, flags, _ptr(bases), _ptr(read_offsets), n_reads, total, max_len, _ptr(ms),
-                  _ptr(lohi), _ptr(status), _ptr(totals), _ptr(ws), ws_bytes)
-        return ms, lohi, status, int(totals.item())
+        return self._step_stats("genie_match_stats_contigs", table, (), (table[1],), bases, read_offsets, intervals, both_strands,
+                                split_breaks)
 
     def find_smems_contigs(self, contigs, mode, bases, read_offsets, min_len=1, rows_hint=None, both_strands=False,
                            split_breaks=False):
@@ -554,17 +546,10 @@ class GenieIndex:
         concatenation and at least one of its occurrences lies inside one contig, so every row has a hit in locate_contigs.
         Options, row order and status as find_smems_long; clipped as match_stats_contigs.  If the rows outnumber rows_hint
         the call is made again with room for all."""
-        if split_breaks and mode != "bwa":
-            raise ValueError("split_breaks needs mode 'bwa' (genie_find_smems_split has no other traversal)")
+        self._bwa_if_split(mode, split_breaks)      # before the table's own checks
         off, table = self._contig_table(contigs)
-        bases, read_offsets, n_reads, total, max_len, flags, strands = self._csr_call(bases, read_offsets, both_strands, split_breaks)
-        totals = torch.zeros(1, dtype=torch.int64, device=self.device)
-        ws, ws_bytes = self._workspace("genie_find_smems_contigs_workspace_bytes", n_reads, total, max_len, flags, table[1])
-        offsets, rows, status = self._run_csr("genie_find_smems_contigs", (*table, N.MODES[mode], flags, _ptr(bases), _ptr(read_offsets),
-                                                                           n_reads, total, max_len, int(min_len)),
-                                              strands * n_reads, int(rows_hint) if rows_hint else strands * max(8 * n_reads, total // 6),
-                                              (_ptr(totals), _ptr(ws), ws_bytes))
-        return offsets, rows, status, int(totals.item())
+        return self._step_smems("genie_find_smems_contigs", table, (), (table[1],), mode, bases, read_offsets, min_len, rows_hint,
+                                both_strands, split_breaks)
 
     def match_stats_min_occ(self, bases, read_offsets, min_occ, intervals=True, both_strands=False, split_breaks=False):
         """match_stats of what occurs at least min_occ times in the reference (genie_match_stats_min_occ) -> (ms, lohi,
@@ -572,15 +557,8 @@ class GenieIndex:
         at least min_occ rows, lohi that interval ((-1, -1) where ms is 0), shortened the number of positions where ms is
         shorter than match_stats's.  A base that occurs fewer than min_occ times is "rare": it flags its strand-read
         READ_ABSENT_BASE, or is a break with split_breaks.  min_occ = 1 is match_stats."""
-        bases, read_offsets, n_reads, total, max_len, flags, strands = self._csr_call(bases, read_offsets, both_strands, split_breaks)
-        ms = torch.empty(strands * total, dtype=torch.int32, device=self.device)
-        lohi = torch.empty((strands * total, 2), dtype=torch.int32, device=self.device) if intervals else None
-        status = torch.empty(strands * n_reads, dtype=torch.int32, device=self.device)
-        totals = torch.zeros(1, dtype=torch.int64, device=self.device)
-        ws, ws_bytes = self._workspace("genie_match_stats_min_occ_workspace_bytes", n_reads, total, max_len, flags)
-        self._run("genie_match_stats_min_occ", flags, int(min_occ), _ptr(bases), _ptr(read_offsets), n_reads, total, max_len,
-                  _ptr(ms), _ptr(lohi), _ptr(status), _ptr(totals), _ptr(ws), ws_bytes)
-        return ms, lohi, status, int(totals.item())
+        return self._step_stats("genie_match_stats_min_occ", (), (int(min_occ),), (), bases, read_offsets, intervals, both_strands,
+                                split_breaks)
 
     def find_smems_min_occ(self, mode, bases, read_offsets, min_occ, min_len=1, rows_hint=None, both_strands=False,
                            split_breaks=False):
@@ -589,16 +567,8 @@ class GenieIndex:
         match contains: hi - lo + 1 >= min_occ on every row.  Options, row order and status as find_smems_long, rare bases
         and shortened as match_stats_min_occ.  Re-seeding is a loop over min_occ = occ + 1 of this call that keeps the rows
         covering the long SMEM's midpoint.  If the rows outnumber rows_hint the call is made again with room for all."""
-        if split_breaks and mode != "bwa":
-            raise ValueError("split_breaks needs mode 'bwa' (genie_find_smems_split has no other traversal)")
-        bases, read_offsets, n_reads, total, max_len, flags, strands = self._csr_call(bases, read_offsets, both_strands, split_breaks)
-        totals = torch.zeros(1, dtype=torch.int64, device=self.device)
-        ws, ws_bytes = self._workspace("genie_find_smems_min_occ_workspace_bytes", n_reads, total, max_len, flags)
-        offsets, rows, status = self._run_csr("genie_find_smems_min_occ", (N.MODES[mode], flags, _ptr(bases), _ptr(read_offsets),
-                                                                           n_reads, total, max_len, int(min_len), int(min_occ)),
-                                              strands * n_reads, int(rows_hint) if rows_hint else strands * max(8 * n_reads, total // 6),
-                                              (_ptr(totals), _ptr(ws), ws_bytes))
-        return offsets, rows, status, int(totals.item())
+        return self._step_smems("genie_find_smems_min_occ", (), (int(min_occ),), (), mode, bases, read_offsets, min_len, rows_hint,
+                                both_strands, split_breaks)
 
     def locate_contigs(self, contigs, rows):
         """SMEM rows int32 [S, 4] (start, end, lo, hi) of any find_smems* call -> (hit_offsets int64[S+1], hits int32[T, 2]
@@ -715,18 +685,9 @@ class GenieIndex:
         pattern_offsets[i+1]), any length; either on the device or the host.  Row S*i + s is pattern i (s = 0) or its reverse
         complement (s = 1): lohi as sa_interval -- (-1, -1) absent, (0, n) the empty pattern, (-2, -2) and status
         READ_BAD_BASE for a code > 3 --, counts = hi - lo + 1 (0 where absent or bad)."""
-        self._need_device()
-        bases = self._as_dev(bases, torch.uint8).reshape(-1)
-        pattern_offsets = self._as_dev(pattern_offsets, torch.int64).reshape(-1)
-        if pattern_offsets.numel() < 1:
-            raise ValueError("pattern_offsets needs N + 1 entries")
-        n_pat = pattern_offsets.numel() - 1
-        total = bases.numel()
-        max_len = int((pattern_offsets[1:] - pattern_offsets[:-1]).max().item()) if n_pat else 0
-        max_len = min(max(max_len, 0), 2**31 - 1)
-        flags = N.READS_BOTH_STRANDS if both_strands else 0
-        strands = 2 if both_strands else 1
-        lohi = torch.empty((strands * n_pat, 2), dtype=torch.int32, device=self.device)
+        bases, pattern_offsets, n_pat, total, max_len, flags, strands = self._csr_call(bases, pattern_offsets, both_strands,
+                                                                                      name="pattern_offsets")
+        lohi =torch.empty((strands * n_pat, 2), dtype=torch.int32, device=self.device)
         cnt = torch.empty(strands * n_pat, dtype=torch.int32, device=self.device) if counts else None
         status = torch.empty(strands * n_pat, dtype=torch.int32, device=self.device)
         ws, ws_bytes = self._workspace("genie_exact_match_workspace_bytes", n_pat, total, max_len, flags)

@@ -10,16 +10,15 @@ ms_c, the contig-exact matching statistic, is restated twice, independently:
                 bisection over the length.  Also counts what the bisection met (for the guard against a vacuous suite).
 
 lohi is lookup_util.interval of the ms_c bases on the concatenation; the SMEM rows are smem_util.smems(concatenation, run,
-min_len, fwd=fwd_c).  Also the cases the host and GPU tests share and the raw ctypes calls on buffers of exactly the
-declared sizes."""
-import ctypes as C
-
+min_len, fwd=fwd_c).  Also the cases the host and GPU tests share and the raw calls of step_calls.py bound to this
+pair of entry points."""
 import numpy as np
 
 import contig_util as CU
 import lookup_util as U
 import match_stats_util as MS
 import smem_util as SM
+import step_calls as SC
 
 BOTH, SPLIT, FLAGS = CU.BOTH, CU.SPLIT, CU.FLAGS
 _PER = {}            # (contig bytes, run bytes) -> fwd of the run against that contig
@@ -332,109 +331,14 @@ def bad_tables(c):
             "zeros": np.zeros(nc + 1, np.int64)}
 
 
-# ------------------------------------------------------------------ the raw calls
-def _setup(bases, offs, off, flags):
-    bases, offs, off = np.asarray(bases, np.uint8), np.asarray(offs, np.int64), np.asarray(off, np.int64)
-    n, total = offs.size - 1, int(bases.size)
-    max_len = int(np.diff(offs).max()) if n else 0
-    return (CU._dev(bases if total else np.zeros(1, np.uint8)), CU._dev(offs), CU._dev(off), n, total, max_len,
-            2 if flags & BOTH else 1, off.size - 1)
+# ------------------------------------------------------------------ the raw calls (step_calls.py, bound to this pair)
+def _bound(call):
+    """call(lib, ix, off, flags, bases, offs, ...) of step_calls' function of that name, the last result the clipped positions."""
+    return lambda lib, ix, off, flags, *args, **kw: call(SC.Pair("contigs", table=off), lib, ix, flags, *args, **kw)
 
 
-def ms_call(lib, ix, off, flags, bases, offs, intervals=True, status=True, totals=True, fill=-7, want_rc=0):
-    """One raw genie_match_stats_contigs on torch buffers of exactly the declared sizes, the workspace exactly what its size
-    function returns, every output filled with `fill` first -> (ms, lohi or None, status or None, clipped or None)."""
-    import torch
-    b, of, tab, n, total, max_len, strands, nc = _setup(bases, offs, off, flags)
-    ws_bytes = lib.genie_match_stats_contigs_workspace_bytes(n, total, max_len, flags, nc)
-    assert ws_bytes >= lib.genie_match_stats_workspace_bytes(n, total, max_len, flags) >= 0
-    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device="cuda")
-    ms = torch.full((strands * total,), fill, dtype=torch.int32, device="cuda")
-    lohi = torch.full((strands * total, 2), fill, dtype=torch.int32, device="cuda") if intervals else None
-    st = torch.full((strands * n,), fill, dtype=torch.int32, device="cuda") if status else None
-    tt = torch.full((1,), fill, dtype=torch.int64, device="cuda") if totals else None
-    p = CU._p
-    rc_ = lib.genie_match_stats_contigs(ix._h, p(tab), nc, flags, p(b), p(of), n, total, max_len, p(ms), p(lohi), p(st), p(tt), p(ws),
-                                        ws_bytes, CU._stream())
-    torch.cuda.synchronize()
-    assert rc_ == want_rc, rc_
-    if rc_:
-        return None
-    return (ms.cpu().numpy(), lohi.cpu().numpy() if intervals else None, st.cpu().numpy() if status else None,
-            int(tt.item()) if totals else None)
-
-
-def smem_call(lib, ix, off, flags, bases, offs, mode=0, min_len=1, cap=0, status=True, totals=True, fill=-7, want_rc=0, spare=0):
-    """One raw genie_find_smems_contigs (d_rows: cap + spare rows, of which the call is told cap) -> (offsets, rows, status or
-    None, clipped or None)."""
-    import torch
-    b, of, tab, n, total, max_len, strands, nc = _setup(bases, offs, off, flags)
-    ws_bytes = lib.genie_find_smems_contigs_workspace_bytes(n, total, max_len, flags, nc)
-    assert ws_bytes >= lib.genie_find_smems_long_ex_workspace_bytes(n, total, max_len, flags) >= 0
-    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device="cuda")
-    out = torch.full((strands * n + 1,), fill, dtype=torch.int64, device="cuda")
-    rw = torch.full((max(cap + spare, 1), 4), fill, dtype=torch.int32, device="cuda")
-    st = torch.full((strands * n,), fill, dtype=torch.int32, device="cuda") if status else None
-    tt = torch.full((1,), fill, dtype=torch.int64, device="cuda") if totals else None
-    p = CU._p
-    rc_ = lib.genie_find_smems_contigs(ix._h, p(tab), nc, mode, flags, p(b), p(of), n, total, max_len, min_len, p(out), p(rw), cap,
-                                       p(st), p(tt), p(ws), ws_bytes, CU._stream())
-    torch.cuda.synchronize()
-    assert rc_ == want_rc, rc_
-    if rc_:
-        return None
-    return (out.cpu().numpy(), rw.cpu().numpy()[:cap + spare], st.cpu().numpy() if status else None,
-            int(tt.item()) if totals else None)
-
-
-def sized_smem_call(lib, ix, off, flags, bases, offs, mode=0, min_len=1, **kw):
-    """The sizing call (out_cap_rows = 0), then the call with exactly that room -> (offsets, rows, status, clipped)."""
-    first = smem_call(lib, ix, off, flags, bases, offs, mode, min_len, cap=0, spare=2, **kw)
-    assert (first[1] == -7).all(), "the sizing call wrote rows"
-    got = smem_call(lib, ix, off, flags, bases, offs, mode, min_len, cap=int(first[0][-1]), **kw)
-    assert np.array_equal(got[0], first[0]) and got[3] == first[3]
-    return got
+ms_call, smem_call, sized_smem_call = _bound(SC.ms_call), _bound(SC.smem_call), _bound(SC.sized_smem_call)
 
 
 def guarded_calls(lib, ix, a, s, off, flags, reads, cap):
-    """Both calls on the guarded buffers of tests/guarded.py (inputs frozen, outputs and workspaces cut from the arena `a`
-    with exactly the declared bytes and the weakest alignment the header allows), on stream `s`, not synchronised -> their
-    statuses and a function that collects the outputs."""
-    import contract_calls as CC
-    from guarded import as_numpy
-    off = np.asarray(off, np.int64)
-    nc = off.size - 1
-    bases, offs = MS.csr(reads, 5, 3, fill=3)
-    n, total = len(reads), int(bases.size)
-    strands = 2 if flags & BOTH else 1
-    max_len = max([len(r) for r in reads] + [0])
-    tab = CC._inp(a, "contig_offsets", off, 8)
-    p = CC._inp(a, "bases", bases)
-    po = CC._inp(a, "read_offsets", offs, 8)
-    ms = a.alloc("ms", strands * total * 4, 4)
-    lohi = a.alloc("lohi", strands * total * 8, 8)
-    st = a.alloc("ms_status", strands * n * 4, 4)
-    tt = a.alloc("ms_totals", 8, 8)
-    wb = lib.genie_match_stats_contigs_workspace_bytes(n, total, max_len, flags, nc)
-    a.alloc("ms_workspace", wb, 256)
-    rcs = [lib.genie_match_stats_contigs(ix._h, CC._vp(tab), nc, flags, CC._vp(p), CC._vp(po), n, total, max_len, CC._vp(a.addr("ms")),
-                                         CC._vp(a.addr("lohi")), CC._vp(a.addr("ms_status")), CC._vp(a.addr("ms_totals")),
-                                         CC._vp(a.addr("ms_workspace")), wb, CC._vp(s))]
-    offsets = a.alloc("offsets", (strands * n + 1) * 8, 8)
-    rows = a.alloc("rows", cap * 16, 16)
-    st2 = a.alloc("status", strands * n * 4, 4)
-    tt2 = a.alloc("totals", 8, 8)
-    wb2 = lib.genie_find_smems_contigs_workspace_bytes(n, total, max_len, flags, nc)
-    a.alloc("workspace", wb2, 256)
-    rcs.append(lib.genie_find_smems_contigs(ix._h, CC._vp(tab), nc, 0, flags, CC._vp(p), CC._vp(po), n, total, max_len, 1,
-                                            CC._vp(a.addr("offsets")), CC._vp(a.addr("rows")), cap, CC._vp(a.addr("status")),
-                                            CC._vp(a.addr("totals")), CC._vp(a.addr("workspace")), wb2, CC._vp(s)))
-
-    def collect():
-        o = as_numpy(offsets, np.int64)
-        got = min(max(int(o[-1]), 0), cap)
-        assert a.holds_poison(rows[got * 16:]), "rows beyond the total were written"
-        return {"ms": as_numpy(ms, np.int32), "lohi": as_numpy(lohi, np.int32, (strands * total, 2)), "ms_status": as_numpy(st, np.int32),
-                "ms_totals": as_numpy(tt, np.int64), "offsets": o, "rows": as_numpy(rows, np.int32, (cap, 4))[:got],
-                "status": as_numpy(st2, np.int32), "totals": as_numpy(tt2, np.int64)}
-    return rcs, collect
+    return SC.guarded_calls(SC.Pair("contigs", table=off), lib, ix, a, s, flags, reads, cap)
