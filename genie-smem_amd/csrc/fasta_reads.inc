@@ -1,6 +1,8 @@
 // fasta_reads.inc -- genie_reads_from_fasta: FASTA text ('>' header lines, sequences wrapped over any number of lines) ->
 // base codes back to back, int64 offsets and the text positions of the records (included by kernels.hip behind
-// text_reads.inc, inside namespace genie; uses its tiles, its newline scan and its LDS-staged store).
+// text_reads.inc, inside namespace genie; uses its tiles and its newline scan).  From ingest_tiles.inc: tile_count and
+// tile_compact behind the classifier, tile_scan64 for fa_scan_kernel's three scans, the launch's tail.  Its own:
+// fa_classify, what fa_scan_kernel makes of the scanned values, and the writer of a header's offset and record start.
 //
 // A read is the concatenation of many lines, so it is no slice of the text -- but reads lie back to back in d_bases, so
 // d_bases is the STREAM COMPACTION of the text's kept bytes, and d_read_offsets[r] is the number of kept bytes in front of
@@ -17,26 +19,21 @@
 //                          in front of the last header so far" (it never decreases) closes the reads that cross tiles, so
 //                          the longest read needs no pass over the offsets and the sizing call knows it too.  Then the
 //                          call's state: N, total_bases, longest read, consumed bytes, malformed or not.
-//   FA3 fa_compact_kernel  a block scan of the lanes' (kept, header) counts places every code in an LDS image of the
-//                          tile's run of d_bases and stores it as tr_translate_kernel does; the lane that holds a header's
-//                          '>' writes d_read_offsets[r] and d_record_starts[r].
+//   FA3 fa_compact_kernel  tile_compact: a block scan of the lanes' (kept, header) counts places every code in an LDS image
+//                          of the tile's run of d_bases and stores it as tr_translate_kernel does; the lane that holds a
+//                          header's '>' writes d_read_offsets[r] and d_record_starts[r].
 // No atomic anywhere: every output is a function of the text alone.  All positions are 64-bit.
 namespace {
 
-constexpr int kFaMaxHeaders = kTrTile / 2 + 1;   // per tile: a header needs a '\n' in front of it (or the text's start)
 enum { kFaHeaders = kTrLines };                  // the state word tr_scan_kernel filled with the lines: here the headers
 
-struct FaLane {
-    uint32_t keep, hdr;                          // bit k: byte k of the lane's 16 is a candidate / a header's '>'
-};
-
-// Which of this lane's 16 bytes are candidates in front of `cut` and which are headers.  c, prev0: the tile's newlines and
-// the last newline before the tile.  Without GENIE_TEXT_PARTIAL cut = T; with it cut <= last_nl.
-__device__ __forceinline__ FaLane fa_classify(const uint8_t *__restrict__ text, long long T, long long tile0, int c, long long prev0,
-                                              int partial, long long last_nl, long long cut, const TrTile &s)
+// Which of this lane's 16 bytes are candidates in front of `cut` (keep) and which are a header's '>' (mark).  c, prev0: the
+// tile's newlines and the last newline before the tile.  Without GENIE_TEXT_PARTIAL cut = T; with it cut <= last_nl.
+__device__ __forceinline__ TileLane fa_classify(const uint8_t *__restrict__ text, long long T, long long tile0, int c, long long prev0,
+                                                int partial, long long last_nl, long long cut, const TrTile &s)
 {
     const int t = threadIdx.x;
-    FaLane out = {0u, 0u};
+    TileLane out = {0u, 0u};
     const long long i0 = tile0 + 16 * t;
     if (i0 >= T) return out;
     int m = 0, hi = c;                                              // m = newlines of the tile before the lane's first byte
@@ -61,7 +58,7 @@ __device__ __forceinline__ FaLane fa_classify(const uint8_t *__restrict__ text, 
         }
         if (i == start) {
             header_line = b == '>';
-            if (header_line && (!partial || i < last_nl)) out.hdr |= 1u << k;
+            if (header_line && (!partial || i < last_nl)) out.mark |= 1u << k;
         }
         if (header_line || i >= cut) continue;
         if (b == '\r') {                                            // dropped when a '\n' follows: one byte of look-ahead
@@ -76,124 +73,47 @@ __device__ __forceinline__ FaLane fa_classify(const uint8_t *__restrict__ text, 
     return out;
 }
 
-// what FA2 leaves per tile beside the two counts
-struct FaTileInfo {
-    uint32_t first_last;     // tile position of the first header | of the last header << 16 (tiles with headers only)
-    uint32_t before_first;   // candidates of the tile in front of its first header
-    uint32_t before_last;    // ... in front of its last header
-    uint32_t longest;        // the most candidates between two consecutive headers of the tile
-};
-
 __global__ void __launch_bounds__(kTrBlock) fa_count_kernel(const uint8_t *__restrict__ text, long long T, int lead, int partial,
                                                             const long long *__restrict__ last, const long long *__restrict__ state,
                                                             unsigned long long *__restrict__ cand, unsigned long long *__restrict__ hdrs,
-                                                            FaTileInfo *__restrict__ info)
+                                                            TileInfo *__restrict__ info)
 {
     __shared__ TrTile s;
-    __shared__ uint16_t hpos[kFaMaxHeaders], hcand[kFaMaxHeaders];   // per header of the tile: where, candidates in front
-    __shared__ uint32_t part[kTrBlock / kWave];
+    __shared__ TileMarks m;
     const long long tile = blockIdx.x;
-    const int t = threadIdx.x;
     const int c = tr_load_tile(text, T, lead, tile, s);
-    const long long tile0 = tile * kTrTile - lead;
     const long long last_nl = state[kTrLastNewline];
-    const FaLane L = fa_classify(text, T, tile0, c, last[tile], partial, last_nl, partial ? last_nl : T, s);
-    uint32_t total;                                                 // candidates in the low half, headers in the high half
-    const uint32_t before = tr_block_exclusive_scan((uint32_t)__popc(L.keep) | ((uint32_t)__popc(L.hdr) << 16), s.wave_total, total);
-    uint32_t h = before >> 16, rest = L.hdr;
-    while (rest) {
-        const int k = __builtin_ctz(rest);
-        hpos[h] = (uint16_t)(16 * t + k);
-        hcand[h] = (uint16_t)((before & 0xFFFFu) + __popc(L.keep & ((1u << k) - 1u)));
-        h++;
-        rest &= rest - 1;
-    }
-    __syncthreads();
-    const int nh = (int)(total >> 16);
-    uint32_t longest = 0;
-    for (int m = t + 1; m < nh; m += kTrBlock) {
-        const uint32_t len = (uint32_t)hcand[m] - (uint32_t)hcand[m - 1];
-        longest = len > longest ? len : longest;
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const uint32_t x = (uint32_t)__shfl_xor((int)longest, off, kWave);
-        longest = x > longest ? x : longest;
-    }
-    if ((t & (kWave - 1)) == 0) part[t >> 6] = longest;
-    __syncthreads();
-    if (t == 0) {
-        for (int w = 1; w < kTrBlock / kWave; w++) longest = part[w] > longest ? part[w] : longest;
-        cand[tile] = total & 0xFFFFu;
-        hdrs[tile] = (unsigned long long)nh;
-        FaTileInfo f = {0u, 0u, 0u, 0u};
-        if (nh > 0) {
-            f.first_last = (uint32_t)hpos[0] | ((uint32_t)hpos[nh - 1] << 16);
-            f.before_first = hcand[0];
-            f.before_last = hcand[nh - 1];
-            f.longest = longest;
-        }
-        info[tile] = f;
-    }
+    const TileLane L = fa_classify(text, T, tile * kTrTile - lead, c, last[tile], partial, last_nl, partial ? last_nl : T, s);
+    tile_count(L, s.wave_total, m, tile, cand, hdrs, info);
 }
 
 // single block: cand[], hdrs[] -> candidates / headers before each tile; then the call's state
 __global__ void __launch_bounds__(kScanBlock) fa_scan_kernel(unsigned long long *__restrict__ cand, unsigned long long *__restrict__ hdrs,
-                                                             const FaTileInfo *__restrict__ info, long long ntiles, long long T, int lead,
+                                                             const TileInfo *__restrict__ info, long long ntiles, long long T, int lead,
                                                              int partial, long long *__restrict__ state)
 {
     constexpr int kWaves = kScanBlock / kWave;
-    __shared__ unsigned long long wc[kWaves], wh[kWaves];
-    __shared__ long long wg[kWaves], wlen[kWaves], wpos[kWaves];
-    __shared__ unsigned long long carry_c, carry_h;
-    __shared__ long long carry_g;                                   // candidates in front of the last header so far (-1: no header)
+    __shared__ long long wc[kWaves], wh[kWaves], wg[kWaves], wlen[kWaves], wpos[kWaves];
     __shared__ long long first_e;                                   // candidates in front of the first header
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) { carry_c = carry_h = 0; carry_g = -1; first_e = 0; }
-    __syncthreads();
+    if (threadIdx.x == 0) first_e = 0;
+    // the carries, of the tiles so far: candidates, headers, candidates in front of the last header (-1: no header)
+    long long carry_c = 0, carry_h = 0, carry_g = -1;
     long long longest = 0, last_header = -1;                        // this thread's share
     for (long long base = 0; base < ntiles; base += kScanBlock) {
         const long long i = base + threadIdx.x;
         const bool mine = i < ntiles;
-        const unsigned long long c = mine ? cand[i] : 0ull, h = mine ? hdrs[i] : 0ull;
-        FaTileInfo f = {0u, 0u, 0u, 0u};
+        const long long c = mine ? (long long)cand[i] : 0ll, h = mine ? (long long)hdrs[i] : 0ll;
+        TileInfo f = {0u, 0u, 0u, 0u};
         if (mine && h) f = info[i];
-        const unsigned long long inc_c = wave_inclusive_scan64(c, lane), inc_h = wave_inclusive_scan64(h, lane);
-        if (lane == kWave - 1) { wc[wave] = inc_c; wh[wave] = inc_h; }
-        __syncthreads();
-        unsigned long long ex_c = carry_c + inc_c - c, ex_h = carry_h + inc_h - h, all_c = 0, all_h = 0;
-#pragma unroll 4
-        for (int w = 0; w < kWaves; w++) {
-            ex_c += w < wave ? wc[w] : 0ull;
-            ex_h += w < wave ? wh[w] : 0ull;
-            all_c += wc[w];
-            all_h += wh[w];
-        }
+        const long long ex_c = tile_scan64<false>(c, carry_c, wc), ex_h = tile_scan64<false>(h, carry_h, wh);
         // candidates in front of the last header before this tile: an exclusive maximum scan, the value never decreases
-        const long long key = h ? (long long)(ex_c + f.before_last) : -1ll;
-        long long mx = key;
-#pragma unroll
-        for (int off = 1; off < kWave; off <<= 1) {
-            const long long v = tr_shfl_up64(mx, off);
-            if (lane >= off && v > mx) mx = v;
-        }
-        if (lane == kWave - 1) wg[wave] = mx;
-        long long g = tr_shfl_up64(mx, 1);
-        if (lane == 0) g = -1;
-        __syncthreads();
-        long long all_g = carry_g;
-        if (carry_g > g) g = carry_g;
-#pragma unroll 4
-        for (int w = 0; w < kWaves; w++) {
-            const long long y = wg[w];
-            if (w < wave && y > g) g = y;
-            if (y > all_g) all_g = y;
-        }
+        const long long g = tile_scan64<true>(h ? ex_c + f.before_last : -1ll, carry_g, wg);
         if (mine) {
-            cand[i] = ex_c;
-            hdrs[i] = ex_h;
+            cand[i] = (unsigned long long)ex_c;
+            hdrs[i] = (unsigned long long)ex_h;
             if (h) {
-                const long long upto = (long long)(ex_c + f.before_first);   // candidates in front of the tile's first header
+                const long long upto = ex_c + f.before_first;                // candidates in front of the tile's first header
                 long long len = f.longest;
                 if (g >= 0) len = upto - g > len ? upto - g : len;           // the read that the first header closes
                 else first_e = upto;                                         // the text's first header: one writer
@@ -201,10 +121,7 @@ __global__ void __launch_bounds__(kScanBlock) fa_scan_kernel(unsigned long long 
                 last_header = i * kTrTile - lead + (long long)(f.first_last >> 16);
             }
         }
-        __syncthreads();
-        if (threadIdx.x == 0) { carry_c += all_c; carry_h += all_h; carry_g = all_g; }
-        __syncthreads();
-    }
+    }                                                               // each scan's barrier parts the others' rounds
     longest = (long long)tr_wave_max64((unsigned long long)longest);
     last_header = (long long)tr_wave_max64((unsigned long long)(last_header + 1)) - 1;
     if (lane == 0) { wlen[wave] = longest; wpos[wave] = last_header; }
@@ -214,7 +131,7 @@ __global__ void __launch_bounds__(kScanBlock) fa_scan_kernel(unsigned long long 
             longest = wlen[w] > longest ? wlen[w] : longest;
             last_header = wpos[w] > last_header ? wpos[w] : last_header;
         }
-        const long long headers = (long long)carry_h, all = (long long)carry_c, upto_last = carry_g;
+        const long long headers = carry_h, all = carry_c, upto_last = carry_g;
         const long long e = headers > 0 ? first_e : all;            // candidates that no record holds: the text is malformed
         long long total = 0;
         if (headers > 0) {
@@ -250,32 +167,15 @@ __global__ void __launch_bounds__(kTrBlock) fa_compact_kernel(const uint8_t *__r
     const int c = tr_load_tile(text, T, lead, tile, s);              // its barriers also cover tab[]
     const long long tile0 = tile * kTrTile - lead;
     const uint8_t *code = reinterpret_cast<const uint8_t *>(tab);
-    const FaLane L = fa_classify(text, T, tile0, c, last[tile], partial, state[kTrLastNewline], partial ? state[kTrConsumed] : T, s);
-    uint32_t total;
-    const uint32_t before = tr_block_exclusive_scan((uint32_t)__popc(L.keep) | ((uint32_t)__popc(L.hdr) << 16), s.wave_total, total);
-    const long long d0 = (long long)cand[tile];                      // the tile's codes are one run of d_bases, from here
-    long long r = (long long)hdrs[tile] + (before >> 16);
-    uint32_t rest = L.hdr;
-    while (rest && r < n) {                                          // header n (GENIE_TEXT_PARTIAL) opens no read of this call
-        const int k = __builtin_ctz(rest);
-        offs[r] = d0 + (before & 0xFFFFu) + __popc(L.keep & ((1u << k) - 1u));
-        if (starts) starts[r] = tile0 + 16 * t + k;
-        r++;
-        rest &= rest - 1;
-    }
+    const TileLane L = fa_classify(text, T, tile0, c, last[tile], partial, state[kTrLastNewline], partial ? state[kTrConsumed] : T, s);
     if (tile == 0 && t == 0) offs[n] = state[kTrTotal];
-    total &= 0xFFFFu;
-    if (total == 0) return;                                          // block-uniform
-    const int olead = (int)(reinterpret_cast<uintptr_t>(bases + d0) & 15);
-    uint8_t *st = reinterpret_cast<uint8_t *>(stage);
-    int at = olead + (int)(before & 0xFFFFu);
-    uint32_t keep = L.keep;
-    while (keep) {
-        st[at++] = code[tr_tile_byte(s, 16 * t + __builtin_ctz(keep))];
-        keep &= keep - 1;
-    }
-    __syncthreads();
-    tr_store_run(stage, olead, (int)total, bases, d0);
+    // the tile's codes are one run of d_bases, from cand[tile]; header n (GENIE_TEXT_PARTIAL) opens no read of this call
+    tile_compact(L, s.wave_total, s.text, stage, (long long)cand[tile], (long long)hdrs[tile], n, bases,
+                 [&](long long r, int k, long long at) {
+                     offs[r] = at;
+                     if (starts) starts[r] = tile0 + 16 * t + k;
+                 },
+                 [&](uint8_t b) { return code[b]; });
 }
 
 struct FastaArea {
@@ -283,7 +183,7 @@ struct FastaArea {
     unsigned long long *cnt;         // per tile (+ 1): FA1
     long long *last;
     unsigned long long *cand, *hdrs; // per tile: FA2, scanned in place
-    FaTileInfo *info;
+    TileInfo *info;
 };
 
 inline int64_t fasta_layout(uint8_t *p, int64_t text_bytes, FastaArea *a)
@@ -295,7 +195,7 @@ inline int64_t fasta_layout(uint8_t *p, int64_t text_bytes, FastaArea *a)
     c.take(a->last, 8 * (ntiles + 1));
     c.take(a->cand, 8 * (ntiles + 1));
     c.take(a->hdrs, 8 * (ntiles + 1));
-    c.take(a->info, (int64_t)sizeof(FaTileInfo) * (ntiles + 1));
+    c.take(a->info, (int64_t)sizeof(TileInfo) * (ntiles + 1));
     return c.at;
 }
 
@@ -315,13 +215,7 @@ int launch_reads_from_fasta(const uint8_t *d_text, int64_t text_bytes, int32_t f
     hipStream_t s = (hipStream_t)stream;
     const int partial = (flags & GENIE_TEXT_PARTIAL) ? 1 : 0;
     long long *offs = reinterpret_cast<long long *>(d_read_offsets);
-    if (text_bytes == 0) {
-        if (offs) HIP_TRY(hipMemsetAsync(offs, 0, 8, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        out5[0] = out5[1] = out5[2] = out5[3] = 0;
-        out5[4] = -1;
-        return GENIE_OK;
-    }
+    if (text_bytes == 0) return tr_empty_text(offs, s, out5);
     const int lead = (int)(reinterpret_cast<uintptr_t>(d_text) & 15);
     const long long ntiles = tr_tiles(text_bytes, lead);
     if (ntiles > 0x7fffffffll) return GENIE_E_INVALID;              // one block each
@@ -340,8 +234,7 @@ int launch_reads_from_fasta(const uint8_t *d_text, int64_t text_bytes, int32_t f
         LAUNCH(fa_compact_kernel, tgrid, tblock, 0, s, d_text, (long long)text_bytes, lead, partial, table, a.last, a.cand, a.hdrs, a.state,
                offs, reinterpret_cast<long long *>(d_record_starts), (long long)cap_reads, d_bases, (long long)cap_bases);
     long long st[kTrStateWords];
-    HIP_TRY(hipMemcpyAsync(st, a.state, sizeof(st), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
+    if (int rc = tr_read_state(a.state, s, st)) return rc;
     out5[0] = st[kTrN];
     out5[1] = st[kTrTotal];
     out5[2] = st[kTrLongest];

@@ -1,7 +1,9 @@
 // segments.inc -- genie_reference_segments and genie_segment_coords: a reference with ambiguous bases is cut at its breaks
 // (codes > 3) and at its record boundaries into SEGMENTS, the maximal runs of A/C/G/T inside one record (included by
-// kernels.hip behind contigs.inc and fasta_reads.inc, inside namespace genie; uses the tiles, the block scan and the
-// LDS-staged store of text_reads.inc, the tile scan of fasta_reads.inc and the table lookup of contigs.inc).
+// kernels.hip behind contigs.inc and fasta_reads.inc, inside namespace genie; uses the tile scan of fasta_reads.inc and
+// the table lookup of contigs.inc).  From ingest_tiles.inc: the loader (fill 0xFF, a break), tile_count and tile_compact
+// behind the classifier, the launch's tail.  Its own: sg_load_tile's boundary bitmap and classification, the error mask
+// in front of both passes, and the writer of a start's offset, record and origin.
 //
 // d_bases is the STREAM COMPACTION of the kept bytes and d_seg_offsets[s] the kept bytes in front of segment s: the shape of
 // genie_reads_from_fasta with "kept byte" for candidate and "segment start" for header.  A kept byte is a START when the byte
@@ -9,12 +11,12 @@
 // given codes, in tiles of kTrTile bytes on the 16-byte grid of their address, one block per tile:
 //   SG0 ctg_validate_kernel (contigs.inc)  the record table's three conditions -> the error mask.  A bad table ends the call:
 //                          the passes below see the mask and store nothing (SG1: zeros for its tile).
-//   SG1 sg_count_kernel    per tile: kept bytes and starts; the kept bytes in front of its first and of its last start; the
-//                          most kept bytes between two of its starts.
+//   SG1 sg_count_kernel    tile_count.  Per tile: kept bytes and starts; the kept bytes in front of its first and of its
+//                          last start; the most kept bytes between two of its starts.
 //       fa_scan_kernel (fasta_reads.inc)   exclusive sums of both counts; its exclusive maximum of "kept bytes in front of the
 //                          last start so far" closes the segments that cross tiles: n_seg, n_kept and the longest segment.
-//   SG2 sg_compact_kernel  places every kept code in an LDS image of the tile's run of d_bases and stores it coalesced; the
-//                          lane that holds a start writes the segment's offset, record and origin.
+//   SG2 sg_compact_kernel  tile_compact: places every kept code in an LDS image of the tile's run of d_bases and stores it
+//                          coalesced; the lane that holds a start writes the segment's offset, record and origin.
 // Record boundaries cost nothing per byte (sg_boundaries): two lanes bisect the table for the tile's first byte and for
 // the byte behind its last, the block sets one bit per boundary between them in an LDS bitmap of the tile (equal
 // offsets, the empty records, collapse: an entry equal to the one in front of it is skipped), and every lane reads its 16
@@ -29,10 +31,6 @@ struct SgTile {
     uint32_t bnd[kTrTile / 32];                  // bit q: a record boundary lies on tile position q
     long long range[2];                          // the table entries with a value inside the tile are [range[0], range[1])
     uint32_t wave_total[kTrBlock / kWave];
-};
-
-struct SgLane {
-    uint32_t keep, start;                        // bit k: byte k of the lane's 16 is kept / a segment's first base
 };
 
 // The first index in [0, nrec + 1] whose entry is not below `key` (nrec + 1: none).  Moves inside the table whatever it holds.
@@ -60,24 +58,13 @@ __device__ __forceinline__ long long sg_record_of(const long long *__restrict__ 
 
 // Loads the tile, stages its record boundaries and classifies this lane's 16 bytes.  Every thread of the block calls it, once;
 // the tile and s.range are readable behind it.
-__device__ __forceinline__ SgLane sg_load_tile(const uint8_t *__restrict__ codes, long long n, int lead, long long tile,
-                                               const long long *__restrict__ off, long long nrec, SgTile &s)
+__device__ __forceinline__ TileLane sg_load_tile(const uint8_t *__restrict__ codes, long long n, int lead, long long tile,
+                                                 const long long *__restrict__ off, long long nrec, SgTile &s)
 {
     const int t = threadIdx.x;
     const long long tile0 = tile * kTrTile - lead;                  // given position of tile position 0
     const long long i0 = tile0 + 16 * t;
-    uint4 w = make_uint4(~0u, ~0u, ~0u, ~0u);
-    if (i0 >= 0 && i0 + 16 <= n) {
-        w = *reinterpret_cast<const uint4 *>(codes + i0);           // codes + i0 = (codes - lead) + a multiple of 16: aligned
-    } else if (i0 + 16 > 0 && i0 < n) {
-        uint32_t x[4] = {~0u, ~0u, ~0u, ~0u};
-#pragma unroll
-        for (int k = 0; k < 16; k++) {
-            const long long i = i0 + k;
-            if (i >= 0 && i < n) x[k >> 2] ^= (uint32_t)(uint8_t)~codes[i] << (8 * (k & 3));
-        }
-        w = make_uint4(x[0], x[1], x[2], x[3]);
-    }
+    const uint4 w = tile_load_word(codes, n, i0, 0xFFu);
     s.text[t] = w;
     if (t < kTrTile / 32) s.bnd[t] = 0u;
     if (off && t < 2) {                                             // lane 0: the first byte's entries; lane 1: behind the last byte
@@ -94,7 +81,7 @@ __device__ __forceinline__ SgLane sg_load_tile(const uint8_t *__restrict__ codes
         __syncthreads();
     }
     const uint32_t ws[4] = {w.x, w.y, w.z, w.w};
-    SgLane L = {0u, 0u};
+    TileLane L = {0u, 0u};
 #pragma unroll
     for (int j = 0; j < 4; j++) {                                   // a code is kept when it is at most 3: its upper six bits are 0
         const uint32_t z = tr_zero_bytes(ws[j] & 0xFCFCFCFCu);
@@ -105,62 +92,26 @@ __device__ __forceinline__ SgLane sg_load_tile(const uint8_t *__restrict__ codes
     else if (tile0 > 0 && tile0 - 1 < n) prev = codes[tile0 - 1];
     const uint32_t before = (L.keep << 1) | (prev <= 3u ? 1u : 0u); // bit k: the byte in front of byte k is kept
     const uint32_t bnd = (s.bnd[t >> 1] >> (16 * (t & 1))) & 0xFFFFu;
-    L.start = L.keep & (~before | bnd) & 0xFFFFu;
+    L.mark = L.keep & (~before | bnd) & 0xFFFFu;
     return L;
 }
 
 __global__ void __launch_bounds__(kTrBlock) sg_count_kernel(const uint8_t *__restrict__ codes, long long n, int lead,
                                                             const long long *__restrict__ off, long long nrec,
                                                             const long long *__restrict__ state, unsigned long long *__restrict__ kept,
-                                                            unsigned long long *__restrict__ starts, FaTileInfo *__restrict__ info)
+                                                            unsigned long long *__restrict__ starts, TileInfo *__restrict__ info)
 {
     __shared__ SgTile s;
-    __shared__ uint16_t skept[kTrTile];                             // per start of the tile: the tile's kept bytes in front of it
-    __shared__ uint32_t part[kTrBlock / kWave];
+    __shared__ TileMarks m;
     const long long tile = blockIdx.x;
-    const int t = threadIdx.x;
     if (state[kSgMask] != 0) {                                      // block-uniform: a bad table, the call fails
-        if (t == 0) {
+        if (threadIdx.x == 0) {
             kept[tile] = starts[tile] = 0ull;
-            info[tile] = FaTileInfo{0u, 0u, 0u, 0u};
+            info[tile] = TileInfo{0u, 0u, 0u, 0u};
         }
         return;
     }
-    const SgLane L = sg_load_tile(codes, n, lead, tile, off, nrec, s);
-    uint32_t total;                                                 // kept bytes in the low half, starts in the high half
-    const uint32_t before = tr_block_exclusive_scan((uint32_t)__popc(L.keep) | ((uint32_t)__popc(L.start) << 16), s.wave_total, total);
-    uint32_t h = before >> 16, rest = L.start;
-    while (rest) {
-        const int k = __builtin_ctz(rest);
-        skept[h++] = (uint16_t)((before & 0xFFFFu) + __popc(L.keep & ((1u << k) - 1u)));
-        rest &= rest - 1;
-    }
-    __syncthreads();
-    const int nh = (int)(total >> 16);
-    uint32_t longest = 0;
-    for (int m = t + 1; m < nh; m += kTrBlock) {
-        const uint32_t len = (uint32_t)skept[m] - (uint32_t)skept[m - 1];
-        longest = len > longest ? len : longest;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint32_t x = (uint32_t)__shfl_xor((int)longest, o, kWave);
-        longest = x > longest ? x : longest;
-    }
-    if ((t & (kWave - 1)) == 0) part[t >> 6] = longest;
-    __syncthreads();
-    if (t == 0) {
-        for (int w = 1; w < kTrBlock / kWave; w++) longest = part[w] > longest ? part[w] : longest;
-        kept[tile] = total & 0xFFFFu;
-        starts[tile] = (unsigned long long)nh;
-        FaTileInfo f = {0u, 0u, 0u, 0u};
-        if (nh > 0) {
-            f.before_first = skept[0];
-            f.before_last = skept[nh - 1];
-            f.longest = longest;
-        }
-        info[tile] = f;
-    }
+    tile_count(sg_load_tile(codes, n, lead, tile, off, nrec, s), s.wave_total, m, tile, kept, starts, info);
 }
 
 __global__ void __launch_bounds__(kTrBlock) sg_compact_kernel(const uint8_t *__restrict__ codes, long long n, int lead,
@@ -179,47 +130,29 @@ __global__ void __launch_bounds__(kTrBlock) sg_compact_kernel(const uint8_t *__r
     if (state[kSgMask] != 0 || nseg > cap_segs || nkept > cap_bases) return;
     const int t = threadIdx.x;
     const long long tile = blockIdx.x;
-    const SgLane L = sg_load_tile(codes, n, lead, tile, off, nrec, s);
+    const TileLane L = sg_load_tile(codes, n, lead, tile, off, nrec, s);
     const long long tile0 = tile * kTrTile - lead;
-    uint32_t total;
-    const uint32_t before = tr_block_exclusive_scan((uint32_t)__popc(L.keep) | ((uint32_t)__popc(L.start) << 16), s.wave_total, total);
-    const long long d0 = (long long)kept[tile];                      // the tile's kept codes are one run of d_bases, from here
-    long long sg = (long long)starts[tile] + (before >> 16);
-    uint32_t rest = L.start;
-    while (rest && sg < nseg) {
-        const int k = __builtin_ctz(rest);
-        const long long i = tile0 + 16 * t + k;
-        long long r = 0, origin = i;
-        if (off) {
-            r = sg_record_of(off, nrec, s.range[0], s.range[1], i);
-            origin = i - off[r];
-        }
-        seg_off[sg] = d0 + (before & 0xFFFFu) + __popc(L.keep & ((1u << k) - 1u));
-        seg_rec[sg] = (int32_t)r;
-        seg_org[sg] = origin;
-        sg++;
-        rest &= rest - 1;
-    }
     if (tile == 0 && t == 0) seg_off[nseg] = nkept;
-    total &= 0xFFFFu;
-    if (total == 0) return;                                          // block-uniform
-    const int olead = (int)(reinterpret_cast<uintptr_t>(bases + d0) & 15);
-    uint8_t *st = reinterpret_cast<uint8_t *>(stage);
-    const uint8_t *tb = reinterpret_cast<const uint8_t *>(s.text);
-    int at = olead + (int)(before & 0xFFFFu);
-    uint32_t keep = L.keep;
-    while (keep) {
-        st[at++] = tb[16 * t + __builtin_ctz(keep)];
-        keep &= keep - 1;
-    }
-    __syncthreads();
-    tr_store_run(stage, olead, (int)total, bases, d0);
+    // the tile's kept codes are one run of d_bases, from kept[tile]
+    tile_compact(L, s.wave_total, s.text, stage, (long long)kept[tile], (long long)starts[tile], nseg, bases,
+                 [&](long long sg, int k, long long at) {
+                     const long long i = tile0 + 16 * t + k;
+                     long long r = 0, origin = i;
+                     if (off) {
+                         r = sg_record_of(off, nrec, s.range[0], s.range[1], i);
+                         origin = i - off[r];
+                     }
+                     seg_off[sg] = at;
+                     seg_rec[sg] = (int32_t)r;
+                     seg_org[sg] = origin;
+                 },
+                 [](uint8_t b) { return b; });
 }
 
 struct SegArea {
     long long *state;
     unsigned long long *kept, *starts;   // per tile: SG1, scanned in place
-    FaTileInfo *info;
+    TileInfo *info;
 };
 
 inline int64_t seg_layout(uint8_t *p, int64_t n_given, SegArea *a)
@@ -229,7 +162,7 @@ inline int64_t seg_layout(uint8_t *p, int64_t n_given, SegArea *a)
     c.take(a->state, 8 * kTrStateWords);
     c.take(a->kept, 8 * (ntiles + 1));
     c.take(a->starts, 8 * (ntiles + 1));
-    c.take(a->info, (int64_t)sizeof(FaTileInfo) * (ntiles + 1));
+    c.take(a->info, (int64_t)sizeof(TileInfo) * (ntiles + 1));
     return c.at;
 }
 
@@ -301,8 +234,7 @@ int launch_reference_segments(const uint8_t *d_codes, int64_t n_given, const int
                a.starts, d_bases, (long long)cap_bases, reinterpret_cast<long long *>(d_seg_offsets), d_seg_record,
                reinterpret_cast<long long *>(d_seg_origin), (long long)cap_segs);
     long long st[kTrStateWords];
-    HIP_TRY(hipMemcpyAsync(st, a.state, sizeof(st), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
+    if (int rc = tr_read_state(a.state, s, st)) return rc;
     out4[0] = st[kTrN];
     out4[1] = st[kTrTotal];
     out4[2] = st[kTrLongest];

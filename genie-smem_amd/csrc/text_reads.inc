@@ -1,6 +1,8 @@
 // text_reads.inc -- genie_reads_from_text: text (one read per line, or four-line FASTQ records) -> base codes back to back
-// and int64 offsets, the input of genie_find_smems_long_ex (included by kernels.hip, inside namespace genie; uses its launch
-// plumbing, the workspace carver and the block-sums scan).
+// and int64 offsets, the input of genie_find_smems_long_ex (included by kernels.hip behind ingest_tiles.inc, inside namespace
+// genie; uses its launch plumbing, the workspace carver and the block-sums scan).  From ingest_tiles.inc: the tiles and
+// their loader, the block scan, tile_stage_store for TR3's second half, and the launch's tail.  Its own: the newline list,
+// tr_scan_kernel's two scans, the line lengths and their offsets scan, FASTQ's checks.
 //
 // Three flat passes over the text, cut into TILES of kTrTile bytes, one block per tile.  Nothing is per read: a line of
 // 10^6 bases and 10^5 empty lines cost the same per byte.  Tiles are cut on the 16-byte grid of the text's ADDRESS, not of
@@ -26,12 +28,7 @@
 // No atomic decides a position: every output byte and offset is a function of the text alone.  All positions are 64-bit.
 namespace {
 
-constexpr int kTrBlock = 256;
-constexpr int kTrTile = 16 * kTrBlock;           // bytes of text per block: 16 per lane
 constexpr unsigned long long kTrNoBad = ~0ull;
-
-// the call's state, in the workspace (int64 each); the host copies it back at the end of the call
-enum { kTrN = 0, kTrTotal, kTrLongest, kTrConsumed, kTrBad, kTrLines, kTrNewlines, kTrLastNewline, kTrStateWords };
 
 struct TrTable {
     uint32_t w[64];                              // code_of_byte, already clamped to 0..4, four entries per word
@@ -43,53 +40,12 @@ struct TrTile {
     uint32_t wave_total[kTrBlock / kWave];
 };
 
-// 0x80 in every byte of x that is zero (exact: no carry between bytes)
-__device__ __forceinline__ uint32_t tr_zero_bytes(uint32_t x)
-{
-    return ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x | 0x7F7F7F7Fu);
-}
-
-// Exclusive scan of one count per thread over the block, and the block's total.  Every thread calls it; a barrier lies
-// between two calls that share `wave_total`.
-__device__ __forceinline__ uint32_t tr_block_exclusive_scan(uint32_t c, uint32_t *wave_total, uint32_t &total)
-{
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
-    uint32_t inc = c;
-#pragma unroll
-    for (int off = 1; off < kWave; off <<= 1) {
-        const uint32_t v = (uint32_t)__shfl_up((int)inc, off, kWave);
-        if (lane >= off) inc += v;
-    }
-    if (lane == kWave - 1) wave_total[wave] = inc;
-    __syncthreads();
-    uint32_t before = inc - c;
-    total = 0;
-#pragma unroll
-    for (int wv = 0; wv < kTrBlock / kWave; wv++) {
-        const uint32_t x = wave_total[wv];
-        before += wv < wave ? x : 0u;
-        total += x;
-    }
-    return before;
-}
-
 // Loads tile `tile` into LDS and lists its newlines; returns their number.  Every thread of the block calls it, once.
 __device__ __forceinline__ int tr_load_tile(const uint8_t *__restrict__ text, long long T, int lead, long long tile, TrTile &s)
 {
     const int t = threadIdx.x;
     const long long i0 = tile * kTrTile + 16 * t - lead;           // text position of this lane's first byte
-    uint4 w = make_uint4(0u, 0u, 0u, 0u);
-    if (i0 >= 0 && i0 + 16 <= T) {
-        w = *reinterpret_cast<const uint4 *>(text + i0);           // text + i0 = (text - lead) + a multiple of 16: aligned
-    } else if (i0 + 16 > 0 && i0 < T) {
-        uint32_t x[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-        for (int k = 0; k < 16; k++) {
-            const long long i = i0 + k;
-            if (i >= 0 && i < T) x[k >> 2] |= (uint32_t)text[i] << (8 * (k & 3));
-        }
-        w = make_uint4(x[0], x[1], x[2], x[3]);
-    }
+    const uint4 w = tile_load_word(text, T, i0, 0u);
     s.text[t] = w;
     const uint32_t ws[4] = {w.x, w.y, w.z, w.w};
     uint32_t mask = 0;                                              // bit k: byte k of the 16 is a newline
@@ -122,14 +78,9 @@ __global__ void __launch_bounds__(kTrBlock) tr_count_kernel(const uint8_t *__res
     }
 }
 
-__device__ __forceinline__ long long tr_shfl_up64(long long v, int off)
-{
-    const unsigned int lo = (unsigned)__shfl_up((int)(unsigned)(unsigned long long)v, off, kWave);
-    const unsigned int hi = (unsigned)__shfl_up((int)(unsigned)((unsigned long long)v >> 32), off, kWave);
-    return (long long)(((unsigned long long)hi << 32) | lo);
-}
-
 // single block: cnt[] -> newlines before each tile, last[] -> last newline before each tile (-1: none); then the state
+// (its two scans share one barrier and one pass over the waves' totals; through tile_scan64, one scan behind the other, the
+// call measured 10 to 30 us slower on 150 to 300 MB of text, so they stay written out)
 __global__ void __launch_bounds__(kScanBlock) tr_scan_kernel(unsigned long long *__restrict__ cnt, long long *__restrict__ last,
                                                              long long ntiles, long long T, int format, int partial,
                                                              long long *__restrict__ state)
@@ -187,18 +138,6 @@ __global__ void __launch_bounds__(kScanBlock) tr_scan_kernel(unsigned long long 
         state[kTrNewlines] = newlines;
         state[kTrLastNewline] = last_nl;
     }
-}
-
-__device__ __forceinline__ unsigned long long tr_wave_max64(unsigned long long v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned int lo = (unsigned)__shfl_xor((int)(unsigned)v, off, kWave);
-        const unsigned int hi = (unsigned)__shfl_xor((int)(unsigned)(v >> 32), off, kWave);
-        const unsigned long long x = ((unsigned long long)hi << 32) | lo;
-        v = x > v ? x : v;
-    }
-    return v;
 }
 
 // offs: d_read_offsets or null (the sizing call); lengths go to offs[r + 1] for r < cap_reads
@@ -340,24 +279,6 @@ __global__ void __launch_bounds__(kScanBlock) tr_offsets_apply(long long *__rest
     if (i == 0) offs[0] = 0;
 }
 
-// The block's run of codes, staged in LDS on the 16-byte grid of its destination: stage bytes [olead, olead + total) go to
-// bases[d0 .. d0 + total), 16 bytes per lane, byte by byte only at the run's two ends.  Every thread of the block calls it,
-// behind the barrier that follows the staging.
-__device__ __forceinline__ void tr_store_run(const uint4 *stage, int olead, int total, uint8_t *__restrict__ bases, long long d0)
-{
-    const uint8_t *st = reinterpret_cast<const uint8_t *>(stage);
-    const int end = olead + total;
-    for (int ch = threadIdx.x; 16 * ch < end; ch += kTrBlock) {
-        const int lo = 16 * ch;
-        if (lo >= olead && lo + 16 <= end) {
-            *reinterpret_cast<uint4 *>(bases + (d0 + (lo - olead))) = stage[ch];
-        } else {
-            for (int k = 0; k < 16; k++)
-                if (lo + k >= olead && lo + k < end) bases[d0 + (lo + k - olead)] = st[lo + k];
-        }
-    }
-}
-
 __global__ void __launch_bounds__(kTrBlock) tr_translate_kernel(const uint8_t *__restrict__ text, long long T, int lead, int format,
                                                                 const TrTable table, const unsigned long long *__restrict__ cnt,
                                                                 const long long *__restrict__ last, const long long *__restrict__ state,
@@ -422,20 +343,9 @@ __global__ void __launch_bounds__(kTrBlock) tr_translate_kernel(const uint8_t *_
     const uint32_t before = tr_block_exclusive_scan((uint32_t)__popc(keep), s.wave_total, total);
     if (keep && before == 0) first_dst = dst;
     __syncthreads();
-    if (total == 0) return;                                          // block-uniform
-    const long long d0 = first_dst;
-    const int olead = (int)(reinterpret_cast<uintptr_t>(bases + d0) & 15);
-    uint8_t *st = reinterpret_cast<uint8_t *>(stage);
-    int at = olead + (int)before;
-    while (keep) {
-        st[at++] = code[tr_tile_byte(s, 16 * t + __builtin_ctz(keep))];
-        keep &= keep - 1;
-    }
-    __syncthreads();
-    tr_store_run(stage, olead, (int)total, bases, d0);
+    tile_stage_store(keep, before, total, s.text, stage, bases, first_dst, [&](uint8_t b) { return code[b]; });
 }
 
-inline long long tr_tiles(int64_t text_bytes, int lead) { return (text_bytes + lead + kTrTile - 1) / kTrTile; }
 inline int64_t tr_scan_blocks(int64_t text_bytes, int64_t cap_reads)
 {
     const int64_t most = cap_reads < text_bytes ? cap_reads : text_bytes;   // a text of T bytes has at most T lines
@@ -493,13 +403,7 @@ int launch_reads_from_text(const uint8_t *d_text, int64_t text_bytes, int32_t fo
     hipStream_t s = (hipStream_t)stream;
     const int partial = (flags & GENIE_TEXT_PARTIAL) ? 1 : 0;
     long long *offs = reinterpret_cast<long long *>(d_read_offsets);
-    if (text_bytes == 0) {
-        if (offs) HIP_TRY(hipMemsetAsync(offs, 0, 8, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        out5[0] = out5[1] = out5[2] = out5[3] = 0;
-        out5[4] = -1;
-        return GENIE_OK;
-    }
+    if (text_bytes == 0) return tr_empty_text(offs, s, out5);
     const int lead = (int)(reinterpret_cast<uintptr_t>(d_text) & 15);
     const long long ntiles = tr_tiles(text_bytes, lead);
     if (ntiles > 0x7fffffffll || tr_scan_blocks(text_bytes, cap_reads) > 0x7fffffffll) return GENIE_E_INVALID;   // one block each
@@ -523,8 +427,7 @@ int launch_reads_from_text(const uint8_t *d_text, int64_t text_bytes, int32_t fo
                offs, (long long)cap_reads, d_bases, (long long)cap_bases);
     }
     long long st[kTrStateWords];
-    HIP_TRY(hipMemcpyAsync(st, a.state, sizeof(st), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
+    if (int rc = tr_read_state(a.state, s, st)) return rc;
     out5[0] = st[kTrN];
     out5[1] = st[kTrTotal];
     out5[2] = st[kTrLongest];

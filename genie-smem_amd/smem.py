@@ -116,16 +116,8 @@ class SMEM:
         both_strands: 2N strand-reads as find_smems_both (2i read i, 2i + 1 its reverse complement).  split_breaks (mode
         "bwa"): breaks cut the reads as find_smems_split; strings are then encoded with ExactMatch.encode_lenient."""
         ix = self.matcher.index(self.lut.lut_size)
-        if isinstance(reads, tuple):
-            bases, read_offsets = reads
-            return ix.find_smems_long(mode, bases, read_offsets, minimum_length, both_strands=both_strands,
-                                      split_breaks=split_breaks)
-        encode = self.matcher.encode_lenient if split_breaks else self.matcher.encode
-        enc = [encode(r) for r in reads]
-        offs = np.zeros(len(enc) + 1, np.int64)
-        offs[1:] = np.cumsum([len(e) for e in enc]) if enc else []
-        bases = np.concatenate(enc).astype(np.uint8) if enc else np.zeros(0, np.uint8)
-        return ix.find_smems_long(mode, bases, offs, minimum_length, both_strands=both_strands, split_breaks=split_breaks)
+        bases, read_offsets = self._csr_reads(reads, split_breaks)
+        return ix.find_smems_long(mode, bases, read_offsets, minimum_length, both_strands=both_strands, split_breaks=split_breaks)
 
     def find_smems_text(self, data, fmt="lines", mode="bwa", minimum_length=1, both_strands=False, split_breaks=True,
                         fold_case=False):
@@ -151,14 +143,7 @@ class SMEM:
         forward_extension(q, p)[1] == q[p:p + ms] and its interval is lohi.  split_breaks: breaks are covered by no match
         and flag no read; strings are then encoded with ExactMatch.encode_lenient."""
         ix = self.matcher.index(self.lut.lut_size)
-        if isinstance(reads, tuple):
-            bases, read_offsets = reads
-        else:
-            encode = self.matcher.encode_lenient if split_breaks else self.matcher.encode
-            enc = [encode(r) for r in reads]
-            read_offsets = np.zeros(len(enc) + 1, np.int64)
-            read_offsets[1:] = np.cumsum([len(e) for e in enc]) if enc else []
-            bases = np.concatenate(enc).astype(np.uint8) if enc else np.zeros(0, np.uint8)
+        bases, read_offsets = self._csr_reads(reads, split_breaks)
         return ix.match_stats(bases, read_offsets, intervals, both_strands, split_breaks)
 
     def find_mems(self, reads, minimum_length, both_strands=False, split_breaks=False, max_occ=0):
@@ -169,14 +154,7 @@ class SMEM:
         max_occ > 0 skips positions whose first minimum_length bases occur more often than that (`skipped` counts them).
         split_breaks: breaks end a match and flag no read; strings are then encoded with ExactMatch.encode_lenient."""
         ix = self.matcher.index(self.lut.lut_size)
-        if isinstance(reads, tuple):
-            bases, read_offsets = reads
-        else:
-            encode = self.matcher.encode_lenient if split_breaks else self.matcher.encode
-            enc = [encode(r) for r in reads]
-            read_offsets = np.zeros(len(enc) + 1, np.int64)
-            read_offsets[1:] = np.cumsum([len(e) for e in enc]) if enc else []
-            bases = np.concatenate(enc).astype(np.uint8) if enc else np.zeros(0, np.uint8)
+        bases, read_offsets = self._csr_reads(reads, split_breaks)
         return ix.find_mems(bases, read_offsets, minimum_length, both_strands, split_breaks, max_occ)
 
     def find_mems_contigs(self, contigs, reads, minimum_length, both_strands=False, split_breaks=False, max_occ=0):
@@ -184,14 +162,7 @@ class SMEM:
         concatenation this matcher's reference is.  reads and the four results as find_mems; every row lies inside one
         contig (GenieIndex.find_mems_contigs), pos is 1-based in the concatenation (contigs.coords names it)."""
         ix = self.matcher.index(self.lut.lut_size)
-        if isinstance(reads, tuple):
-            bases, read_offsets = reads
-        else:
-            encode = self.matcher.encode_lenient if split_breaks else self.matcher.encode
-            enc = [encode(r) for r in reads]
-            read_offsets = np.zeros(len(enc) + 1, np.int64)
-            read_offsets[1:] = np.cumsum([len(e) for e in enc]) if enc else []
-            bases = np.concatenate(enc).astype(np.uint8) if enc else np.zeros(0, np.uint8)
+        bases, read_offsets = self._csr_reads(reads, split_breaks)
         return ix.find_mems_contigs(contigs, bases, read_offsets, minimum_length, both_strands, split_breaks, max_occ)
 
     def chain_mems(self, offsets, rows, contigs=None, **chain_options):

@@ -9,6 +9,8 @@ import re
 
 import numpy as np
 
+from ingest_calls import SPARE, Call
+
 OK, INVALID, NO_DEVICE, TOO_LONG, CAPACITY = 0, -1, -4, -6, -10
 POSITIONS, HITS = 0, 1
 TILE = 4096                     # bytes of the given reference per block in csrc/segments.inc (on the 16-byte grid of the address)
@@ -171,45 +173,24 @@ def _p(t):
     return C.c_void_p(t.data_ptr() if t is not None and t.numel() else 0)
 
 
-def segments_call(lib, codes, off=None, cap_bases=None, cap_segs=None, sizing=False, lead=0, fill=0xA5, want_rc=OK, spare=3):
-    """One raw genie_reference_segments: the codes at an address that is `lead` modulo 16, outputs of cap + spare elements
-    filled with `fill` (the call is told cap), the scratch exactly what its size function returns -> dict of numpy arrays
-    (out4; bases, seg_offsets, seg_record, seg_origin whole, spare included).  Default capacities: the true sizes."""
+CALL = Call("genie_reference_segments", [("int64", 1), ("int32", 0), ("int64", 0)], 4, null_cap=-5)
+
+
+def segments_call(lib, codes, off=None, cap_bases=None, cap_segs=None, sizing=False, lead=0, fill=0xA5, want_rc=OK, spare=SPARE):
+    """ingest_calls.Call.run of genie_reference_segments with the record table `off` (None: NULL, one record) -> dict of numpy
+    arrays (out4; bases, seg_offsets, seg_record, seg_origin whole, spare included).  Default capacities: the true sizes."""
     import torch
-    codes = np.asarray(codes, np.uint8)
-    n = codes.size
     nrec = 1 if off is None else len(off) - 1
-    whole = torch.zeros(n + 16, dtype=torch.uint8, device="cuda")
-    d_codes = whole[lead:lead + n]
-    if n:
-        d_codes.copy_(torch.from_numpy(codes))
     d_off = None if off is None else torch.as_tensor(np.asarray(off, np.int64)).cuda()
-    tmp_bytes = lib.genie_reference_segments_tmp_bytes(n, nrec)
-    assert tmp_bytes > 0 and tmp_bytes % 256 == 0
-    tmp = torch.full((tmp_bytes,), fill, dtype=torch.uint8, device="cuda")
-    out4 = (C.c_int64 * 4)(-9, -9, -9, -9)
+    got = CALL.run(lib, codes, (_p(d_off), nrec), lambda cap: CALL.tmp_bytes(lib, np.asarray(codes).size, nrec), cap_bases, cap_segs,
+                   sizing, lead, fill, spare)
+    assert got[0] == want_rc, got[0]
     if sizing:
-        rc_ = lib.genie_reference_segments(_p(d_codes), n, _p(d_off), nrec, None, -5, None, None, None, -5, out4, _p(tmp), tmp_bytes,
-                                           _stream())
-        assert rc_ == want_rc, rc_
-        return {"out4": list(out4)}
-    if cap_bases is None or cap_segs is None:
-        size = segments_call(lib, codes, off, sizing=True, lead=lead)["out4"]
-        cap_segs = size[0] if cap_segs is None else cap_segs
-        cap_bases = size[1] if cap_bases is None else cap_bases
-    bases = torch.full((cap_bases + spare,), fill, dtype=torch.uint8, device="cuda")
-    so = torch.full((cap_segs + 1 + spare,), -7, dtype=torch.int64, device="cuda")
-    sr = torch.full((cap_segs + spare,), -7, dtype=torch.int32, device="cuda")
-    sg = torch.full((cap_segs + spare,), -7, dtype=torch.int64, device="cuda")
-    rc_ = lib.genie_reference_segments(_p(d_codes), n, _p(d_off), nrec, _p(bases), cap_bases, _p(so), _p(sr), _p(sg), cap_segs, out4,
-                                       _p(tmp), tmp_bytes, _stream())
-    torch.cuda.synchronize()
-    assert rc_ == want_rc, rc_
-    return {"out4": list(out4), "bases": bases.cpu().numpy(), "seg_offsets": so.cpu().numpy(), "seg_record": sr.cpu().numpy(),
-            "seg_origin": sg.cpu().numpy(), "fill": fill}
+        return {"out4": got[1]}
+    return {"out4": got[1], "bases": got[2], "seg_offsets": got[3][0], "seg_record": got[3][1], "seg_origin": got[3][2], "fill": fill}
 
 
-def same_as_cut(got, want, spare=3):
+def same_as_cut(got, want, spare=SPARE):
     """The outputs of a filling segments_call with the true capacities against cut()'s; everything behind them untouched."""
     bases, so, sr, sg, longest = want
     S, kept = len(sr), len(bases)

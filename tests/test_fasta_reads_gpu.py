@@ -158,6 +158,15 @@ def test_many_tiny_records(lib, tiny_records):
     assert FU.same_as_model(lib, tiny_records, FU.PARTIAL)[1][0] == 2999
 
 
+@pytest.mark.parametrize("head", [b"", b">x\nA"])
+def test_densest_headers(lib, head):
+    """A header every two bytes, TILE / 2 in every full tile -- the most a tile can hold -- at both parities of the headers
+    against the tile grid (behind the head the first '>' ends the line "A>", so both texts hold as many records)."""
+    text = head + b">\n" * (2 * TILE + 3)
+    assert FU.same_as_model(lib, text)[1][0] == 2 * TILE + 3
+    assert FU.same_as_model(lib, text, FU.PARTIAL)[1][0] == 2 * TILE + 2
+
+
 def test_more_than_1024_tiles(lib):
     """A little over 4 MiB: the one-block scans over the tiles take a second round."""
     rng = np.random.default_rng(12)

@@ -75,6 +75,17 @@ def test_record_boundaries(lib, name):
         assert all(np.array_equal(a, b) for a, b in zip(want[:4], same[:4]))
 
 
+def test_every_byte_a_start(lib):
+    """A record boundary on every byte and no break: TILE starts in every full tile, the most a tile can hold."""
+    n = 2 * TILE + 5
+    codes = np.random.default_rng(41).integers(0, 4, n).astype(np.uint8)
+    off = list(range(n + 1))
+    want = SU.cut(codes, off)
+    assert len(want[2]) == n and want[4] == 1
+    for lead in (0, 5):
+        SU.same_as_cut(SU.segments_call(lib, codes, off, lead=lead), want)
+
+
 @pytest.mark.parametrize("density,seed", SU.RANDOM)
 def test_random_references(lib, pkg, density, seed):
     codes, off = SU.random_case(density, seed)

@@ -58,6 +58,15 @@ FIND_SMEMS_MIN_OCC = {
 # at each of SCRATCH_N
 COMPACT = [32, 40, 40, 7848, 78160]
 LOCATE = [512, 768, 4608, 4008192, 40078592]
+# The ingestion calls, recorded before their kernels were put on shared tile pieces: at each of INGEST_BYTES (text_bytes or
+# n_given) the bytes at each of INGEST_COUNTS (cap_reads or n_records)
+INGEST_BYTES = [0, 1, 4095, 4096, 4097, 10**8]
+INGEST_COUNTS = [0, 1, 10**6]
+INGEST = {
+    "reads_from_text": [[1536] * 3] * 5 + [[781824, 781824, 789504]],
+    "reads_from_fasta": [[1536] * 3] * 5 + [[1172224] * 3],
+    "reference_segments": [[1024] * 3] * 5 + [[781568] * 3],
+}
 
 
 @pytest.fixture(scope="module")
@@ -102,3 +111,9 @@ def test_step_call_workspace_bytes(lib, name, want, contigs):
 def test_compact_and_locate_tmp_bytes(lib):
     assert [lib.genie_compact_tmp_bytes(s) for s in SCRATCH_N] == COMPACT
     assert [lib.genie_locate_tmp_bytes(s) for s in SCRATCH_N] == LOCATE
+
+
+@pytest.mark.parametrize("name", list(INGEST))
+def test_ingest_tmp_bytes(lib, name):
+    size = getattr(lib, f"genie_{name}_tmp_bytes")
+    assert [[size(b, c) for c in INGEST_COUNTS] for b in INGEST_BYTES] == INGEST[name]

@@ -5,6 +5,8 @@ import ctypes as C
 
 import numpy as np
 
+import ingest_calls
+
 LINES, FASTQ = 0, 1
 PARTIAL = 1
 OK, E_INVALID, E_CAPACITY = 0, -1, -10
@@ -75,51 +77,23 @@ def reads_of(offs, bases):
     return [bytes(bases[offs[r]:offs[r + 1]]) for r in range(len(offs) - 1)]
 
 
-def tmp_bytes(lib, nbytes, cap_reads):
-    return int(lib.genie_reads_from_text_tmp_bytes(nbytes, cap_reads))
+CALL = ingest_calls.Call("genie_reads_from_text", [("int64", 1)], 5)
+tmp_bytes = CALL.tmp_bytes
 
 
 def raw_call(lib, text_ptr, nbytes, fmt, flags, table, bases_ptr, cap_bases, offs_ptr, cap_reads, tmp_ptr, tmp_len, stream=None):
     """One call on raw addresses -> (status, out5 list)."""
-    out5 = (C.c_int64 * 5)(-99, -99, -99, -99, -99)
     table = np.ascontiguousarray(table, np.uint8)
-    rc = lib.genie_reads_from_text(C.c_void_p(text_ptr), nbytes, fmt, flags, table.ctypes.data_as(C.c_void_p),
-                                   C.c_void_p(bases_ptr), cap_bases, C.c_void_p(offs_ptr), cap_reads, out5,
-                                   C.c_void_p(tmp_ptr), tmp_len, C.c_void_p(stream) if stream else None)
-    return rc, list(out5)
+    return CALL.raw(lib, text_ptr, nbytes, (fmt, flags, table.ctypes.data_as(C.c_void_p)), bases_ptr, cap_bases, [offs_ptr], cap_reads,
+                    tmp_ptr, tmp_len, stream)
 
 
-def device_parse(lib, text, fmt, flags=0, table=ACGT4, fill=0xA5):
-    """The sizing call, then the full call into buffers of exactly the sizes it reported, on the current torch stream
-    -> (status, out5, read_offsets, bases) as numpy, like parse().  Asserts that the two calls agree on out5 and that
-    the outputs' slack (one int64 past the offsets, 8 bytes past the bases) keeps its fill."""
-    import torch
-    text = bytes(text)
-    t = torch.from_numpy(np.frombuffer(text, np.uint8).copy()).cuda() if text else torch.zeros(1, dtype=torch.uint8, device="cuda")
-    stream = torch.cuda.current_stream().cuda_stream
-    tb = tmp_bytes(lib, len(text), 0)
-    tmp = torch.empty(max(tb, 256), dtype=torch.uint8, device="cuda")
-    rc0, size5 = raw_call(lib, t.data_ptr() if text else 0, len(text), fmt, flags, table, 0, 0, 0, 0, tmp.data_ptr(), tb, stream)
-    n, total = size5[0], size5[1]
-    assert n >= 0 and total >= 0
-    offs = torch.full((n + 2,), -77, dtype=torch.int64, device="cuda")
-    bases = torch.full((total + 8,), fill, dtype=torch.uint8, device="cuda")
-    tb = tmp_bytes(lib, len(text), n)
-    tmp = torch.empty(max(tb, 256), dtype=torch.uint8, device="cuda")
-    rc, out5 = raw_call(lib, t.data_ptr() if text else 0, len(text), fmt, flags, table, bases.data_ptr(), total, offs.data_ptr(), n,
-                        tmp.data_ptr(), tb, stream)
-    assert (rc, out5) == (rc0, size5), "the sizing call and the full call disagree"
-    o, b = offs.cpu().numpy(), bases.cpu().numpy()
-    assert o[n + 1] == -77 and (b[total:] == fill).all(), "written past the outputs"
-    return rc, out5, o[:n + 1], b[:total]
+def device_parse(lib, text, fmt, flags=0, table=ACGT4):
+    """CALL.run with the sizes the sizing call reported -> (status, out5, read_offsets, bases) as numpy, like parse()."""
+    text, table = bytes(text), np.ascontiguousarray(table, np.uint8)
+    rc, out5, b, (o,) = CALL.run(lib, text, (fmt, flags, table.ctypes.data_as(C.c_void_p)), lambda cap: tmp_bytes(lib, len(text), cap))
+    return rc, out5, o[:out5[0] + 1], b[:out5[1]]
 
 
 def same_as_model(lib, text, fmt, flags=0, table=ACGT4):
-    want = parse(text, fmt, flags, table)
-    got = device_parse(lib, text, fmt, flags, table)
-    assert got[0] == want[0], (got[0], want[0], got[1], want[1])
-    assert got[1] == want[1], (got[1], want[1])
-    if want[0] == OK:
-        assert np.array_equal(got[2], want[2]), "offsets"
-        assert np.array_equal(got[3], want[3]), "bases"
-    return want
+    return ingest_calls.same(device_parse(lib, text, fmt, flags, table), parse(text, fmt, flags, table), ("offsets", "bases"))
