@@ -449,6 +449,22 @@ struct ChainAnchors {
 int64_t chain_mems_workspace_bytes(int64_t U, int64_t total_rows, int64_t n_contigs);
 int launch_chain_mems(const genie_index *ix, const ContigTable &ctg, const ChainBatch &b, const CsrRows &out, const ChainAnchors &an,
                       void *d_ws, void *stream);
+// align.inc: every chain of launch_chain_mems aligned; the reads as the batch that found the rows (its workspace is the call's)
+struct AlignBatch {
+    const int64_t *offsets;
+    const int32_t *rows;
+    int64_t U, total_rows;
+    const int32_t *anchor_chain, *anchor_pred;
+    const int64_t *chain_offsets;
+    const int32_t *chains;
+    int64_t cap_chains;
+};
+struct AlignParams {
+    int32_t match, mismatch, gap_open, gap_extend, band, max_indel, end_bonus;
+};
+int64_t align_chains_workspace_bytes(int64_t U, int64_t cap_chains);
+int launch_align_chains(const genie_index *ix, const ContigTable &ctg, const CsrBatch &b, const AlignBatch &ab, const AlignParams &prm,
+                        int32_t *d_aln, int64_t *d_totals, void *stream);
 // min_occ.inc: matching statistics and SMEMs of what occurs at least min_occ times
 int64_t match_stats_min_occ_workspace_bytes(int64_t N, int64_t total_bases, int32_t flags);
 int launch_match_stats_min_occ(const genie_index *ix, int32_t min_occ, const CsrBatch &b, int32_t *d_ms, int32_t *d_lohi,

@@ -1430,6 +1430,7 @@ int launch_locate(const genie_index *ix, const int32_t *d_lohi, int32_t stride, 
 #include "min_occ.inc"
 #include "mems.inc"
 #include "chains.inc"
+#include "align.inc"
 #include "ingest_tiles.inc"
 #include "text_reads.inc"
 #include "fasta_reads.inc"

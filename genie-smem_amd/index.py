@@ -627,20 +627,63 @@ class GenieIndex:
         self._run("genie_chain_mems", *head, _ptr(chains), kept, *tail)
         chains = chains[:kept]
         if by_score and kept:
-            units = torch.arange(U, device=self.device)
-            unit = torch.repeat_interleave(units, chain_offsets[1:] - chain_offsets[:-1])
-            # stable sorts, least significant key first: last ascending, score descending, unit ascending
-            order = torch.argsort(chains[:, 7], stable=True)
-            order = order[torch.argsort(-chains[order, 4].long(), stable=True)]
-            order = order[torch.argsort(unit[order], stable=True)]
-            rank = torch.empty(kept, dtype=torch.int64, device=self.device)
-            rank[order] = torch.arange(kept, device=self.device) - chain_offsets[unit[order]]
-            a_unit = torch.repeat_interleave(units, offsets[1:] - offsets[:-1])
-            ac = anchors[0][:a_unit.numel()]
-            has = ac >= 0
-            ac[has] = rank[chain_offsets[a_unit[has]] + ac[has].long()].to(torch.int32)
-            chains = chains[order]
+            chains = chains[self._chains_by_score(offsets, chain_offsets, chains, anchors[0])]
         return chain_offsets, chains, anchors[0], anchors[1], anchors[2], dropped
+
+    def _chains_by_score(self, offsets, chain_offsets, chains, anchor_chain):
+        """The order of chain_mems' by_score: each unit's chains by (score descending, last ascending); anchor_chain is
+        renumbered in place -> the permutation, which the caller applies to the chain rows (and to what is parallel to them)."""
+        U, kept = offsets.numel() - 1, chains.shape[0]
+        units = torch.arange(U, device=self.device)
+        unit = torch.repeat_interleave(units, chain_offsets[1:] - chain_offsets[:-1])
+        # stable sorts, least significant key first: last ascending, score descending, unit ascending
+        order = torch.argsort(chains[:, 7], stable=True)
+        order = order[torch.argsort(-chains[order, 4].long(), stable=True)]
+        order = order[torch.argsort(unit[order], stable=True)]
+        rank = torch.empty(kept, dtype=torch.int64, device=self.device)
+        rank[order] = torch.arange(kept, device=self.device) - chain_offsets[unit[order]]
+        a_unit = torch.repeat_interleave(units, offsets[1:] - offsets[:-1])
+        ac = anchor_chain[:a_unit.numel()]
+        has = ac >= 0
+        ac[has] = rank[chain_offsets[a_unit[has]] + ac[has].long()].to(torch.int32)
+        return order
+
+    def align_chains(self, reads, offsets, rows, chains_result, contigs=None, both_strands=False, match=1, mismatch=4, gap_open=6,
+                     gap_extend=1, band=32, max_indel=64, end_bonus=5):
+        """Every chain of chain_mems aligned (genie_align_chains): a banded affine gap fill between the chain's members and
+        a banded extension at both ends -> (aln int32[C, 8] = (score, q_begin, q_end, r_begin, r_end, flags, n_used,
+        matched), (aligned, skipped)) on the device, one row per chain row.  reads: (bases, read_offsets) as find_mems took
+        them; offsets / rows: its first two results; chains_result: what chain_mems returned for them with by_score=False
+        (the call walks anchor_chain and anchor_pred as the C call wrote them); contigs and both_strands as in those calls.
+        A match scores `match`, a mismatch -mismatch, a gap of g bases -(gap_open + g gap_extend); gaps are filled inside a
+        band of `band` diagonals around the straight line, a chain with a gap whose sides differ by more than max_indel is
+        skipped (flags 4, the rest 0); an extension that reaches its end of the read within end_bonus of its best local
+        score goes to the end (flags 1: left, 2: right).  r_begin / r_end are 1-based in the concatenation.  Score and end
+        points only: no traceback.  The defaults are this wrapper's; the C call has none."""
+        bases, read_offsets = reads
+        bases, read_offsets, n_reads, total, max_len, flags, strands = self._csr_call(bases, read_offsets, both_strands)
+        offsets = self._as_dev(offsets, torch.int64).reshape(-1)
+        rows = self._as_dev(rows, torch.int32)
+        chain_offsets, chains, anchor_chain, anchor_pred = (self._as_dev(t, d) for t, d in zip(
+            chains_result[:4], (torch.int64, torch.int32, torch.int32, torch.int32)))
+        if rows.dim() != 2 or rows.shape[1] != 4 or chains.dim() != 2 or chains.shape[1] != 8:
+            raise ValueError("rows must be [R, 4] and the chain rows [C, 8]")
+        U, R, kept = offsets.numel() - 1, rows.shape[0], chains.shape[0]
+        if U != strands * n_reads or chain_offsets.numel() != U + 1 or min(anchor_chain.numel(), anchor_pred.numel()) < R:
+            raise ValueError("offsets, chain offsets and anchor arrays must be those of these reads' find_mems and chain_mems")
+        table = (C.c_void_p(0), 0)
+        if contigs is not None:
+            off, table = self._contig_table(contigs)
+        prm = (int(match), int(mismatch), int(gap_open), int(gap_extend), int(band), int(max_indel), int(end_bonus))
+        aln = torch.empty((max(kept, 1), 8), dtype=torch.int32, device=self.device)
+        totals = torch.empty(2, dtype=torch.int64, device=self.device)
+        ws, ws_bytes = self._workspace("genie_align_chains_workspace_bytes", U, kept)
+        none = C.c_void_p(0)
+        self._run("genie_align_chains", *table, flags, _ptr(bases), _ptr(read_offsets), n_reads, total, max_len, _ptr(offsets),
+                  _ptr(rows) if R else none, U, R, _ptr(anchor_chain) if R else none, _ptr(anchor_pred) if R else none,
+                  _ptr(chain_offsets), _ptr(chains) if kept else none, kept, *prm, _ptr(aln) if kept else none, _ptr(totals),
+                  _ptr(ws), ws_bytes)
+        return aln[:kept], tuple(int(x) for x in totals.tolist())
 
     def contig_coords(self, contigs, pos, stride=1):
         """1-based concatenation positions -> int32 [count, 2] = (contig, 1-based offset inside it) on the device

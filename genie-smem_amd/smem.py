@@ -182,6 +182,31 @@ class SMEM:
             mems = self.find_mems_contigs(contigs, reads, minimum_length, both_strands, split_breaks, max_occ)
         return mems, self.chain_mems(mems[0], mems[1], contigs, **chain_options)
 
+    def align_chains(self, reads, offsets, rows, chains_result, contigs=None, both_strands=False, split_breaks=False, **align_options):
+        """Every chain of chain_mems aligned (genie_align_chains) -> (aln int32[C, 8] = (score, q_begin, q_end, r_begin,
+        r_end, flags, n_used, matched), (aligned, skipped)): GenieIndex.align_chains, which documents the options (match,
+        mismatch, gap_open, gap_extend, band, max_indel, end_bonus) and their defaults.  reads as find_mems took them, with
+        the same split_breaks (it decides how strings are encoded, nothing else); chains_result: chain_mems' result with
+        by_score=False."""
+        ix = self.matcher.index(self.lut.lut_size)
+        return ix.align_chains(self._csr_reads(reads, split_breaks), offsets, rows, chains_result, contigs, both_strands, **align_options)
+
+    def find_alignments(self, reads, minimum_length, contigs=None, both_strands=False, split_breaks=False, max_occ=0, align_options=None,
+                        **chain_options):
+        """find_chains followed by align_chains -> (mems, chains, aln): the first two as find_chains returns them, aln int32[C, 8]
+        parallel to the chain rows.  With by_score=True the chains of a unit come by (score descending, last ascending), as
+        chain_mems orders them, and aln follows the same order.  align_options: a dict of align_chains' options."""
+        by_score = bool(chain_options.pop("by_score", False))
+        csr = self._csr_reads(reads, split_breaks)
+        mems, chains = self.find_chains(csr, minimum_length, contigs, both_strands, split_breaks, max_occ, by_score=False, **chain_options)
+        aln, _ = self.align_chains(csr, mems[0], mems[1], chains, contigs, both_strands, split_breaks, **(align_options or {}))
+        if by_score and chains[1].shape[0]:
+            ix = self.matcher.index(self.lut.lut_size)
+            order = ix._chains_by_score(mems[0], chains[0], chains[1], chains[2])
+            chains = (chains[0], chains[1][order]) + tuple(chains[2:])
+            aln = aln[order]
+        return mems, chains, aln
+
     def locate_contigs(self, contigs, rows):
         """SMEM rows (start, end, lo, hi) of any find_smems* call -> (hit_offsets, hits int32[T, 2] = (contig, 1-based
         offset), dropped): GenieIndex.locate_contigs.  The rows stay SMEMs of the concatenation; occurrences that bridge two

@@ -645,6 +645,89 @@ int genie_chain_mems(const genie_index *ix, const int64_t *d_contig_offsets, int
                      int64_t *d_totals,               /* 2, may be NULL: {chains kept, chains not kept} */
                      void *d_workspace, int64_t workspace_bytes, void *stream);
 
+/* Align every chain: a banded affine gap fill between the members of a chain and a banded extension at both ends, where
+ * genie_chain_mems stops.  A chain's score is an estimate from anchor lengths; this call looks at the bases between the anchors
+ * and beyond the first and the last.  Score and end points only: no traceback, no CIGAR.  Everything is integer and
+ * deterministic: the outputs are a function of the inputs alone.
+ * Inputs.
+ *   reads    d_bases, d_read_offsets, N, total_bases, max_len, flags exactly as genie_find_mems* take them.
+ *            GENIE_READS_BOTH_STRANDS gives S = 2 (else 1); unit u = S i + s is read i on strand s, of length L.  On strand 1
+ *            the query Q is the reverse complement, built on the fly: position p is 3 - bases[o + L - 1 - p], and a code > 3
+ *            stays what it is.  GENIE_READS_SPLIT_BREAKS is accepted and changes nothing; any other bit: GENIE_E_INVALID.
+ *   anchors  d_offsets[U + 1], d_rows, total_rows: the MEM rows as genie_find_mems* wrote them; U must equal S N
+ *            (GENIE_E_INVALID).  d_anchor_chain and d_anchor_pred as genie_chain_mems wrote them: both are required.
+ *   chains   d_chain_offsets[U + 1], d_chains, cap_chains as genie_chain_mems wrote them.  The chains with global index
+ *            c < C = min(d_chain_offsets[U], cap_chains) are aligned.
+ *   contigs  d_contig_offsets, n_contigs as genie_chain_mems takes them; NULL with n_contigs == 0: one contig [0, n).  The
+ *            chain's contig is column 6 of its row; its bounds [clo, chi) are two reads of the table.
+ *   T        the reference: the packed 2-bit bases of the image.
+ * Parameters (int32; the call has no defaults): match a in [1, 64]; mismatch b in [0, 64]; gap_open o in [0, 64]; gap_extend e
+ * in [1, 64]; band w in [0, 511]; max_indel in [0, 1023 - 2 w]; end_bonus in [0, 32768].  A gap of g bases costs o + g e.  No
+ * dynamic program is wider than 2 w + max_indel + 1 <= GENIE_ALIGN_MAX_DIAGS diagonals.  Anything outside its range gives
+ * GENIE_E_INVALID.  Scores fit an int32: (2 max_len + max_indel + 2 w + 2) max(a, b, o + e) + 2 end_bonus < 2^30, else
+ * GENIE_E_TOO_LONG.
+ * Base score.  s(x, y) = a if x == y and x <= 3, else -b: a break of the query (a code > 3) is a mismatch against everything.
+ * Banded affine dynamic program.  For strings x[0 .. A), y[0 .. B) and the diagonals d = j - i in [dlo, dhi]: cells outside
+ * the rectangle or outside the band are -infinity; H(0, 0) = 0;
+ *   E(i, j) = max(H(i, j-1) - o - e, E(i, j-1) - e);  F(i, j) = max(H(i-1, j) - o - e, F(i-1, j) - e);
+ *   H(i, j) = max(H(i-1, j-1) + s(x_i, y_j), E(i, j), F(i, j)).
+ * Members.  The members of chain c of unit u are found by starting at row `last` (column 7 of the chain row) and following
+ * d_anchor_pred while d_anchor_chain equals c - d_chain_offsets[u].  Their starts s and reference positions t = pos - 1 rise
+ * strictly; their length is l = e - s.
+ * Trimming, from the last member backwards.  cur = (qs, ts) = (s, t) of the last member, which is used whole.  For each
+ * earlier member j, in descending order: ov = max(0, s_j + l_j - qs, t_j + l_j - ts) and l' = l_j - ov.  If l' <= 0 member j is
+ * skipped.  Otherwise the gap is A = qs - (s_j + l'), B = ts - (t_j + l'), both >= 0.  If |B - A| > max_indel the chain is
+ * SKIPPED: flag bit 4 is set and every other column is 0.  Otherwise a l' + gapfill is added and cur = (s_j, t_j).  gapfill is
+ * H(A, B) of the dynamic program on Q[s_j + l' .. qs) and T[t_j + l' .. ts) with the band [min(0, B - A) - w, max(0, B - A) + w].
+ * Extension of x[0 .. A) against y, where y is cut to its first A + w bases and B is its length, with the band [-w, w]: M is
+ * the largest H over all cells (>= 0, because H(0, 0) = 0), taken at the cell with the smallest i + j and among those the
+ * smallest i.  If row A has a cell inside the band and the rectangle, G = max_j H(A, j), taken at the smallest such j.  If
+ * G + end_bonus >= M the extension is TO THE END: its value is G + end_bonus and it consumes (A, j_G); a tie goes to the end;
+ * with A = 0 this rule gives the value end_bonus.  Otherwise the extension is local: its value is M at (i*, j*).
+ * Where the extensions run.  Right: x = Q[e_last .. L), y = T[t_last + l_last .. chi).  Left: x = Q[0 .. qs) reversed,
+ * y = T[clo .. ts) reversed, with (qs, ts) the start of the first used member.
+ * Output.  d_aln: 8 int32 per chain, 16-byte aligned, parallel to d_chains:
+ *   (score, q_begin, q_end, r_begin, r_end, flags, n_used, matched)
+ * score is the sum of the members' a l', the gap fills and both extensions; [q_begin, q_end) is the aligned part of the
+ * strand-read; r_begin and r_end are 1-based in the concatenation, as in chain rows, r_end one past the last base; flags bit 1:
+ * the left extension went to the read's start, bit 2: the right extension went to the read's end, bit 4: the chain was
+ * skipped; n_used is the number of members not skipped by trimming; matched is the sum of l'.  d_totals (2 int64, may be
+ * NULL): {chains aligned, chains skipped}.  Rows of d_aln at or past C are left untouched.  No atomic decides a value.
+ * Rows, chain rows and anchor arrays that break the assumptions give undefined values, but no load or store outside the
+ * declared sizes and no unbounded loop: the walk is bounded by the unit's row count, positions are clamped to [0, L] and
+ * [clo, chi), a contig or unit index to its table.
+ * Checked before the device check, so on any handle, GENIE_E_INVALID: a null ix, d_offsets or d_chain_offsets; null bases or
+ * read offsets where there are reads; a null d_rows, d_anchor_chain or d_anchor_pred with total_rows > 0; a null d_chains or
+ * d_aln with cap_chains > 0; a negative size; U != S N; a flag or parameter outside its range; d_rows, d_chains or d_aln not
+ * 16-byte, an offsets array, d_totals or the table not 8-byte, an anchor array not 4-byte aligned; a table with n_contigs < 1
+ * or a null table with n_contigs != 0 (GENIE_E_TOO_LONG for n_contigs above 2^31 - 2).  Then GENIE_E_TOO_LONG as above.  Then,
+ * for U > 0, a d_workspace that is null, not 256-byte aligned or smaller than genie_align_chains_workspace_bytes(U, cap_chains)
+ * gives GENIE_E_CAPACITY.  Then GENIE_E_NO_DEVICE.  The read offsets and the row offsets are checked on the device as
+ * genie_find_mems* and genie_chain_mems check them (GENIE_E_INVALID), at the cost of the call's only synchronisation of
+ * `stream`.  U == 0 or C == 0 writes zero totals and nothing else.
+ * The workspace function returns GENIE_E_INVALID for negative arguments, is a multiple of 256 and monotone in both: 4 bytes
+ * per chain (the chain's unit), 0 bytes per unit, and 256 for the verdict of the offset checks.
+ * Kernels: one wave per chain, lanes over the band's diagonals and rows over the query's bases, the row before in LDS (8 bytes
+ * per diagonal), bands of more than 64 diagonals in chunks of 64.  Cost: per gap and per end, rows x ceil(diagonals / 64)
+ * steps; a chain is not split, so one chain with very long gaps runs on one wave. */
+#define GENIE_ALIGN_MAX_DIAGS 1024
+int64_t genie_align_chains_workspace_bytes(int64_t U, int64_t cap_chains);
+int genie_align_chains(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs, int32_t flags,
+                       const uint8_t *d_bases, const int64_t *d_read_offsets, int64_t N, int64_t total_bases, int64_t max_len,
+                       const int64_t *d_offsets,        /* U + 1 */
+                       const int32_t *d_rows,           /* 4 * total_rows, 16-byte aligned */
+                       int64_t U, int64_t total_rows,
+                       const int32_t *d_anchor_chain,   /* total_rows */
+                       const int32_t *d_anchor_pred,    /* total_rows */
+                       const int64_t *d_chain_offsets,  /* U + 1 */
+                       const int32_t *d_chains,         /* 8 * cap_chains, 16-byte aligned */
+                       int64_t cap_chains,
+                       int32_t match, int32_t mismatch, int32_t gap_open, int32_t gap_extend, int32_t band, int32_t max_indel,
+                       int32_t end_bonus,
+                       int32_t *d_aln,                  /* 8 * cap_chains, 16-byte aligned */
+                       int64_t *d_totals,               /* 2, may be NULL: {chains aligned, chains skipped} */
+                       void *d_workspace, int64_t workspace_bytes, void *stream);
+
 /* Matching statistics and SMEMs that are EXACT WITH RESPECT TO THE SEQUENCE SET.  genie_match_stats and the SMEM calls on a
  * reference of several sequences answer for the concatenation; genie_locate_contigs then drops the occurrences that bridge
  * two sequences, and with them seeds.  Contigs ACGT | TTGA and the read CGTT: the concatenation holds CGTT once, across the
