@@ -100,9 +100,13 @@ struct AlnEnd {
 // The banded affine program on x[0 .. A), y[0 .. B) over the diagonals [dlo, dhi], dlo <= 0 <= dhi, at most kAlnDiags of them:
 // x_i is position q0 + dir i of the strand-read, y_j base t0 + dir j of the reference.  kExt: the extension's rule, else
 // H(A, B).  A >= 1.  st: the wave's row, kAlnDiags (H, vertical); rw: its kAlnRefBytes reference bases.
-template <bool kExt>
+// kTrace (cigars.inc): every cell of the rows 1 .. min(A, B - dlo) also leaves four bits in dirs, where it came from: bits 0-1 the
+// source of H, taken in the canonical order (0 the diagonal on a match, 1 the diagonal otherwise, 2 F, 3 E), bit 2: F(i, j) is
+// F(i-1, j) - e, bit 3: E(i, j) is E(i, j-1) - e.  Row i is ceil(D / 64) * 32 bytes, two diagonals to a byte, the even one low.
+template <bool kExt, bool kTrace = false>
 __device__ __forceinline__ AlnEnd aln_dp(const DevIndex &ix, const AlnRead &rd, int q0, int t0, int dir, int A, int B, int dlo, int dhi,
-                                         const AlignParams &p, int lane, int2 *__restrict__ st, uint8_t *__restrict__ rw)
+                                         const AlignParams &p, int lane, int2 *__restrict__ st, uint8_t *__restrict__ rw,
+                                         uint8_t *__restrict__ dirs = nullptr)
 {
     const int D = dhi - dlo + 1 < kAlnDiags ? dhi - dlo + 1 : kAlnDiags;
     const int nchunks = (D + kWave - 1) / kWave;
@@ -143,6 +147,7 @@ __device__ __forceinline__ AlnEnd aln_dp(const DevIndex &ix, const AlnRead &rd, 
             const uint32_t x = (uint32_t)__builtin_amdgcn_readlane((int)xq, k);
             const int first_idx = -i - dlo > 0 ? -i - dlo : 0, last_idx = D - 1 < B - i - dlo ? D - 1 : B - i - dlo;
             int carry = kAlnNeg;                                     // the largest x_k of the chunks before
+            [[maybe_unused]] int ecarry = kAlnNeg;                   // kTrace: E of the last lane of the chunk before
             for (int c = first_idx / kWave; c <= last_idx / kWave; c++) {
                 const int idx = c * kWave + lane, d = dlo + idx, j = i + d;
                 const bool inb = idx < D, valid = inb && j >= 0 && j <= B;
@@ -177,6 +182,15 @@ __device__ __forceinline__ AlnEnd aln_dp(const DevIndex &ix, const AlnRead &rd, 
                     v = kAlnNeg;
                 }
                 if (inb) st[idx] = make_int2(h, v);
+                if constexpr (kTrace) {
+                    int ep = __shfl_up(g, 1, kWave);                 // E(i, j - 1)
+                    ep = lane == 0 ? ecarry : ep;
+                    ecarry = __builtin_amdgcn_readlane(g, kWave - 1);
+                    const int src = (j >= 1 && h == diag) ? ((x == y && x <= 3u) ? 0 : 1) : (h == v ? 2 : 3);
+                    const int nib = src | (up.x - oe > up.y - e ? 0 : 4) | (g == ep - e ? 8 : 0);
+                    const int odd = __shfl_down(nib, 1, kWave);
+                    if (!(lane & 1)) dirs[(long long)(i - 1) * (nchunks * 32) + c * 32 + (lane >> 1)] = (uint8_t)(nib | (odd << 4));
+                }
                 const int top = __builtin_amdgcn_readlane(incl, kWave - 1);
                 carry = top > carry ? top : carry;
                 if (kExt) {
@@ -369,6 +383,8 @@ __global__ void __launch_bounds__(kScanBlock) align_totals_kernel(const long lon
 }
 
 }  // namespace
+
+#include "cigars.inc"
 
 int64_t align_chains_workspace_bytes(int64_t U, int64_t cap_chains)
 {

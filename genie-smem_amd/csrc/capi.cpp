@@ -642,6 +642,36 @@ int64_t genie_align_chains_workspace_bytes(int64_t U, int64_t cap_chains)
     return align_chains_workspace_bytes(U, cap_chains);
 }
 
+// The argument checks genie_align_chains and genie_chain_cigars share, in the header's order up to GENIE_E_TOO_LONG
+static int align_args(const genie_index *ix, const CsrBatch &b, const int64_t *d_contig_offsets, int64_t n_contigs, const AlignBatch &ab,
+                      const AlignParams &p, const int32_t *d_aln, const int64_t *d_totals)
+{
+    if (!ix || bad_batch(b, kReadFlags) || !ab.offsets || !ab.chain_offsets) return GENIE_E_INVALID;
+    if (ab.U < 0 || ab.total_rows < 0 || ab.cap_chains < 0 || b.ws_bytes < 0 || ab.U != b.strand_reads()) return GENIE_E_INVALID;
+    if ((ab.total_rows > 0 && (!ab.rows || !ab.anchor_chain || !ab.anchor_pred)) || (ab.cap_chains > 0 && (!ab.chains || !d_aln)))
+        return GENIE_E_INVALID;
+    if (p.match < 1 || p.match > 64 || p.mismatch < 0 || p.mismatch > 64 || p.gap_open < 0 || p.gap_open > 64 || p.gap_extend < 1 ||
+        p.gap_extend > 64 || p.band < 0 || p.band > 511 || p.max_indel < 0 || p.max_indel > GENIE_ALIGN_MAX_DIAGS - 1 - 2 * p.band ||
+        p.end_bonus < 0 || p.end_bonus > 32768)
+        return GENIE_E_INVALID;
+    if (misaligned(b.read_offsets, 7) || misaligned(ab.offsets, 7) || misaligned(ab.rows, 15) || misaligned(ab.chain_offsets, 7) ||
+        misaligned(ab.chains, 15) || misaligned(ab.anchor_chain, 3) || misaligned(ab.anchor_pred, 3) || misaligned(d_aln, 15) ||
+        misaligned(d_totals, 7))
+        return GENIE_E_INVALID;
+    // the table is optional: null with n_contigs == 0, or a table as every contig call takes it
+    if (!d_contig_offsets && n_contigs != 0) return GENIE_E_INVALID;
+    if (d_contig_offsets)
+        if (int rc = contig_args(d_contig_offsets, n_contigs)) return rc;
+    return GENIE_OK;
+}
+
+// every score fits an int with room to spare: the kernels' minus infinity is -2^30
+static bool align_too_long(int64_t max_len, const AlignParams &p)
+{
+    const int64_t worst = std::max<int64_t>(std::max(p.match, p.mismatch), p.gap_open + p.gap_extend);
+    return (2 * max_len + p.max_indel + 2 * p.band + 2) * worst + 2 * (int64_t)p.end_bonus >= ((int64_t)1 << 30);
+}
+
 int genie_align_chains(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs, int32_t flags, const uint8_t *d_bases,
                        const int64_t *d_read_offsets, int64_t N, int64_t total_bases, int64_t max_len, const int64_t *d_offsets,
                        const int32_t *d_rows, int64_t U, int64_t total_rows, const int32_t *d_anchor_chain, const int32_t *d_anchor_pred,
@@ -650,30 +680,49 @@ int genie_align_chains(const genie_index *ix, const int64_t *d_contig_offsets, i
                        int64_t *d_totals, void *d_workspace, int64_t workspace_bytes, void *stream)
 {
     const CsrBatch b{flags, d_bases, d_read_offsets, N, total_bases, max_len, nullptr, d_workspace, workspace_bytes};
+    const AlignBatch ab{d_offsets, d_rows, U, total_rows, d_anchor_chain, d_anchor_pred, d_chain_offsets, d_chains, cap_chains};
+    const AlignParams prm{match, mismatch, gap_open, gap_extend, band, max_indel, end_bonus};
     // argument checks first: they need no device image
-    if (!ix || bad_batch(b, kReadFlags) || !d_offsets || !d_chain_offsets) return GENIE_E_INVALID;
-    if (U < 0 || total_rows < 0 || cap_chains < 0 || workspace_bytes < 0 || U != b.strand_reads()) return GENIE_E_INVALID;
-    if ((total_rows > 0 && (!d_rows || !d_anchor_chain || !d_anchor_pred)) || (cap_chains > 0 && (!d_chains || !d_aln))) return GENIE_E_INVALID;
-    if (match < 1 || match > 64 || mismatch < 0 || mismatch > 64 || gap_open < 0 || gap_open > 64 || gap_extend < 1 || gap_extend > 64 ||
-        band < 0 || band > 511 || max_indel < 0 || max_indel > GENIE_ALIGN_MAX_DIAGS - 1 - 2 * band || end_bonus < 0 || end_bonus > 32768)
-        return GENIE_E_INVALID;
-    if (misaligned(d_read_offsets, 7) || misaligned(d_offsets, 7) || misaligned(d_rows, 15) || misaligned(d_chain_offsets, 7) ||
-        misaligned(d_chains, 15) || misaligned(d_anchor_chain, 3) || misaligned(d_anchor_pred, 3) || misaligned(d_aln, 15) ||
-        misaligned(d_totals, 7))
-        return GENIE_E_INVALID;
-    // the table is optional: null with n_contigs == 0, or a table as every contig call takes it
-    if (!d_contig_offsets && n_contigs != 0) return GENIE_E_INVALID;
-    if (d_contig_offsets)
-        if (int rc = contig_args(d_contig_offsets, n_contigs)) return rc;
-    // every score fits an int with room to spare: the kernels' minus infinity is -2^30
-    const int64_t worst = std::max<int64_t>(std::max(match, mismatch), gap_open + gap_extend);
-    if ((2 * max_len + max_indel + 2 * band + 2) * worst + 2 * (int64_t)end_bonus >= ((int64_t)1 << 30)) return GENIE_E_TOO_LONG;
+    if (int rc = align_args(ix, b, d_contig_offsets, n_contigs, ab, prm, d_aln, d_totals)) return rc;
+    if (align_too_long(max_len, prm)) return GENIE_E_TOO_LONG;
     if (U > 0 && (!d_workspace || misaligned(d_workspace, 255) || workspace_bytes < align_chains_workspace_bytes(U, cap_chains)))
         return GENIE_E_CAPACITY;
     if (int rc = ready(ix)) return rc;
+    return launch_align_chains(ix, {d_contig_offsets, n_contigs}, b, ab, prm, d_aln, d_totals, stream);
+}
+
+int64_t genie_chain_cigars_workspace_bytes(int64_t U, int64_t cap_chains, int64_t n_sel, int64_t dir_bytes)
+{
+    if (U < 0 || cap_chains < 0 || n_sel < 0 || dir_bytes < 0) return (int64_t)GENIE_E_INVALID;
+    return chain_cigars_workspace_bytes(U, cap_chains, n_sel, dir_bytes);
+}
+
+int genie_chain_cigars(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs, int32_t flags, const uint8_t *d_bases,
+                       const int64_t *d_read_offsets, int64_t N, int64_t total_bases, int64_t max_len, const int64_t *d_offsets,
+                       const int32_t *d_rows, int64_t U, int64_t total_rows, const int32_t *d_anchor_chain, const int32_t *d_anchor_pred,
+                       const int64_t *d_chain_offsets, const int32_t *d_chains, int64_t cap_chains, int32_t match, int32_t mismatch,
+                       int32_t gap_open, int32_t gap_extend, int32_t band, int32_t max_indel, int32_t end_bonus, const int32_t *d_aln,
+                       const int64_t *d_sel, int64_t n_sel, int64_t *d_cigar_offsets, uint32_t *d_cigar, int64_t cap_ops, int32_t *d_info,
+                       int64_t *d_dir_need, int64_t *d_totals, int64_t dir_bytes, void *d_workspace, int64_t workspace_bytes,
+                       void *stream)
+{
+    const CsrBatch b{flags, d_bases, d_read_offsets, N, total_bases, max_len, nullptr, d_workspace, workspace_bytes};
     const AlignBatch ab{d_offsets, d_rows, U, total_rows, d_anchor_chain, d_anchor_pred, d_chain_offsets, d_chains, cap_chains};
-    return launch_align_chains(ix, {d_contig_offsets, n_contigs}, b, ab, {match, mismatch, gap_open, gap_extend, band, max_indel, end_bonus},
-                               d_aln, d_totals, stream);
+    const AlignParams prm{match, mismatch, gap_open, gap_extend, band, max_indel, end_bonus};
+    // argument checks first: they need no device image
+    if (int rc = align_args(ix, b, d_contig_offsets, n_contigs, ab, prm, d_aln, d_totals)) return rc;
+    if (!d_aln || !d_cigar_offsets || !d_info || n_sel < 0 || cap_ops < 0 || dir_bytes < 0) return GENIE_E_INVALID;
+    if (misaligned(d_sel, 7) || misaligned(d_cigar_offsets, 7) || misaligned(d_info, 15) || misaligned(d_cigar, 3) ||
+        misaligned(d_dir_need, 7))
+        return GENIE_E_INVALID;
+    if (align_too_long(max_len, prm)) return GENIE_E_TOO_LONG;
+    const int64_t sel = d_sel ? n_sel : cap_chains;
+    if ((U > 0 || sel > 0) && (!d_workspace || misaligned(d_workspace, 255) ||
+                               workspace_bytes < chain_cigars_workspace_bytes(U, cap_chains, sel, dir_bytes)))
+        return GENIE_E_CAPACITY;
+    if (int rc = ready(ix)) return rc;
+    return launch_chain_cigars(ix, {d_contig_offsets, n_contigs}, b, ab, prm, d_aln,
+                               {d_sel, n_sel, d_cigar_offsets, d_cigar, cap_ops, d_info, d_dir_need, d_totals, dir_bytes}, stream);
 }
 
 int genie_contig_coords(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs, const int32_t *d_pos, int32_t stride,

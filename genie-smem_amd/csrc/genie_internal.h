@@ -465,6 +465,20 @@ struct AlignParams {
 int64_t align_chains_workspace_bytes(int64_t U, int64_t cap_chains);
 int launch_align_chains(const genie_index *ix, const ContigTable &ctg, const CsrBatch &b, const AlignBatch &ab, const AlignParams &prm,
                         int32_t *d_aln, int64_t *d_totals, void *stream);
+// cigars.inc: the edit script of selected chains of launch_align_chains; sel may be null: the chains 0 .. C - 1
+struct CigarOut {
+    const int64_t *sel;
+    int64_t n_sel;
+    int64_t *offsets;
+    uint32_t *cigar;
+    int64_t cap_ops;
+    int32_t *info;
+    int64_t *dir_need, *totals;
+    int64_t dir_bytes;
+};
+int64_t chain_cigars_workspace_bytes(int64_t U, int64_t cap_chains, int64_t n_sel, int64_t dir_bytes);
+int launch_chain_cigars(const genie_index *ix, const ContigTable &ctg, const CsrBatch &b, const AlignBatch &ab, const AlignParams &prm,
+                        const int32_t *d_aln, const CigarOut &out, void *stream);
 // min_occ.inc: matching statistics and SMEMs of what occurs at least min_occ times
 int64_t match_stats_min_occ_workspace_bytes(int64_t N, int64_t total_bases, int32_t flags);
 int launch_match_stats_min_occ(const genie_index *ix, int32_t min_occ, const CsrBatch &b, int32_t *d_ms, int32_t *d_lohi,

@@ -22,6 +22,19 @@ def _stream(device):
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
+_CIGAR_LETTERS = {1: "I", 2: "D", 4: "S", 7: "=", 8: "X"}
+
+
+def cigar_strings(cigar_offsets, cigar):
+    """The CSR of chain_cigars as text, one string per selected chain, such as "3S20=1X5=2D40=" ("" for a chain without ops).
+    A host helper: tensors are copied to the host first."""
+    off = cigar_offsets.cpu().numpy() if hasattr(cigar_offsets, "cpu") else np.asarray(cigar_offsets)
+    if hasattr(cigar, "cpu"):
+        cigar = cigar.view(torch.int32).cpu().numpy() if cigar.dtype == torch.uint32 else cigar.cpu().numpy()
+    ops = np.asarray(cigar).astype(np.int64) & 0xFFFFFFFF
+    return ["".join(f"{int(v) >> 4}{_CIGAR_LETTERS[int(v) & 15]}" for v in ops[int(off[k]):int(off[k + 1])]) for k in range(len(off) - 1)]
+
+
 class GenieIndex:
     def __init__(self):
         self._h = C.c_void_p(0)
@@ -684,6 +697,66 @@ class GenieIndex:
                   _ptr(chain_offsets), _ptr(chains) if kept else none, kept, *prm, _ptr(aln) if kept else none, _ptr(totals),
                   _ptr(ws), ws_bytes)
         return aln[:kept], tuple(int(x) for x in totals.tolist())
+
+    def chain_cigars(self, reads, offsets, rows, chains_result, aln, select=None, contigs=None, both_strands=False, match=1, mismatch=4,
+                     gap_open=6, gap_extend=1, band=32, max_indel=64, end_bonus=5, ops_hint=None, dir_bytes_hint=None):
+        """The CIGAR of selected chains (genie_chain_cigars): the traceback of align_chains -> (cigar_offsets int64[n_sel+1],
+        cigar uint32[ops], info int32[n_sel, 8] = (chain, flags, n_ops, nm, n_eq, n_x, ins_bases, del_bases)) on the device;
+        cigar_strings turns the first two into text.  reads, offsets, rows, chains_result, contigs, both_strands and the
+        scoring options exactly as align_chains took them; aln: its first result.  select: global chain indices (rows of
+        chains / aln), any order, repeats allowed, None: every chain.  An op is SAM's len << 4 | op with I = 1, D = 2, S = 4,
+        '=' = 7, X = 8, in strand-read order, the clipped ends as S.  flags 4: the chain was skipped by align_chains, 16: an
+        index outside the chains (or an aln row that is not this chain's); such a chain has no ops.  ops_hint and
+        dir_bytes_hint size the first call (ops in all; bytes for the directions of the dynamic programs, four bits per
+        cell); when either is too small the call is made again with room for all."""
+        bases, read_offsets = reads
+        bases, read_offsets, n_reads, total, max_len, flags, strands = self._csr_call(bases, read_offsets, both_strands)
+        offsets = self._as_dev(offsets, torch.int64).reshape(-1)
+        rows = self._as_dev(rows, torch.int32)
+        chain_offsets, chains, anchor_chain, anchor_pred = (self._as_dev(t, d) for t, d in zip(
+            chains_result[:4], (torch.int64, torch.int32, torch.int32, torch.int32)))
+        aln = self._as_dev(aln, torch.int32)
+        if rows.dim() != 2 or rows.shape[1] != 4 or chains.dim() != 2 or chains.shape[1] != 8 or aln.shape != chains.shape:
+            raise ValueError("rows must be [R, 4], the chain rows [C, 8] and aln parallel to them")
+        U, R, kept = offsets.numel() - 1, rows.shape[0], chains.shape[0]
+        if U != strands * n_reads or chain_offsets.numel() != U + 1 or min(anchor_chain.numel(), anchor_pred.numel()) < R:
+            raise ValueError("offsets, chain offsets and anchor arrays must be those of these reads' find_mems and chain_mems")
+        none = C.c_void_p(0)
+        sel = None
+        if select is not None:
+            sel = self._as_dev(select, torch.int64).reshape(-1)
+            if sel.numel() == 0:
+                sel = torch.zeros(1, dtype=torch.int64, device=self.device)[:0]
+        n_sel = kept if sel is None else sel.numel()
+        # an empty selection still has to be told from `every chain`: any aligned non-null address, it is never read
+        sel_ptr = none if sel is None else C.c_void_p(sel.data_ptr() if n_sel else 8)
+        table = (C.c_void_p(0), 0)
+        if contigs is not None:
+            off, table = self._contig_table(contigs)
+        prm = (int(match), int(mismatch), int(gap_open), int(gap_extend), int(band), int(max_indel), int(end_bonus))
+        # aln and chains may be empty tensors: the call wants an address for d_aln whatever cap_chains is
+        aln_buf = aln if kept else torch.zeros((1, 8), dtype=torch.int32, device=self.device)
+        cigar_offsets = torch.empty(n_sel + 1, dtype=torch.int64, device=self.device)
+        info = torch.empty((max(n_sel, 1), 8), dtype=torch.int32, device=self.device)
+        totals = torch.empty(3, dtype=torch.int64, device=self.device)
+        cap_ops = int(ops_hint) if ops_hint else 8 * n_sel
+        dir_bytes = int(dir_bytes_hint) if dir_bytes_hint is not None else min(n_sel << 14, 1 << 28)
+        while True:
+            cigar = torch.empty(max(cap_ops, 1), dtype=torch.int32, device=self.device)
+            ws, ws_bytes = self._workspace("genie_chain_cigars_workspace_bytes", U, kept, n_sel if sel is not None else kept, dir_bytes)
+            self._run("genie_chain_cigars", *table, flags, _ptr(bases), _ptr(read_offsets), n_reads, total, max_len, _ptr(offsets),
+                      _ptr(rows) if R else none, U, R, _ptr(anchor_chain) if R else none, _ptr(anchor_pred) if R else none,
+                      _ptr(chain_offsets), _ptr(chains) if kept else none, kept, *prm, _ptr(aln_buf), sel_ptr, n_sel,
+                      _ptr(cigar_offsets), _ptr(cigar) if cap_ops else none, cap_ops, _ptr(info), none, _ptr(totals), dir_bytes,
+                      _ptr(ws), ws_bytes)
+            need = int(totals[2].item())
+            if need > dir_bytes:                                     # some chain found no room for its directions
+                dir_bytes = need
+                continue
+            ops = int(cigar_offsets[n_sel].item())
+            if ops <= cap_ops:
+                return cigar_offsets, cigar[:ops].view(torch.uint32), info[:n_sel]
+            cap_ops = ops
 
     def contig_coords(self, contigs, pos, stride=1):
         """1-based concatenation positions -> int32 [count, 2] = (contig, 1-based offset inside it) on the device

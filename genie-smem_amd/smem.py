@@ -207,6 +207,67 @@ class SMEM:
             aln = aln[order]
         return mems, chains, aln
 
+    def chain_cigars(self, reads, offsets, rows, chains_result, aln, select=None, contigs=None, both_strands=False, split_breaks=False,
+                     **cigar_options):
+        """The CIGAR of selected chains (genie_chain_cigars) -> (cigar_offsets, cigar uint32[ops], info int32[n_sel, 8] =
+        (chain, flags, n_ops, nm, n_eq, n_x, ins_bases, del_bases)): GenieIndex.chain_cigars, which documents `select`, the
+        options (align_chains' scoring options, which must be those aln was made with, ops_hint, dir_bytes_hint) and their
+        defaults.  reads, split_breaks and chains_result as align_chains took them; aln: its first result."""
+        ix = self.matcher.index(self.lut.lut_size)
+        return ix.chain_cigars(self._csr_reads(reads, split_breaks), offsets, rows, chains_result, aln, select, contigs, both_strands,
+                               **cigar_options)
+
+    def map_reads(self, reads, minimum_length, contigs=None, both_strands=True, split_breaks=False, max_occ=0, align_options=None,
+                  **chain_options):
+        """One mapping per read: find_alignments, then per read the non-skipped chain of the highest alignment score over its
+        strand-reads (a tie goes to the smaller global chain index), then chain_cigars on that selection -> (hits int32[N, 6] =
+        (chain, strand, contig, offset, score, nm), cigar_offsets int64[N+1], cigar uint32[ops]) on the device.  chain is the
+        global chain index (the row of find_alignments' chains and aln), strand 1 the reverse complement, offset the 1-based
+        start of the alignment inside its contig (in the concatenation, and contig 0, without `contigs`); the CIGAR is in
+        strand-read order, as SAM has it.  A read without a chain gets (-1, 0, -1, 0, 0, 0) and an empty CIGAR."""
+        import torch
+        ix = self.matcher.index(self.lut.lut_size)
+        csr = self._csr_reads(reads, split_breaks)
+        opts = dict(align_options or {})
+        mems, chains, aln = self.find_alignments(csr, minimum_length, contigs, both_strands, split_breaks, max_occ, opts, by_score=False,
+                                                 **chain_options)
+        S = 2 if both_strands else 1
+        U, kept = mems[0].numel() - 1, chains[1].shape[0]
+        n_reads = U // S
+        dev = aln.device
+        hits = torch.zeros((n_reads, 6), dtype=torch.int32, device=dev)
+        hits[:, 0] = -1
+        hits[:, 2] = -1
+        if kept == 0 or n_reads == 0:
+            return hits, torch.zeros(n_reads + 1, dtype=torch.int64, device=dev), torch.zeros(0, dtype=torch.int32, device=dev).view(torch.uint32)
+        unit = torch.repeat_interleave(torch.arange(U, device=dev), chains[0][1:] - chains[0][:-1])
+        read = unit // S
+        live = (aln[:, 5] & 4) == 0
+        # the best score of every read, then the smallest chain index that has it
+        score = torch.where(live, aln[:, 0].long(), torch.full((kept,), -(1 << 40), dtype=torch.int64, device=dev))
+        best = torch.full((n_reads,), -(1 << 40), dtype=torch.int64, device=dev).scatter_reduce(0, read, score, "amax")
+        index = torch.arange(kept, device=dev)
+        cand = torch.where(live & (score == best[read]), index, torch.full_like(index, kept))
+        pick = torch.full((n_reads,), kept, dtype=torch.int64, device=dev).scatter_reduce(0, read, cand, "amin")
+        has = pick < kept
+        sel = pick[has]
+        offs, cigar, info = ix.chain_cigars(csr, mems[0], mems[1], chains, aln, sel, contigs, both_strands, **opts)
+        got = aln[sel]
+        hits[has, 0] = sel.to(torch.int32)
+        hits[has, 1] = (unit[sel] % S).to(torch.int32)
+        if contigs is not None:
+            hits[has, 2:4] = ix.contig_coords(contigs, got[:, 3].contiguous())
+        else:
+            hits[has, 2] = 0
+            hits[has, 3] = got[:, 3]
+        hits[has, 4] = got[:, 0]
+        hits[has, 5] = info[:, 3]
+        counts = torch.zeros(n_reads, dtype=torch.int64, device=dev)
+        counts[has] = offs[1:] - offs[:-1]
+        cigar_offsets = torch.zeros(n_reads + 1, dtype=torch.int64, device=dev)
+        cigar_offsets[1:] = torch.cumsum(counts, 0)
+        return hits, cigar_offsets, cigar
+
     def locate_contigs(self, contigs, rows):
         """SMEM rows (start, end, lo, hi) of any find_smems* call -> (hit_offsets, hits int32[T, 2] = (contig, 1-based
         offset), dropped): GenieIndex.locate_contigs.  The rows stay SMEMs of the concatenation; occurrences that bridge two

@@ -728,6 +728,96 @@ int genie_align_chains(const genie_index *ix, const int64_t *d_contig_offsets, i
                        int64_t *d_totals,               /* 2, may be NULL: {chains aligned, chains skipped} */
                        void *d_workspace, int64_t workspace_bytes, void *stream);
 
+/* The CIGAR of selected chains: the traceback of genie_align_chains, where that call stops at score and end points.  The call
+ * takes everything genie_align_chains takes, with the same parameters, ranges and checks, the rows d_aln as that call wrote
+ * them, and a selection.  Everything is integer and deterministic: the outputs are a function of the inputs alone.
+ * Selection.  d_sel: n_sel int64 global chain indices, 8-byte aligned.  NULL: the chains 0 .. C - 1 in order, C =
+ * min(d_chain_offsets[U], cap_chains); n_sel is then ignored and taken as C (the outputs hold C entries, the workspace is that of
+ * n_sel = cap_chains).  An index may occur more than once: its results are repeated.  An index outside [0, C) gives a flagged,
+ * empty result (bit 16), not an error.
+ * Pieces.  The alignment of a chain is cut into pieces in forward strand-read order: the left extension; then, alternately, a
+ * used member's l' bases and the gap fill behind it; the last member whole; the right extension.  Members, trimming, l', the
+ * gaps (A, B) and their bands are exactly those of genie_align_chains.  A member is l' ops '='.  A gap fill is the canonical
+ * path (below) of the same program from (A, B) back to (0, 0).  An extension is the canonical path of the GLOBAL program
+ * between (0, 0) and the cell (i*, j*) the extension consumed, on the rectangle [0, i*] x [0, j*] with the band [-w, w]; the cell
+ * is read off d_aln:
+ *   right: i* = q_end - e_last,  j* = (r_end - 1) - (t_last + l_last);
+ *   left:  i* = qs - q_begin,    j* = ts - (r_begin - 1), on the reversed strings.
+ * The program is causal, so H(i*, j*) of this rectangle is the value the extension found.  i* = 0 forces j* = 0 and gives no
+ * ops.  An end cell outside the band or outside the extension's rectangle [0, A] x [0, B], or with i* = 0 < j*, flags the chain
+ * (bit 16, no ops).  Rows of d_aln that genie_align_chains did not write give undefined values but, like every other input
+ * here, no access outside the declared sizes and no unbounded loop: the end cells are checked before they are used, and a
+ * trace takes at most i + j steps whatever it reads.
+ * The canonical path is defined on the values H / E / F above, from the piece's end cell backwards.
+ *   State H at (i, j): stop at (0, 0).  Otherwise the first that holds: (1) i, j >= 1, (i-1, j-1) inside band and rectangle and
+ *   H(i, j) == H(i-1, j-1) + s(x_i, y_j): emit '=' if x_i == y_j and x_i <= 3, else 'X', go to H at (i-1, j-1); (2) H(i, j) ==
+ *   F(i, j): go to state F; (3) else go to state E.
+ *   State F (consumes query): emit 'I' and move to (i-1, j); stay in F iff F(i, j) == F(i-1, j) - e, with (i, j) the cell before
+ *   the move; otherwise the state is H.  A tie between opening and extending goes to extending.
+ *   State E (consumes reference): emit 'D' and move to (i, j-1); stay in E iff E(i, j) == E(i, j-1) - e; otherwise H.
+ * The order is diagonal, F, E, and extend before open: the order in which the kernel's recurrence compares.  A path from a
+ * finite cell only meets finite cells.  The closed forms of genie_align_chains are this path: A = 0 or B = 0 is one 'D' or one
+ * 'I' of A + B bases, A = B = 0 is nothing.  The ops of a piece are emitted from its end cell backwards and reversed; the left
+ * extension runs on reversed strings, so its ops come out in strand-read order as they are emitted.
+ * Ops.  An op is SAM's uint32 len << 4 | op with I = 1, D = 2, S = 4, '=' = 7, X = 8 (len < 2^28).  Neighbouring equal ops
+ * are merged across piece borders.  A leading S of q_begin bases and a trailing S of L - q_end bases are written when non-zero.
+ * The ops are in strand-read order: on strand 1 that of the reverse complement, SAM's convention.  A query code above 3 is
+ * always 'X'.
+ * Outputs, all in caller buffers:
+ *   d_cigar_offsets  n_sel + 1 int64, 8-byte aligned; [n_sel] holds the true total even when cap_ops is smaller
+ *   d_cigar          cap_ops uint32, 4-byte aligned; NULL is the sizing call.  Ops past cap_ops are dropped.
+ *   d_info           8 int32 per selected chain, 16-byte aligned:
+ *                    (chain, flags, n_ops, nm, n_eq, n_x, ins_bases, del_bases), nm = n_x + ins_bases + del_bases.  Flag bit
+ *                    4: the chain was skipped by genie_align_chains; bit 8: no room for its directions; bit 16: bad index or
+ *                    end cell.  Any flag set means n_ops = 0 and the other columns 0.
+ *   d_dir_need       n_sel int64, 8-byte aligned, may be NULL: the direction bytes each selected chain needs
+ *   d_totals         3 int64, 8-byte aligned, may be NULL: {chains written, chains flagged, direction bytes needed in all}
+ * Outputs past n_sel and past the true op total are left untouched.  No atomic decides a value.
+ * Direction storage.  Every cell of a piece with A >= 1 and B >= 1 keeps four bits: bits 0-1 the source of H (0 diagonal and
+ * '=', 1 diagonal and 'X', 2 F, 3 E), bit 2: F(i, j) == F(i-1, j) - e, bit 3: E(i, j) == E(i, j-1) - e.  A piece of A rows on D
+ * diagonals takes A * ceil(D / 64) * 32 bytes: row i - 1, two diagonals to a byte, the even one in the low half.  Pieces in
+ * closed form take nothing.  The need of a chain is the sum over its pieces, a function of its geometry alone (members, gaps
+ * and end points); a flagged chain needs 0.  The storage is dir_bytes of the workspace, the caller's budget: selected chain k
+ * gets room iff the running sum of the needs through k is at most dir_bytes; the others get bit 8, and d_totals[2] tells what to
+ * come back with.
+ * Checks: all those of genie_align_chains up to its alignment and table checks, in that order (d_aln is required whatever
+ * cap_chains is, and is read only); then GENIE_E_INVALID for a null d_aln, d_cigar_offsets or d_info, a negative n_sel, cap_ops
+ * or dir_bytes, a d_sel, d_cigar_offsets, d_dir_need not 8-byte, d_info not 16-byte or d_cigar not 4-byte aligned; then
+ * GENIE_E_TOO_LONG as there; then, for U > 0 or a selection, a d_workspace that is null, not 256-byte aligned or smaller than
+ * genie_chain_cigars_workspace_bytes(U, cap_chains, n_sel, dir_bytes) gives GENIE_E_CAPACITY; then GENIE_E_NO_DEVICE.  The read
+ * offsets and the row offsets are checked on the device as there (GENIE_E_INVALID), at the cost of the call's only
+ * synchronisation of `stream`.  No selected chain: d_cigar_offsets[0] = 0 and zero totals.
+ * The workspace function returns GENIE_E_INVALID for negative arguments, is a multiple of 256 and monotone in all four: 4 bytes
+ * per chain (the chain's unit), 20 bytes per selected chain (op count 4, need 8, direction offset 8) and 8 per 1024 of them (the
+ * scan), 0 bytes per unit, dir_bytes rounded up to 256, and 256 for the verdict of the offset checks.
+ * Kernels: a plan (one lane per selected chain: the need), one block for the running sum, the fill (one wave per selected
+ * chain, genie_align_chains' program with one 4-bit store per cell), and the trace (one lane per selected chain, one step per
+ * op base), run twice: it counts, the offsets are scanned, it writes. */
+int64_t genie_chain_cigars_workspace_bytes(int64_t U, int64_t cap_chains, int64_t n_sel, int64_t dir_bytes);
+int genie_chain_cigars(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs, int32_t flags,
+                       const uint8_t *d_bases, const int64_t *d_read_offsets, int64_t N, int64_t total_bases, int64_t max_len,
+                       const int64_t *d_offsets,        /* U + 1 */
+                       const int32_t *d_rows,           /* 4 * total_rows, 16-byte aligned */
+                       int64_t U, int64_t total_rows,
+                       const int32_t *d_anchor_chain,   /* total_rows */
+                       const int32_t *d_anchor_pred,    /* total_rows */
+                       const int64_t *d_chain_offsets,  /* U + 1 */
+                       const int32_t *d_chains,         /* 8 * cap_chains, 16-byte aligned */
+                       int64_t cap_chains,
+                       int32_t match, int32_t mismatch, int32_t gap_open, int32_t gap_extend, int32_t band, int32_t max_indel,
+                       int32_t end_bonus,
+                       const int32_t *d_aln,            /* 8 * cap_chains, 16-byte aligned: as genie_align_chains wrote it */
+                       const int64_t *d_sel,            /* n_sel, may be NULL: every chain */
+                       int64_t n_sel,
+                       int64_t *d_cigar_offsets,        /* n_sel + 1 */
+                       uint32_t *d_cigar,               /* cap_ops, may be NULL: sizing only */
+                       int64_t cap_ops,
+                       int32_t *d_info,                 /* 8 * n_sel, 16-byte aligned */
+                       int64_t *d_dir_need,             /* n_sel, may be NULL */
+                       int64_t *d_totals,               /* 3, may be NULL */
+                       int64_t dir_bytes,
+                       void *d_workspace, int64_t workspace_bytes, void *stream);
+
 /* Matching statistics and SMEMs that are EXACT WITH RESPECT TO THE SEQUENCE SET.  genie_match_stats and the SMEM calls on a
  * reference of several sequences answer for the concatenation; genie_locate_contigs then drops the occurrences that bridge
  * two sequences, and with them seeds.  Contigs ACGT | TTGA and the read CGTT: the concatenation holds CGTT once, across the
