@@ -385,6 +385,7 @@ __global__ void __launch_bounds__(kScanBlock) align_totals_kernel(const long lon
 }  // namespace
 
 #include "cigars.inc"
+#include "select.inc"
 
 int64_t align_chains_workspace_bytes(int64_t U, int64_t cap_chains)
 {

@@ -725,6 +725,48 @@ int genie_chain_cigars(const genie_index *ix, const int64_t *d_contig_offsets, i
                                {d_sel, n_sel, d_cigar_offsets, d_cigar, cap_ops, d_info, d_dir_need, d_totals, dir_bytes}, stream);
 }
 
+int64_t genie_select_alignments_workspace_bytes(int64_t N, int64_t cap_chains)
+{
+    if (N < 0 || cap_chains < 0) return (int64_t)GENIE_E_INVALID;
+    return select_alignments_workspace_bytes(N, cap_chains);
+}
+
+int genie_select_alignments(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs, int32_t flags,
+                            const int64_t *d_read_offsets, int64_t N, const int64_t *d_chain_offsets, int64_t U, const int32_t *d_chains,
+                            const int32_t *d_aln, int64_t cap_chains, int32_t mask_level, int32_t pri_ratio, int32_t max_secondary,
+                            int32_t min_score, int32_t mapq_full, int32_t *d_class, int64_t *d_sel_offsets, int64_t *d_sel,
+                            int32_t *d_records, int64_t cap_sel, int32_t *d_read_counts, int64_t *d_totals, void *d_workspace,
+                            int64_t workspace_bytes, void *stream)
+{
+    // argument checks first: they need no device image
+    if (!ix || !d_chain_offsets || !d_sel_offsets || (N > 0 && !d_read_offsets)) return GENIE_E_INVALID;
+    if (cap_chains > 0 && (!d_chains || !d_aln || !d_class)) return GENIE_E_INVALID;
+    if (d_sel && !d_records) return GENIE_E_INVALID;
+    if (N < 0 || U < 0 || cap_chains < 0 || cap_sel < 0 || workspace_bytes < 0 || (flags & ~kReadFlags) != 0) return GENIE_E_INVALID;
+    const int32_t S = (flags & GENIE_READS_BOTH_STRANDS) ? 2 : 1;
+    if (N > 0x7fffffffffffffffll / S || U != S * N) return GENIE_E_INVALID;
+    if (mask_level < 0 || mask_level > 100 || pri_ratio < 0 || pri_ratio > 100 || max_secondary < 0 || max_secondary > (1 << 20) ||
+        min_score < 1 || min_score > (1 << 30) || mapq_full < 1 || mapq_full > (1 << 20))
+        return GENIE_E_INVALID;
+    if (misaligned(d_read_offsets, 7) || misaligned(d_chain_offsets, 7) || misaligned(d_chains, 15) || misaligned(d_aln, 15) ||
+        misaligned(d_class, 15) || misaligned(d_sel_offsets, 7) || misaligned(d_sel, 7) || misaligned(d_records, 15) ||
+        misaligned(d_read_counts, 15) || misaligned(d_totals, 7))
+        return GENIE_E_INVALID;
+    // the table is optional: null with n_contigs == 0, or a table as every contig call takes it
+    if (!d_contig_offsets && n_contigs != 0) return GENIE_E_INVALID;
+    if (d_contig_offsets)
+        if (int rc = contig_args(d_contig_offsets, n_contigs)) return rc;
+    // reads and chains are named by an int32 in d_class and d_records
+    if (N > 0x7fffffffll || cap_chains > 0x7fffffffll) return GENIE_E_TOO_LONG;
+    if (U > 0 && (!d_workspace || misaligned(d_workspace, 255) || workspace_bytes < select_alignments_workspace_bytes(N, cap_chains)))
+        return GENIE_E_CAPACITY;
+    if (int rc = ready(ix)) return rc;
+    const SelectBatch b{d_read_offsets, N, S, d_chain_offsets, U, d_chains, d_aln, cap_chains, mask_level, pri_ratio, max_secondary,
+                        min_score, mapq_full};
+    return launch_select_alignments(ix, {d_contig_offsets, n_contigs}, b,
+                                    {d_class, d_sel_offsets, d_sel, d_records, cap_sel, d_read_counts, d_totals}, d_workspace, stream);
+}
+
 int genie_contig_coords(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs, const int32_t *d_pos, int32_t stride,
                         int64_t count, int32_t *d_out, void *stream)
 {

@@ -479,6 +479,28 @@ struct CigarOut {
 int64_t chain_cigars_workspace_bytes(int64_t U, int64_t cap_chains, int64_t n_sel, int64_t dir_bytes);
 int launch_chain_cigars(const genie_index *ix, const ContigTable &ctg, const CsrBatch &b, const AlignBatch &ab, const AlignParams &prm,
                         const int32_t *d_aln, const CigarOut &out, void *stream);
+// select.inc: per read, the primary, supplementary and secondary alignments among the rows of launch_align_chains
+struct SelectBatch {
+    const int64_t *read_offsets;
+    int64_t N;
+    int32_t S;                            // strands: U == S N
+    const int64_t *chain_offsets;
+    int64_t U;
+    const int32_t *chains, *aln;
+    int64_t cap_chains;
+    int32_t mask_level, pri_ratio, max_secondary, min_score, mapq_full;
+};
+struct SelectOut {
+    int32_t *klass;
+    int64_t *sel_offsets, *sel;           // sel may be null: sizing only
+    int32_t *records;
+    int64_t cap_sel;
+    int32_t *read_counts;                 // may be null
+    int64_t *totals;                      // may be null
+};
+int64_t select_alignments_workspace_bytes(int64_t N, int64_t cap_chains);
+int launch_select_alignments(const genie_index *ix, const ContigTable &ctg, const SelectBatch &b, const SelectOut &out, void *ws,
+                             void *stream);
 // min_occ.inc: matching statistics and SMEMs of what occurs at least min_occ times
 int64_t match_stats_min_occ_workspace_bytes(int64_t N, int64_t total_bases, int32_t flags);
 int launch_match_stats_min_occ(const genie_index *ix, int32_t min_occ, const CsrBatch &b, int32_t *d_ms, int32_t *d_lohi,

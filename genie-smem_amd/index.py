@@ -5,6 +5,7 @@ Everything that computes goes through the C ABI (include/genie_smem.h); torch on
 device memory, the stream and -- multi-GPU -- the one-time broadcast of the index image.
 """
 import ctypes as C
+import re
 
 import numpy as np
 import torch
@@ -23,6 +24,7 @@ def _stream(device):
 
 
 _CIGAR_LETTERS = {1: "I", 2: "D", 4: "S", 7: "=", 8: "X"}
+_CIGAR_OP = re.compile(r"(\d+)([IDS=X])")
 
 
 def cigar_strings(cigar_offsets, cigar):
@@ -33,6 +35,28 @@ def cigar_strings(cigar_offsets, cigar):
         cigar = cigar.view(torch.int32).cpu().numpy() if cigar.dtype == torch.uint32 else cigar.cpu().numpy()
     ops = np.asarray(cigar).astype(np.int64) & 0xFFFFFFFF
     return ["".join(f"{int(v) >> 4}{_CIGAR_LETTERS[int(v) & 15]}" for v in ops[int(off[k]):int(off[k + 1])]) for k in range(len(off) - 1)]
+
+
+def paf_lines(records, info, cigar_offsets, cigar, read_names, read_lengths, contig_names, contig_lengths):
+    """The records of select_alignments with chain_cigars' results for its `sel` as PAF text, one line per record: the twelve
+    columns (query name, length, start, end in forward read coordinates, strand, target name, length, 0-based start, end,
+    matches = n_eq, alignment length = n_eq + n_x + ins_bases + del_bases, mapq), then tp:A:P (primary and supplementary) or
+    tp:A:S (secondary), NM:i and cg:Z, the CIGAR without its clips: columns 3 and 4 say them.  A host helper: tensors are
+    copied to the host first."""
+    host = lambda t: t.cpu().numpy() if hasattr(t, "cpu") else np.asarray(t)      # noqa: E731
+    rec, inf = host(records).reshape(-1, 12), host(info).reshape(-1, 8)
+    texts = cigar_strings(cigar_offsets, cigar)
+    if not len(rec) == len(inf) == len(texts):
+        raise ValueError("records, info and the CIGARs must be parallel: chain_cigars on select_alignments' sel")
+    lines = []
+    for (read, _, kind, strand, contig, offset, r_span, qb, qe, _, _, mapq), row, text in zip(rec.tolist(), inf.tolist(), texts):
+        n_eq, n_x, ins, dele = row[4:8]
+        core = "".join(f"{n}{op}" for n, op in _CIGAR_OP.findall(text) if op != "S")
+        cols = [read_names[read], int(read_lengths[read]), qb, qe, "-" if strand else "+", contig_names[contig], int(contig_lengths[contig]),
+                offset - 1, offset - 1 + r_span, n_eq, n_eq + n_x + ins + dele, mapq, "tp:A:" + ("S" if kind == 2 else "P"),
+                f"NM:i:{row[3]}", "cg:Z:" + core]
+        lines.append("\t".join(str(c) for c in cols))
+    return lines
 
 
 class GenieIndex:
@@ -757,6 +781,55 @@ class GenieIndex:
             if ops <= cap_ops:
                 return cigar_offsets, cigar[:ops].view(torch.uint32), info[:n_sel]
             cap_ops = ops
+
+    def select_alignments(self, read_offsets, chain_offsets, chains, aln, contigs=None, both_strands=False, mask_level=50, pri_ratio=80,
+                          max_secondary=5, min_score=1, mapq_full=40):
+        """The alignments of every read (genie_select_alignments): its chains, as align_chains scored them, classified as
+        primary (kind 0), supplementary (1), secondary (2) or none (3) by minimap2's parent rule, with a mapping quality ->
+        (sel_offsets int64[N+1], sel int64[n], records int32[n, 12] = (read, chain, kind, strand, contig, offset, r_span,
+        q_begin, q_end, score, sub, mapq), klass int32[C, 4] = (kind, parent, order, mapq), read_counts int32[N, 4] =
+        (candidates, primaries, secondaries, best chain or -1), totals int64[4] = (candidates, primaries, secondaries,
+        selected)) on the device.  sel lists, read by read, the primaries by (score descending, chain ascending) and then at
+        most max_secondary secondaries that score at least pri_ratio percent of their primary; it is chain_cigars' `select`.
+        read_offsets as find_mems took them; chain_offsets and chains: chain_mems' first two results; aln: align_chains'
+        first.  Two candidates overlap when their forward read intervals share more than mask_level percent of the shorter;
+        chains below min_score are no candidates; mapq = 60 (1 - sub / score) min(1, matched / mapq_full), rounded down.  q_begin
+        and q_end are in forward read coordinates, offset is 1-based inside the contig.  The defaults are this wrapper's; the
+        C call has none."""
+        self._need_device()
+        read_offsets = self._as_dev(read_offsets, torch.int64).reshape(-1)
+        chain_offsets = self._as_dev(chain_offsets, torch.int64).reshape(-1)
+        chains, aln = self._as_dev(chains, torch.int32), self._as_dev(aln, torch.int32)
+        if read_offsets.numel() < 1:
+            raise ValueError("read_offsets needs N + 1 entries")
+        if chains.dim() != 2 or chains.shape[1] != 8 or aln.shape != chains.shape:
+            raise ValueError("the chain rows must be [C, 8] and aln parallel to them")
+        strands = 2 if both_strands else 1
+        n_reads, U, kept = read_offsets.numel() - 1, chain_offsets.numel() - 1, chains.shape[0]
+        if U != strands * n_reads:
+            raise ValueError("chain_offsets must be those of these reads' chain_mems")
+        table = (C.c_void_p(0), 0)
+        if contigs is not None:
+            off, table = self._contig_table(contigs)
+        prm = (int(mask_level), int(pri_ratio), int(max_secondary), int(min_score), int(mapq_full))
+        none = C.c_void_p(0)
+        klass = torch.empty((max(kept, 1), 4), dtype=torch.int32, device=self.device)
+        sel_offsets = torch.empty(n_reads + 1, dtype=torch.int64, device=self.device)
+        read_counts = torch.empty((max(n_reads, 1), 4), dtype=torch.int32, device=self.device)
+        totals = torch.empty(4, dtype=torch.int64, device=self.device)
+        ws, ws_bytes = self._workspace("genie_select_alignments_workspace_bytes", n_reads, kept)
+        head = (*table, N.READS_BOTH_STRANDS if both_strands else 0, _ptr(read_offsets), n_reads, _ptr(chain_offsets), U,
+                _ptr(chains) if kept else none, _ptr(aln) if kept else none, kept, *prm, _ptr(klass) if kept else none, _ptr(sel_offsets))
+        tail = (_ptr(read_counts), _ptr(totals), _ptr(ws), ws_bytes)
+        cap_sel = n_reads                                            # most reads have one alignment; more: a second call
+        while True:
+            sel = torch.empty(max(cap_sel, 1), dtype=torch.int64, device=self.device)
+            records = torch.empty((max(cap_sel, 1), 12), dtype=torch.int32, device=self.device)
+            self._run("genie_select_alignments", *head, _ptr(sel), _ptr(records), cap_sel, *tail)
+            n_sel = int(sel_offsets[n_reads].item())
+            if n_sel <= cap_sel:
+                return sel_offsets, sel[:n_sel], records[:n_sel], klass[:kept], read_counts[:n_reads], totals
+            cap_sel = n_sel
 
     def contig_coords(self, contigs, pos, stride=1):
         """1-based concatenation positions -> int32 [count, 2] = (contig, 1-based offset inside it) on the device

@@ -268,6 +268,32 @@ class SMEM:
         cigar_offsets[1:] = torch.cumsum(counts, 0)
         return hits, cigar_offsets, cigar
 
+    def select_alignments(self, read_offsets, chain_offsets, chains, aln, contigs=None, both_strands=False, **select_options):
+        """The alignments of every read (genie_select_alignments) -> (sel_offsets, sel, records int32[n, 12] = (read, chain, kind,
+        strand, contig, offset, r_span, q_begin, q_end, score, sub, mapq), klass, read_counts, totals):
+        GenieIndex.select_alignments, which documents the options (mask_level, pri_ratio, max_secondary, min_score, mapq_full)
+        and their defaults."""
+        ix = self.matcher.index(self.lut.lut_size)
+        return ix.select_alignments(read_offsets, chain_offsets, chains, aln, contigs, both_strands, **select_options)
+
+    def map_records(self, reads, minimum_length, contigs=None, both_strands=True, split_breaks=False, max_occ=0, align_options=None,
+                    select_options=None, **chain_options):
+        """Every alignment of every read: find_alignments, select_alignments on its rows, chain_cigars on that selection ->
+        (records int32[n, 12], sel_offsets int64[N+1], cigar_offsets int64[n+1], cigar uint32[ops], info int32[n, 8]) on the
+        device, records, CIGARs and info parallel: read i's alignments are the rows sel_offsets[i] .. sel_offsets[i+1], its
+        primary first, then its supplementary ones, then its secondaries.  records as select_alignments returns them (kind 0
+        primary, 1 supplementary, 2 secondary; q_begin / q_end in forward read coordinates); the CIGAR is in strand-read
+        order, as SAM has it; paf_lines turns the lot into text.  align_options, select_options: dicts of align_chains' and
+        select_alignments' options."""
+        ix = self.matcher.index(self.lut.lut_size)
+        csr = self._csr_reads(reads, split_breaks)
+        opts = dict(align_options or {})
+        mems, chains, aln = self.find_alignments(csr, minimum_length, contigs, both_strands, split_breaks, max_occ, opts, by_score=False,
+                                                 **chain_options)
+        sel_offsets, sel, records = ix.select_alignments(csr[1], chains[0], chains[1], aln, contigs, both_strands, **(select_options or {}))[:3]
+        offs, cigar, info = ix.chain_cigars(csr, mems[0], mems[1], chains, aln, sel, contigs, both_strands, **opts)
+        return records, sel_offsets, offs, cigar, info
+
     def locate_contigs(self, contigs, rows):
         """SMEM rows (start, end, lo, hi) of any find_smems* call -> (hit_offsets, hits int32[T, 2] = (contig, 1-based
         offset), dropped): GenieIndex.locate_contigs.  The rows stay SMEMs of the concatenation; occurrences that bridge two

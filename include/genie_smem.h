@@ -818,6 +818,90 @@ int genie_chain_cigars(const genie_index *ix, const int64_t *d_contig_offsets, i
                        int64_t dir_bytes,
                        void *d_workspace, int64_t workspace_bytes, void *stream);
 
+/* The alignments of every read: which of its chains, as genie_align_chains scored them, are its primary, its supplementary
+ * and its secondary alignments, each with a mapping quality; the selection goes straight into genie_chain_cigars as d_sel.
+ * Everything is integer and deterministic.  The rule is minimap2's parent rule and the quality minimap2's shape without the
+ * logarithm: a POLICY, expressed through five scalars, not a model.
+ * Inputs, all as the earlier calls wrote them:
+ *   reads    d_read_offsets[N + 1], N: used for the read lengths L alone.
+ *   flags    GENIE_READS_BOTH_STRANDS: S = 2 strand-reads per read, unit 2 i + 1 the reverse complement of read i; otherwise
+ *            S = 1.  GENIE_READS_SPLIT_BREAKS is accepted and changes nothing; any other bit: GENIE_E_INVALID.
+ *   chains   d_chain_offsets[U + 1] with U == S N (GENIE_E_INVALID), d_chains (only column 6, the contig, is read), d_aln,
+ *            cap_chains.  C = min(d_chain_offsets[U], cap_chains).
+ *   contigs  d_contig_offsets, n_contigs as genie_align_chains takes them; NULL with n_contigs == 0: one contig [0, n).
+ * Parameters (int32; the call has no defaults): mask_level in [0, 100]; pri_ratio in [0, 100]; max_secondary in [0, 2^20];
+ * min_score in [1, 2^30]; mapq_full in [1, 2^20].  Anything outside its range gives GENIE_E_INVALID.
+ * Candidates.  The candidates of read i are the chains c < C of its units S i .. S i + S - 1 whose d_aln row has flag bit 4
+ * clear and score >= min_score.
+ * Query interval.  A candidate's interval is taken in FORWARD read coordinates: on strand 0 [q_begin, q_end), on strand 1
+ * [L - q_end, L - q_begin); both ends are clamped to [0, L].  Its length is end - begin.
+ * Key order.  (score descending, global chain index ascending): a tie goes to the smaller chain index.
+ * Overlap.  Two candidates of a read overlap iff 100 ov > mask_level min(len_i, len_j) in 64-bit arithmetic, ov the length of
+ * the intersection of their forward intervals.  Equality is no overlap.  Strand and contig play no part.
+ * Classification.  Walk the candidates of a read in key order.  A candidate that overlaps no earlier primary is a primary.
+ * Otherwise it is a secondary, and its parent is the first primary in key order that it overlaps.  The read's first primary
+ * has kind 0, later primaries kind 1 (supplementary), secondaries kind 2, chains c < C that are no candidate kind 3.
+ * Per primary P: n_sec(P) is the number of its secondaries, sub(P) the largest score among them (0 if none), and
+ *   mapq(P) = floor(60 (score - min(sub, score)) min(matched, mapq_full) / (score mapq_full))
+ * in int64, matched being column 7 of d_aln (taken as 0 when negative): a value in [0, 60].  A secondary has mapq 0.
+ * Selection of a read: first its primaries in key order; then the ELIGIBLE secondaries in key order, at most max_secondary of
+ * them.  A secondary is eligible iff 100 score >= pri_ratio score(parent).  Equality is eligible.
+ * Outputs, all in caller buffers:
+ *   d_class        4 int32 per chain, 16-byte aligned, parallel to d_aln, written for every c < C:
+ *                  (kind, parent, order, mapq).  parent is the global chain index of its primary, a primary its own, -1 for
+ *                  kind 3; order is its index inside its read's selection, -1 if not selected.  Rows at or past C are left
+ *                  untouched.
+ *   d_sel_offsets  N + 1 int64, 8-byte aligned; [N] holds the true total even when cap_sel is smaller
+ *   d_sel          cap_sel int64 global chain indices, 8-byte aligned, in the order above; NULL is the sizing call.  Entries
+ *                  past cap_sel are dropped.
+ *   d_records      12 int32 per selected chain, 16-byte aligned, parallel to d_sel; may be NULL only together with d_sel:
+ *                  (read, chain, kind, strand, contig, offset, r_span, q_begin, q_end, score, sub, mapq)
+ *                  offset is the 1-based start inside the contig, r_begin - d_contig_offsets[contig], and r_begin itself (and
+ *                  contig 0) without a table; r_span = r_end - r_begin; q_begin and q_end are in forward read coordinates;
+ *                  sub is 0 for a secondary.
+ *   d_read_counts  4 int32 per read, 16-byte aligned, may be NULL: (candidates, primaries, secondaries, best chain or -1)
+ *   d_totals       4 int64, 8-byte aligned, may be NULL: {candidates, primaries, secondaries, selected}; it stays on the device
+ * No atomic decides a value: the outputs are a function of the inputs alone.  d_aln or chain rows that break the assumptions
+ * give undefined values, but no load or store outside the declared sizes and no unbounded loop: the contig index is clamped to
+ * the table, positions are clamped to [0, L], and the rounds of a read are bounded by its chain count.
+ * Checked before the device check, so on any handle, GENIE_E_INVALID: a null ix, d_chain_offsets or d_sel_offsets; null read
+ * offsets where there are reads; a null d_chains, d_aln or d_class with cap_chains > 0; a d_sel without d_records; a negative
+ * size; a flag outside the two; U != S N; a parameter outside its range; d_chains, d_aln, d_class, d_records or d_read_counts not
+ * 16-byte, an offsets array, d_sel, d_totals or the table not 8-byte aligned; a table with n_contigs < 1 or a null table with
+ * n_contigs != 0 (GENIE_E_TOO_LONG for n_contigs above 2^31 - 2).  Then GENIE_E_TOO_LONG for N or cap_chains above 2^31 - 1:
+ * reads and chains are named by an int32.  Then, for U > 0, a d_workspace that is null, not 256-byte aligned or smaller than
+ * genie_select_alignments_workspace_bytes(N, cap_chains) gives GENIE_E_CAPACITY.  Then GENIE_E_NO_DEVICE.  The chain offsets are
+ * checked on the device as genie_align_chains checks its row offsets (GENIE_E_INVALID), at the cost of the call's only
+ * synchronisation of `stream`.  U == 0 or C == 0 writes zero offsets and zero totals (and, for U > 0, the counts of every read).
+ * The workspace function returns GENIE_E_INVALID for negative arguments, is a multiple of 256 and monotone in both: 4 bytes
+ * per chain (sub of a primary), 64 bytes per read (its counts 16, its selected count 4, the wide mark 4, its row in the list of
+ * wide reads twice 16, that list's offset 8) and 8 per 1024 reads (the scan), and 256 for the verdict of the offset check.
+ * Kernels: greedy rounds, which give the walk's result without a sort: the best unassigned candidate (an arg-max over a packed
+ * 64-bit key) becomes a primary and takes every unassigned candidate that overlaps it; the selected secondaries are further
+ * arg-max rounds.  A read of at most GENIE_SELECT_LANE_MAX chains is run by one lane; the others are compacted into a list and
+ * run one wave each, the state of their first GENIE_SELECT_TILE chains in LDS and that of the rest in d_class.  Cost of a read
+ * of c chains with p primaries: about (p + max_secondary) ceil(c / 64) wave steps. */
+#define GENIE_SELECT_LANE_MAX 8
+#define GENIE_SELECT_TILE 512
+int64_t genie_select_alignments_workspace_bytes(int64_t N, int64_t cap_chains);
+int genie_select_alignments(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs, int32_t flags,
+                            const int64_t *d_read_offsets,  /* N + 1 */
+                            int64_t N,
+                            const int64_t *d_chain_offsets, /* U + 1 */
+                            int64_t U,
+                            const int32_t *d_chains,        /* 8 * cap_chains, 16-byte aligned */
+                            const int32_t *d_aln,           /* 8 * cap_chains, 16-byte aligned: as genie_align_chains wrote it */
+                            int64_t cap_chains,
+                            int32_t mask_level, int32_t pri_ratio, int32_t max_secondary, int32_t min_score, int32_t mapq_full,
+                            int32_t *d_class,               /* 4 * cap_chains, 16-byte aligned */
+                            int64_t *d_sel_offsets,         /* N + 1 */
+                            int64_t *d_sel,                 /* cap_sel, may be NULL: sizing only */
+                            int32_t *d_records,             /* 12 * cap_sel, 16-byte aligned; NULL only with d_sel */
+                            int64_t cap_sel,
+                            int32_t *d_read_counts,         /* 4 * N, 16-byte aligned, may be NULL */
+                            int64_t *d_totals,              /* 4, may be NULL */
+                            void *d_workspace, int64_t workspace_bytes, void *stream);
+
 /* Matching statistics and SMEMs that are EXACT WITH RESPECT TO THE SEQUENCE SET.  genie_match_stats and the SMEM calls on a
  * reference of several sequences answer for the concatenation; genie_locate_contigs then drops the occurrences that bridge
  * two sequences, and with them seeds.  Contigs ACGT | TTGA and the read CGTT: the concatenation holds CGTT once, across the
