@@ -386,6 +386,7 @@ __global__ void __launch_bounds__(kScanBlock) align_totals_kernel(const long lon
 
 #include "cigars.inc"
 #include "select.inc"
+#include "pairs.inc"
 
 int64_t align_chains_workspace_bytes(int64_t U, int64_t cap_chains)
 {

@@ -767,6 +767,40 @@ int genie_select_alignments(const genie_index *ix, const int64_t *d_contig_offse
                                     {d_class, d_sel_offsets, d_sel, d_records, cap_sel, d_read_counts, d_totals}, d_workspace, stream);
 }
 
+int64_t genie_pair_alignments_workspace_bytes(int64_t N, int64_t n_records)
+{
+    if (N < 0 || n_records < 0) return (int64_t)GENIE_E_INVALID;
+    return pair_alignments_workspace_bytes(N, n_records);
+}
+
+int genie_pair_alignments(const genie_index *ix, int64_t N, const int64_t *d_sel_offsets, const int32_t *d_records, int64_t n_records,
+                          const int32_t *d_class, int64_t cap_chains, int32_t orient, int32_t isize_min, int32_t isize_max,
+                          int32_t isize_mean, int32_t pen_slope, int32_t pen_max, int32_t pen_unpaired, int32_t mapq_boost,
+                          int32_t *d_pairs, int32_t *d_sam, int64_t *d_totals, void *d_workspace, int64_t workspace_bytes, void *stream)
+{
+    // argument checks first: they need no device image
+    if (!ix || !d_sel_offsets || !d_pairs) return GENIE_E_INVALID;
+    if (N < 0 || (N & 1) != 0 || n_records < 0 || cap_chains < 0 || workspace_bytes < 0) return GENIE_E_INVALID;
+    if (n_records > 0 && (!d_records || !d_sam)) return GENIE_E_INVALID;
+    if (cap_chains > 0 && !d_class) return GENIE_E_INVALID;
+    const int32_t isize_most = 1 << 30;
+    if (orient < 1 || orient > 7 || isize_min < 0 || isize_min > isize_most || isize_max < 0 || isize_max > isize_most ||
+        isize_mean < 0 || isize_mean > isize_most || isize_min > isize_max || pen_slope < 0 || pen_slope > 65536 || pen_max < 0 ||
+        pen_max > (1 << 20) || pen_unpaired < 0 || pen_unpaired > (1 << 20) || mapq_boost < 0 || mapq_boost > 60)
+        return GENIE_E_INVALID;
+    if (misaligned(d_records, 15) || misaligned(d_class, 15) || misaligned(d_pairs, 15) || misaligned(d_sam, 15) ||
+        misaligned(d_sel_offsets, 7) || misaligned(d_totals, 7))
+        return GENIE_E_INVALID;
+    // reads and records are named by an int32 in d_pairs and d_sam
+    if (N > 0x7fffffffll || n_records > 0x7fffffffll) return GENIE_E_TOO_LONG;
+    if (N > 0 && (!d_workspace || misaligned(d_workspace, 255) || workspace_bytes < pair_alignments_workspace_bytes(N, n_records)))
+        return GENIE_E_CAPACITY;
+    if (int rc = ready(ix)) return rc;
+    const PairBatch b{N, d_sel_offsets, d_records, n_records, d_class, cap_chains, orient, isize_min, isize_max, isize_mean,
+                      pen_slope, pen_max, pen_unpaired, mapq_boost};
+    return launch_pair_alignments(ix, b, {d_pairs, d_sam, d_totals}, d_workspace, stream);
+}
+
 int genie_contig_coords(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs, const int32_t *d_pos, int32_t stride,
                         int64_t count, int32_t *d_out, void *stream)
 {

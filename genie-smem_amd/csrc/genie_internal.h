@@ -501,6 +501,22 @@ struct SelectOut {
 int64_t select_alignments_workspace_bytes(int64_t N, int64_t cap_chains);
 int launch_select_alignments(const genie_index *ix, const ContigTable &ctg, const SelectBatch &b, const SelectOut &out, void *ws,
                              void *stream);
+// pairs.inc: per pair of mates (reads 2k and 2k + 1), the records of launch_select_alignments that go together, and SAM's fields
+struct PairBatch {
+    int64_t N;                            // reads, even
+    const int64_t *sel_offsets;           // N + 1
+    const int32_t *records;
+    int64_t n_records;
+    const int32_t *klass;
+    int64_t cap_chains;
+    int32_t orient, isize_min, isize_max, isize_mean, pen_slope, pen_max, pen_unpaired, mapq_boost;
+};
+struct PairOut {
+    int32_t *pairs, *sam;
+    int64_t *totals;                      // may be null
+};
+int64_t pair_alignments_workspace_bytes(int64_t N, int64_t n_records);
+int launch_pair_alignments(const genie_index *ix, const PairBatch &b, const PairOut &out, void *ws, void *stream);
 // min_occ.inc: matching statistics and SMEMs of what occurs at least min_occ times
 int64_t match_stats_min_occ_workspace_bytes(int64_t N, int64_t total_bases, int32_t flags);
 int launch_match_stats_min_occ(const genie_index *ix, int32_t min_occ, const CsrBatch &b, int32_t *d_ms, int32_t *d_lohi,

@@ -59,6 +59,66 @@ def paf_lines(records, info, cigar_offsets, cigar, read_names, read_lengths, con
     return lines
 
 
+def sam_header(contig_names, contig_lengths):
+    """The header lines of a SAM file for sam_lines: @HD (unsorted, grouped by query), one @SQ per contig, @PG."""
+    lines = ["@HD\tVN:1.6\tSO:unsorted\tGO:query"]
+    lines += [f"@SQ\tSN:{name}\tLN:{int(length)}" for name, length in zip(contig_names, contig_lengths)]
+    return lines + ["@PG\tID:genie-smem_amd\tPN:genie-smem_amd"]
+
+
+_COMPLEMENT = str.maketrans("ACGTNacgtn", "TGCANtgcan")
+
+
+def sam_lines(records, sam, info, cigar_offsets, cigar, read_names, contig_names, seqs=None, quals=None):
+    """The records of an interleaved batch of mates (map_pairs) as SAM text: one line per record, read by read in record
+    order -- QNAME, FLAG and MAPQ from pair_alignments' `sam`, RNAME, POS (the record's 1-based offset), the chain's CIGAR
+    with its clips, RNEXT (`=`, a contig name or `*`) and PNEXT from mate_record, TLEN, SEQ and QUAL (`*` when not given;
+    given in read orientation, they are turned for strand 1), NM:i and AS:i -- and, for a read without records, the unmapped
+    line: flag 0x4 plus the pair bits, placed at its mate's position if the mate is mapped.  read_names has one name per read;
+    reads 2k and 2k + 1 are mates.  A host helper: tensors are copied to the host first."""
+    host = lambda t: t.cpu().numpy() if hasattr(t, "cpu") else np.asarray(t)      # noqa: E731
+    rec, fields, inf = host(records).reshape(-1, 12).tolist(), host(sam).reshape(-1, 4).tolist(), host(info).reshape(-1, 8).tolist()
+    texts = cigar_strings(cigar_offsets, cigar)
+    if not len(rec) == len(fields) == len(inf) == len(texts):
+        raise ValueError("records, sam, info and the CIGARs must be parallel: map_pairs' results")
+    if len(read_names) % 2:
+        raise ValueError("an even number of reads: reads 2k and 2k + 1 are mates")
+    by_read, chosen = [[] for _ in read_names], {}
+    for j, (row, field) in enumerate(zip(rec, fields)):
+        by_read[row[0]].append(j)
+        if not field[0] & 0x900:
+            chosen[row[0]] = j
+
+    def seq_qual(read, strand):
+        seq = seqs[read] if seqs is not None else "*"
+        qual = quals[read] if quals is not None else "*"
+        if strand:
+            seq = seq if seq == "*" else seq.translate(_COMPLEMENT)[::-1]
+            qual = qual if qual == "*" else qual[::-1]
+        return [seq, qual]
+
+    lines = []
+    for read, name in enumerate(read_names):
+        for j in by_read[read]:
+            _, _, _, strand, contig, offset, _, _, _, score, _, _ = rec[j]
+            flag, mapq, mate, tlen = fields[j]
+            rnext, pnext = "*", 0
+            if mate >= 0:
+                rnext, pnext = "=" if rec[mate][4] == contig else contig_names[rec[mate][4]], rec[mate][5]
+            cols = [name, flag, contig_names[contig], offset, mapq, texts[j] or "*", rnext, pnext, tlen] + seq_qual(read, strand)
+            lines.append("\t".join(str(c) for c in cols + [f"NM:i:{inf[j][3]}", f"AS:i:{score}"]))
+        if not by_read[read]:
+            flag, rname, pos, rnext = 0x1 | 0x4 | (0x80 if read & 1 else 0x40), "*", 0, "*"
+            mate = chosen.get(read ^ 1)
+            if mate is None:
+                flag |= 0x8
+            else:
+                flag |= 0x20 if rec[mate][3] else 0
+                rname, pos, rnext = contig_names[rec[mate][4]], rec[mate][5], "="
+            lines.append("\t".join(str(c) for c in [name, flag, rname, pos, 0, "*", rnext, pos, 0] + seq_qual(read, 0)))
+    return lines
+
+
 class GenieIndex:
     def __init__(self):
         self._h = C.c_void_p(0)
@@ -830,6 +890,39 @@ class GenieIndex:
             if n_sel <= cap_sel:
                 return sel_offsets, sel[:n_sel], records[:n_sel], klass[:kept], read_counts[:n_reads], totals
             cap_sel = n_sel
+
+    def pair_alignments(self, sel_offsets, records, klass, orient="fr", isize_min=0, isize_max=1000, isize_mean=300, pen_slope=8,
+                        pen_max=16, pen_unpaired=17, mapq_boost=40):
+        """The alignments of paired-end reads (genie_pair_alignments): reads 2k and 2k + 1 are the mates of pair k; for every
+        pair the best concordant combination of the mates' candidate records (the head of a read and the secondaries of that
+        head) against the two heads taken alone -> (pairs int32[P, 8] = (rec0, rec1, flags, pair_score, sub_score, isize,
+        n_concordant, type), sam int32[R, 4] = (flag, mapq, mate_record, tlen), totals int64[4] = (pairs with both mates
+        mapped, proper pairs, mates whose chosen record is not their head, pairs with exactly one mate mapped)) on the device.
+        sel_offsets, records, klass: select_alignments' first, third and fourth results.  orient: "fr", "rf", "same", "any" or
+        the mask itself (bit 0 FR, bit 1 RF, bit 2 same strand).  A combination is concordant when its orientation is allowed
+        and isize_min <= span <= isize_max; it is worth the two scores less min(pen_max, |span - isize_mean| pen_slope / 256),
+        and the pair is proper when the best one is worth at least the two heads less pen_unpaired.  sam holds SAM's flag bits
+        and, for the chosen record of a proper pair, a mapq raised to the pair's by at most mapq_boost.  The defaults are this
+        wrapper's -- a concordant pair of heads always beats the unpaired alternative: pen_max < pen_unpaired --; the C call
+        has none."""
+        self._need_device()
+        sel_offsets = self._as_dev(sel_offsets, torch.int64).reshape(-1)
+        records, klass = self._as_dev(records, torch.int32), self._as_dev(klass, torch.int32)
+        if sel_offsets.numel() < 1 or (sel_offsets.numel() - 1) % 2:
+            raise ValueError("sel_offsets needs N + 1 entries for an even number of reads: mates are interleaved")
+        if records.dim() != 2 or records.shape[1] != 12 or klass.dim() != 2 or klass.shape[1] != 4:
+            raise ValueError("records must be [R, 12] and klass [C, 4], as select_alignments returns them")
+        n_reads, n_rec, kept = sel_offsets.numel() - 1, records.shape[0], klass.shape[0]
+        mask = N.PAIR_ORIENT[orient] if isinstance(orient, str) else int(orient)
+        prm = (mask, int(isize_min), int(isize_max), int(isize_mean), int(pen_slope), int(pen_max), int(pen_unpaired), int(mapq_boost))
+        none = C.c_void_p(0)
+        pairs = torch.empty((max(n_reads // 2, 1), 8), dtype=torch.int32, device=self.device)
+        sam = torch.empty((max(n_rec, 1), 4), dtype=torch.int32, device=self.device)
+        totals = torch.empty(4, dtype=torch.int64, device=self.device)
+        ws, ws_bytes = self._workspace("genie_pair_alignments_workspace_bytes", n_reads, n_rec)
+        self._run("genie_pair_alignments", n_reads, _ptr(sel_offsets), _ptr(records) if n_rec else none, n_rec,
+                  _ptr(klass) if kept else none, kept, *prm, _ptr(pairs), _ptr(sam) if n_rec else none, _ptr(totals), _ptr(ws), ws_bytes)
+        return pairs[:n_reads // 2], sam[:n_rec], totals
 
     def contig_coords(self, contigs, pos, stride=1):
         """1-based concatenation positions -> int32 [count, 2] = (contig, 1-based offset inside it) on the device

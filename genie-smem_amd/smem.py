@@ -294,6 +294,38 @@ class SMEM:
         offs, cigar, info = ix.chain_cigars(csr, mems[0], mems[1], chains, aln, sel, contigs, both_strands, **opts)
         return records, sel_offsets, offs, cigar, info
 
+    def pair_alignments(self, sel_offsets, records, klass, **pair_options):
+        """The alignments of paired-end reads (genie_pair_alignments) -> (pairs int32[P, 8] = (rec0, rec1, flags, pair_score,
+        sub_score, isize, n_concordant, type), sam int32[R, 4] = (flag, mapq, mate_record, tlen), totals):
+        GenieIndex.pair_alignments, which documents the options (orient, isize_min, isize_max, isize_mean, pen_slope, pen_max,
+        pen_unpaired, mapq_boost) and their defaults.  Reads 2k and 2k + 1 are the mates of pair k."""
+        ix = self.matcher.index(self.lut.lut_size)
+        return ix.pair_alignments(sel_offsets, records, klass, **pair_options)
+
+    def map_pairs(self, reads, minimum_length, contigs=None, both_strands=True, split_breaks=False, max_occ=0, align_options=None,
+                  select_options=None, pair_options=None, **chain_options):
+        """Every alignment of every mate, paired: map_records on the interleaved batch, then pair_alignments on its records ->
+        (records, sel_offsets, cigar_offsets, cigar, info, pairs, sam): map_records' five results, then pairs int32[P, 8] and
+        sam int32[n, 4] parallel to records; sam_lines turns the lot into text.  reads: an interleaved batch (reads 2k and
+        2k + 1 are mates) in any form map_records takes, or a tuple (reads1, reads2) of two batches of equally many reads,
+        each in such a form, which text_reads.interleave_reads makes one.  pair_options: a dict of pair_alignments' options."""
+        import torch
+        from .text_reads import interleave_reads
+        ix = self.matcher.index(self.lut.lut_size)
+        if isinstance(reads, tuple) and len(reads) == 2 and all(isinstance(r, (list, tuple)) for r in reads):
+            ix._need_device()
+            one, two = (self._csr_reads(r, split_breaks) for r in reads)
+            reads = interleave_reads((ix._as_dev(one[0], torch.uint8), ix._as_dev(one[1], torch.int64)), two)
+        csr = self._csr_reads(reads, split_breaks)
+        opts = dict(align_options or {})
+        mems, chains, aln = self.find_alignments(csr, minimum_length, contigs, both_strands, split_breaks, max_occ, opts, by_score=False,
+                                                 **chain_options)
+        sel_offsets, sel, records, klass = ix.select_alignments(csr[1], chains[0], chains[1], aln, contigs, both_strands,
+                                                                **(select_options or {}))[:4]
+        offs, cigar, info = ix.chain_cigars(csr, mems[0], mems[1], chains, aln, sel, contigs, both_strands, **opts)
+        pairs, sam, _ = ix.pair_alignments(sel_offsets, records, klass, **(pair_options or {}))
+        return records, sel_offsets, offs, cigar, info, pairs, sam
+
     def locate_contigs(self, contigs, rows):
         """SMEM rows (start, end, lo, hi) of any find_smems* call -> (hit_offsets, hits int32[T, 2] = (contig, 1-based
         offset), dropped): GenieIndex.locate_contigs.  The rows stay SMEMs of the concatenation; occurrences that bridge two

@@ -125,6 +125,32 @@ def record_names(data, record_starts):
     return names
 
 
+def interleave_reads(csr1, csr2):
+    """Two batches (bases, read_offsets) of equally many reads -> the interleaved batch (bases uint8, read_offsets int64[2n+1]):
+    read 2k is read k of the first and read 2k + 1 read k of the second, the convention of the paired calls, so the two files
+    of a paired run become one batch.  Torch calls on the tensors' device only: nothing per read on the host."""
+    (b1, o1), (b2, o2) = csr1, csr2
+    o1 = torch.as_tensor(o1).to(torch.int64).reshape(-1)
+    dev = o1.device
+    o2 = torch.as_tensor(o2).to(device=dev, dtype=torch.int64).reshape(-1)
+    b1 = torch.as_tensor(b1).to(device=dev, dtype=torch.uint8).reshape(-1)
+    b2 = torch.as_tensor(b2).to(device=dev, dtype=torch.uint8).reshape(-1)
+    if o1.numel() < 1 or o1.numel() != o2.numel():
+        raise ValueError("the two batches must hold equally many reads")
+    n = o1.numel() - 1
+    len1, len2 = o1[1:] - o1[:-1], o2[1:] - o2[:-1]
+    offsets = torch.zeros(2 * n + 1, dtype=torch.int64, device=dev)
+    offsets[1:] = torch.cumsum(torch.stack([len1, len2], 1).reshape(-1), 0)
+    # per base of a batch: how far its read moved; the bases of a batch are those its offsets name, from position 0 on
+    shifts = [torch.repeat_interleave(offsets[first:2 * n:2] - o[:-1], lens) for o, lens, first in ((o1, len1, 0), (o2, len2, 1))]
+    if shifts[0].numel() > b1.numel() or shifts[1].numel() > b2.numel():
+        raise ValueError("read_offsets name more bases than there are")
+    bases = torch.empty(shifts[0].numel() + shifts[1].numel(), dtype=torch.uint8, device=dev)
+    for b, shift in zip((b1, b2), shifts):
+        bases[torch.arange(shift.numel(), device=dev) + shift] = b[:shift.numel()]
+    return bases, offsets
+
+
 def default_byte_codes():
     """A C G T -> 0 1 2 3, every other byte 4."""
     table = np.full(256, 4, np.uint8)

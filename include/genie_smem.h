@@ -902,6 +902,91 @@ int genie_select_alignments(const genie_index *ix, const int64_t *d_contig_offse
                             int64_t *d_totals,              /* 4, may be NULL */
                             void *d_workspace, int64_t workspace_bytes, void *stream);
 
+/* The alignments of paired-end reads: for every pair of mates, which of their candidate records of genie_select_alignments go
+ * together, a pair mapping quality, and SAM's per-record fields (flag, mapq, mate, template length) of every record.
+ * Everything is integer and deterministic: a POLICY, expressed through eight scalars, not a model.
+ * Inputs:
+ *   ix       used for the device and the launch sizes, as genie_select_alignments uses it.
+ *   N        the number of reads, even (GENIE_E_INVALID otherwise); P = N / 2.  Mate m in {0, 1} of pair k is read 2 k + m: the
+ *            interleaved convention, as GENIE_TEXT_FASTQ gives it on an interleaved file.
+ *   records  d_sel_offsets[N + 1], d_records (12 int32 per record) and n_records: genie_select_alignments' outputs.
+ *            R = min(d_sel_offsets[N], n_records); only records j < R exist for this call.
+ *   class    d_class (4 int32 per chain) and cap_chains as genie_select_alignments wrote them.  Only column 1 (parent) is read,
+ *            at index records[j].chain clamped to [0, cap_chains); with cap_chains == 0 no secondary is a candidate.
+ * No contig table is needed: a record carries its contig and its 1-based offset inside it.
+ * Parameters (int32; the call has no defaults): orient in [1, 7]: bit 0 FR, bit 1 RF, bit 2 same strand; isize_min, isize_max,
+ * isize_mean each in [0, 2^30] with isize_min <= isize_max; pen_slope in [0, 65536]; pen_max in [0, 2^20]; pen_unpaired in
+ * [0, 2^20]; mapq_boost in [0, 60].  Anything outside its range gives GENIE_E_INVALID.
+ * Candidates.  The records of read r are the rows [so[r], so[r + 1]) of d_sel_offsets cut to [0, R); its HEAD is the first of
+ * them, after genie_select_alignments the kind-0 primary.  A record is a candidate iff it is the head, or it has kind 2 and
+ * d_class[chain].parent equals the head's chain.  Supplementary records (kind 1) and secondaries of a supplementary are never
+ * candidates.  For a record: b = offset - 1, e = b + r_span, s = strand, w = score.
+ * Combination.  A candidate x of mate 0 with a candidate y of mate 1.  Without the same contig the combination has no type.
+ * span = max(e_x, e_y) - min(b_x, b_y).  With opposite strands, f the strand-0 record and r the strand-1 record, the type is
+ * the first that holds of: f.b <= r.b and f.e <= r.e: FR (0); r.b <= f.b and r.e <= f.e: RF (1); otherwise (one strictly inside
+ * the other) none (3).  With equal strands the type is "same" (2).  A combination is CONCORDANT iff its type's bit is set in
+ * orient (type 3 never is) and isize_min <= span <= isize_max.  Its value is
+ *   W = w_x + w_y - min(pen_max, floor(|span - isize_mean| pen_slope / 256))
+ * in int64; stored columns are clamped to the int32 range.
+ * Decision per pair.  W1 is the value of the best concordant combination, the key order being (W descending, x's record index
+ * ascending, y's ascending); W2 the largest W among the OTHER concordant combinations, 0 when there is none; with both heads
+ * present U = w(head 0) + w(head 1) - pen_unpaired.  The pair is PROPER iff both mates have records, a concordant combination
+ * exists and W1 >= U.  Equality is proper.  For a proper pair the CHOSEN record of each mate is x*, y* of the best combination and
+ *   pair_mapq = 0 if W1 <= 0, else floor(60 (W1 - min(max(W2, U, 0), W1)) / W1).
+ * Otherwise the chosen record of a mate that has records is its head; a mate without records has none (-1).
+ * Outputs, all in caller buffers:
+ *   d_pairs   8 int32 per pair, 16-byte aligned: (rec0, rec1, flags, pair_score, sub_score, isize, n_concordant, type)
+ *             rec0, rec1: the global record indices of the chosen records, or -1.  flags: bit 1 proper; bit 2 mate 0 has
+ *             records; bit 4 mate 1 has records; bit 8 mate 0's chosen record is not its head; bit 16 the same for mate 1.
+ *             pair_score = W1 when a concordant combination exists, else 0; sub_score = W2; isize and type: the span and type of
+ *             the two chosen records when both exist and share a contig, otherwise 0 and -1; n_concordant clamped to int32.
+ *   d_sam     4 int32 per record, 16-byte aligned, parallel to d_records, written for every j < R:
+ *             (flag, mapq, mate_record, tlen)
+ *             flag, in SAM's bits: 0x1 always; 0x2 on every record of a proper pair; 0x8 the mate has no chosen record; 0x10 the
+ *             record's strand is 1; 0x20 the mate's chosen record exists and has strand 1; 0x40 / 0x80 mate 0 / mate 1; 0x800
+ *             kind 1; 0x100 every record that is neither chosen nor kind 1 (a displaced head is one of those).
+ *             mapq: a chosen record of a proper pair max(q, min(pair_mapq, q + mapq_boost)), q its own mapq column clamped to
+ *             [0, 60]; a chosen record otherwise q; kind 1 its own; all others 0.
+ *             mate_record: the mate's chosen record, or -1.
+ *             tlen: 0 unless mate_record >= 0 and the contigs agree; then the span of this record and the mate's chosen one,
+ *             positive if this record's b is smaller, negative if larger, at equal b positive for mate 0 and negative for mate 1.
+ *             Rows at or past R are left untouched.
+ *   d_totals  4 int64, 8-byte aligned, may be NULL: {pairs with both mates mapped, proper pairs, mates whose chosen record is not
+ *             their head, pairs with exactly one mate mapped}; it stays on the device
+ * No atomic decides a value: the outputs are a function of the inputs alone.  Garbage records or class rows give undefined
+ * values, but no access outside the declared sizes and no unbounded loop: the record ranges are clamped to [0, R] and ordered,
+ * the chain index is clamped, and a pair's work is bounded by the product of its record counts.
+ * Checked before the device check, so on any handle, GENIE_E_INVALID: a null ix, d_sel_offsets or d_pairs; an odd or negative N,
+ * a negative size; a null d_records or d_sam with n_records > 0; a null d_class with cap_chains > 0; a parameter outside its
+ * range; d_records, d_class, d_pairs or d_sam not 16-byte, d_sel_offsets or d_totals not 8-byte aligned.  Then GENIE_E_TOO_LONG
+ * for N or n_records above 2^31 - 1: reads and records are named by an int32.  Then, for N > 0, a d_workspace that is null, not
+ * 256-byte aligned or smaller than genie_pair_alignments_workspace_bytes(N, n_records) gives GENIE_E_CAPACITY.  Then
+ * GENIE_E_NO_DEVICE.  The record offsets are checked on the device as genie_select_alignments checks its chain offsets
+ * (GENIE_E_INVALID), at the cost of the call's only synchronisation of `stream`.  N == 0 writes zero totals and nothing else.
+ * The workspace function returns GENIE_E_INVALID for negative arguments, is a multiple of 256 and monotone in both: 48 bytes per
+ * pair (the wide mark 4, its mapping quality 4, its row in the list of wide pairs twice 16, that list's offset 8) and 8 per 1024
+ * pairs (the scan), each piece rounded up to 256 on its own, and 256 for the verdict of the offset check; nothing per record.
+ * Kernels: a pair whose record counts multiply to at most GENIE_PAIR_LANE_MAX is decided by one lane; the others are compacted
+ * into a list and run one wave each, lanes over the flattened combinations, the values of the first GENIE_PAIR_TILE records of
+ * each mate in LDS and those beyond read from d_records; the best combination is an arg-max reduction, W2 one more over each
+ * lane's two largest values; then one lane per record writes its d_sam row.  Cost of a pair of a x b records: about
+ * ceil(a b / 64) wave steps. */
+#define GENIE_PAIR_LANE_MAX 64
+#define GENIE_PAIR_TILE 256
+int64_t genie_pair_alignments_workspace_bytes(int64_t N, int64_t n_records);
+int genie_pair_alignments(const genie_index *ix, int64_t N,
+                          const int64_t *d_sel_offsets,     /* N + 1 */
+                          const int32_t *d_records,         /* 12 * n_records, 16-byte aligned */
+                          int64_t n_records,
+                          const int32_t *d_class,           /* 4 * cap_chains, 16-byte aligned */
+                          int64_t cap_chains,
+                          int32_t orient, int32_t isize_min, int32_t isize_max, int32_t isize_mean, int32_t pen_slope,
+                          int32_t pen_max, int32_t pen_unpaired, int32_t mapq_boost,
+                          int32_t *d_pairs,                 /* 8 * N / 2, 16-byte aligned */
+                          int32_t *d_sam,                   /* 4 * n_records, 16-byte aligned */
+                          int64_t *d_totals,                /* 4, may be NULL */
+                          void *d_workspace, int64_t workspace_bytes, void *stream);
+
 /* Matching statistics and SMEMs that are EXACT WITH RESPECT TO THE SEQUENCE SET.  genie_match_stats and the SMEM calls on a
  * reference of several sequences answer for the concatenation; genie_locate_contigs then drops the occurrences that bridge
  * two sequences, and with them seeds.  Contigs ACGT | TTGA and the read CGTT: the concatenation holds CGTT once, across the
