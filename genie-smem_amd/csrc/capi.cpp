@@ -801,6 +801,72 @@ int genie_pair_alignments(const genie_index *ix, int64_t N, const int64_t *d_sel
     return launch_pair_alignments(ix, b, {d_pairs, d_sam, d_totals}, d_workspace, stream);
 }
 
+int64_t genie_rescue_windows_workspace_bytes(int64_t N)
+{
+    if (N < 0) return (int64_t)GENIE_E_INVALID;
+    return rescue_windows_workspace_bytes(N);
+}
+
+int genie_rescue_windows(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs, const int64_t *d_read_offsets,
+                         int64_t N, const int64_t *d_sel_offsets, const int32_t *d_records, int64_t n_records, const int32_t *d_pairs,
+                         int32_t orient, int32_t isize_max, int32_t min_anchor_score, int32_t *d_windows, int64_t *d_totals,
+                         void *d_workspace, int64_t workspace_bytes, void *stream)
+{
+    // argument checks first: they need no device image
+    if (!ix || !d_sel_offsets) return GENIE_E_INVALID;
+    if (N < 0 || (N & 1) != 0 || n_records < 0 || workspace_bytes < 0) return GENIE_E_INVALID;
+    if (N > 0 && (!d_read_offsets || !d_pairs || !d_windows)) return GENIE_E_INVALID;
+    if (n_records > 0 && !d_records) return GENIE_E_INVALID;
+    if (orient < 1 || orient > 7 || isize_max < 1 || isize_max > GENIE_WINDOW_MAX / 2 || min_anchor_score < 0 ||
+        min_anchor_score > (1 << 30))
+        return GENIE_E_INVALID;
+    if (misaligned(d_records, 15) || misaligned(d_pairs, 15) || misaligned(d_read_offsets, 7) || misaligned(d_sel_offsets, 7) ||
+        misaligned(d_windows, 7) || misaligned(d_totals, 7))
+        return GENIE_E_INVALID;
+    // the table is optional: null with n_contigs == 0, or a table as every contig call takes it
+    if (!d_contig_offsets && n_contigs != 0) return GENIE_E_INVALID;
+    if (d_contig_offsets)
+        if (int rc = contig_args(d_contig_offsets, n_contigs)) return rc;
+    // reads and records are named by an int32 in d_pairs
+    if (N > 0x7fffffffll || n_records > 0x7fffffffll) return GENIE_E_TOO_LONG;
+    if (N > 0 && (!d_workspace || misaligned(d_workspace, 255) || workspace_bytes < rescue_windows_workspace_bytes(N)))
+        return GENIE_E_CAPACITY;
+    if (int rc = ready(ix)) return rc;
+    const RescueBatch b{N, d_read_offsets, d_sel_offsets, d_records, n_records, d_pairs, orient, isize_max, min_anchor_score};
+    return launch_rescue_windows(ix, {d_contig_offsets, n_contigs}, b, d_windows, d_totals, d_workspace, stream);
+}
+
+int64_t genie_window_mems_workspace_bytes(int64_t U)
+{
+    if (U < 0) return (int64_t)GENIE_E_INVALID;
+    return window_mems_workspace_bytes(U);
+}
+
+int genie_window_mems(const genie_index *ix, int32_t flags, const uint8_t *d_bases, const int64_t *d_read_offsets, int64_t N,
+                      int64_t total_bases, int64_t max_len, int64_t U, const int32_t *d_windows, int32_t min_len,
+                      const int64_t *d_in_offsets, const int32_t *d_in_rows, int64_t in_total_rows, int64_t *d_offsets, int32_t *d_rows,
+                      int64_t out_cap_rows, int32_t *d_status, int64_t *d_totals, void *d_workspace, int64_t workspace_bytes,
+                      void *stream)
+{
+    const CsrBatch b{flags, d_bases, d_read_offsets, N, total_bases, max_len, d_status, d_workspace, workspace_bytes};
+    // argument checks first: they need no device image
+    if (!ix || bad_batch(b, kReadFlags) || !d_offsets || !d_read_offsets) return GENIE_E_INVALID;
+    if (U < 0 || N > 0x7fffffffffffffffll / b.strands() || U != b.strand_reads() || out_cap_rows < 0 || in_total_rows < 0 ||
+        workspace_bytes < 0 || min_len < 1)
+        return GENIE_E_INVALID;
+    if ((U > 0 && !d_windows) || (d_in_offsets && in_total_rows > 0 && !d_in_rows)) return GENIE_E_INVALID;
+    if (misaligned(d_rows, 15) || misaligned(d_in_rows, 15) || misaligned(d_offsets, 7) || misaligned(d_in_offsets, 7) ||
+        misaligned(d_read_offsets, 7) || misaligned(d_windows, 7) || misaligned(d_totals, 7) || misaligned(d_status, 3))
+        return GENIE_E_INVALID;
+    // units are named by an int32 in the list of the units to search
+    if (U > 0x7fffffffll) return GENIE_E_TOO_LONG;
+    if (U > 0 && (!d_workspace || misaligned(d_workspace, 255) || workspace_bytes < window_mems_workspace_bytes(U)))
+        return GENIE_E_CAPACITY;
+    if (int rc = ready(ix)) return rc;
+    const WindowBatch wb{U, d_windows, min_len, d_in_offsets, d_in_rows, in_total_rows};
+    return launch_window_mems(ix, b, wb, {d_offsets, d_rows, out_cap_rows, d_totals}, stream);
+}
+
 int genie_contig_coords(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs, const int32_t *d_pos, int32_t stride,
                         int64_t count, int32_t *d_out, void *stream)
 {

@@ -517,6 +517,30 @@ struct PairOut {
 };
 int64_t pair_alignments_workspace_bytes(int64_t N, int64_t n_records);
 int launch_pair_alignments(const genie_index *ix, const PairBatch &b, const PairOut &out, void *ws, void *stream);
+// windows.inc: where to seed a mate again next to its partner, and the MEMs of strand-reads against windows of the reference
+struct RescueBatch {
+    int64_t N;                            // reads, even
+    const int64_t *read_offsets;          // N + 1
+    const int64_t *sel_offsets;           // N + 1
+    const int32_t *records;
+    int64_t n_records;
+    const int32_t *pairs;
+    int32_t orient, isize_max, min_anchor_score;
+};
+int64_t rescue_windows_workspace_bytes(int64_t N);
+int launch_rescue_windows(const genie_index *ix, const ContigTable &ctg, const RescueBatch &b, int32_t *d_windows, int64_t *d_totals,
+                          void *ws, void *stream);
+struct WindowBatch {
+    int64_t U;
+    const int32_t *windows;               // 2 per unit
+    int32_t min_len;
+    const int64_t *in_offsets;            // U + 1, or null: no input rows
+    const int32_t *in_rows;
+    int64_t in_total_rows;
+};
+int64_t window_mems_workspace_bytes(int64_t U);
+// the reads, the status and the workspace as the batch of a CSR call; out.offsets has U + 1 entries, out.totals three
+int launch_window_mems(const genie_index *ix, const CsrBatch &b, const WindowBatch &wb, const CsrRows &out, void *stream);
 // min_occ.inc: matching statistics and SMEMs of what occurs at least min_occ times
 int64_t match_stats_min_occ_workspace_bytes(int64_t N, int64_t total_bases, int32_t flags);
 int launch_match_stats_min_occ(const genie_index *ix, int32_t min_occ, const CsrBatch &b, int32_t *d_ms, int32_t *d_lohi,

@@ -1431,6 +1431,7 @@ int launch_locate(const genie_index *ix, const int32_t *d_lohi, int32_t stride, 
 #include "mems.inc"
 #include "chains.inc"
 #include "align.inc"
+#include "windows.inc"
 #include "ingest_tiles.inc"
 #include "text_reads.inc"
 #include "fasta_reads.inc"

@@ -924,6 +924,77 @@ class GenieIndex:
                   _ptr(klass) if kept else none, kept, *prm, _ptr(pairs), _ptr(sam) if n_rec else none, _ptr(totals), _ptr(ws), ws_bytes)
         return pairs[:n_reads // 2], sam[:n_rec], totals
 
+    def rescue_windows(self, read_offsets, sel_offsets, records, pairs, contigs=None, orient="fr", isize_max=1000, min_anchor_score=40):
+        """Where to seed a mate again next to its partner (genie_rescue_windows) -> (windows int32[2N, 2] = (wb, we), 0-based
+        and half-open in the concatenation, (0, 0) for none; totals int64[3] = (units with a window, pairs with at least one,
+        reads that are targets)) on the device.  Unit 2r + s is strand s of read r.  read_offsets as find_mems took them;
+        sel_offsets, records: select_alignments' first and third results; pairs: pair_alignments' first.  A mate of a pair that
+        is not proper is a target when the other mate's chosen record scores at least min_anchor_score; its windows are where
+        a record would have to lie to be concordant with that record under orient and isize_max (pair_alignments' options).
+        The defaults are this wrapper's; the C call has none."""
+        self._need_device()
+        read_offsets = self._as_dev(read_offsets, torch.int64).reshape(-1)
+        sel_offsets = self._as_dev(sel_offsets, torch.int64).reshape(-1)
+        records, pairs = self._as_dev(records, torch.int32), self._as_dev(pairs, torch.int32)
+        n_reads = sel_offsets.numel() - 1
+        if n_reads < 0 or n_reads % 2 or read_offsets.numel() != n_reads + 1:
+            raise ValueError("read_offsets and sel_offsets need N + 1 entries for an even number of reads: mates are interleaved")
+        if records.dim() != 2 or records.shape[1] != 12 or pairs.dim() != 2 or pairs.shape[1] != 8 or pairs.shape[0] != n_reads // 2:
+            raise ValueError("records must be [R, 12] and pairs [N / 2, 8], as select_alignments and pair_alignments return them")
+        table = (C.c_void_p(0), 0)
+        if contigs is not None:
+            off, table = self._contig_table(contigs)
+        mask = N.PAIR_ORIENT[orient] if isinstance(orient, str) else int(orient)
+        n_rec = records.shape[0]
+        none = C.c_void_p(0)
+        windows = torch.zeros((max(2 * n_reads, 1), 2), dtype=torch.int32, device=self.device)
+        totals = torch.empty(3, dtype=torch.int64, device=self.device)
+        ws, ws_bytes = self._workspace("genie_rescue_windows_workspace_bytes", n_reads)
+        self._run("genie_rescue_windows", *table, _ptr(read_offsets), n_reads, _ptr(sel_offsets), _ptr(records) if n_rec else none, n_rec,
+                  _ptr(pairs) if n_reads else none, mask, int(isize_max), int(min_anchor_score), _ptr(windows), _ptr(totals), _ptr(ws),
+                  ws_bytes)
+        return windows[:2 * n_reads], totals
+
+    def window_mems(self, bases, read_offsets, windows, min_len, offsets=None, rows=None, both_strands=False, split_breaks=False,
+                    rows_hint=None):
+        """The MEMs of every strand-read against its own window of the reference, merged into the MEM rows of the batch
+        (genie_window_mems) -> (offsets int64[U+1], mems int32[R, 4] = (start, end, pos, row), status int32[U], totals
+        int64[3] = (rows in all, window rows added, units over a cap)) on the device.  bases / read_offsets and the units as
+        find_mems; windows int32[U, 2] = (wb, we), 0-based and half-open, wb == we for none (rescue_windows' first result, or
+        any other); offsets / rows: the first two results of find_mems* for the same batch, or None.  A unit without a window
+        keeps its rows; one with a window gets the union of its rows and the MEMs of at least min_len bases against the window
+        alone, ordered by (start, pos, end), the new rows with row -1.  status 1: searched, 2: more than WINDOW_MAX_ROWS rows,
+        4: a read above MAX_READ_LEN (both keep their rows).  If the rows outnumber rows_hint the call is made again with room
+        for all."""
+        bases, read_offsets, n_reads, total, max_len, flags, strands = self._csr_call(bases, read_offsets, both_strands, split_breaks)
+        U = strands * n_reads
+        windows = self._as_dev(windows, torch.int32)
+        if windows.numel() != 2 * U:
+            raise ValueError("windows must be [U, 2], one row per strand-read")
+        if windows.numel() == 0:
+            windows = torch.zeros((1, 2), dtype=torch.int32, device=self.device)
+        none = C.c_void_p(0)
+        tail_in = (none, none, 0)
+        if offsets is not None:
+            in_offsets = self._as_dev(offsets, torch.int64).reshape(-1)
+            in_rows = self._as_dev(rows, torch.int32)
+            if in_offsets.numel() != U + 1 or in_rows.dim() != 2 or in_rows.shape[1] != 4:
+                raise ValueError("offsets must have U + 1 entries and rows be [R, 4], as find_mems returns them")
+            tail_in = (_ptr(in_offsets), _ptr(in_rows) if in_rows.shape[0] else none, in_rows.shape[0])
+        out_offsets = torch.empty(U + 1, dtype=torch.int64, device=self.device)
+        status = torch.empty(max(U, 1), dtype=torch.int32, device=self.device)
+        totals = torch.empty(3, dtype=torch.int64, device=self.device)
+        ws, ws_bytes = self._workspace("genie_window_mems_workspace_bytes", U)
+        cap_rows = int(rows_hint) if rows_hint else tail_in[2] + 8 * U
+        while True:
+            out = torch.empty((max(cap_rows, 1), 4), dtype=torch.int32, device=self.device)
+            self._run("genie_window_mems", flags, _ptr(bases), _ptr(read_offsets), n_reads, total, max_len, U, _ptr(windows), int(min_len),
+                      *tail_in, _ptr(out_offsets), _ptr(out), out.shape[0], _ptr(status), _ptr(totals), _ptr(ws), ws_bytes)
+            found = int(totals[0].item())
+            if found <= out.shape[0]:
+                return out_offsets, out[:found], status[:U], totals
+            cap_rows = found                      # capacity guess too small: rerun with the exact size
+
     def contig_coords(self, contigs, pos, stride=1):
         """1-based concatenation positions -> int32 [count, 2] = (contig, 1-based offset inside it) on the device
         (genie_contig_coords); (-1, -1) for a position outside [1, n].  pos: int32, flat; with stride > 1 every stride-th

@@ -302,13 +302,34 @@ class SMEM:
         ix = self.matcher.index(self.lut.lut_size)
         return ix.pair_alignments(sel_offsets, records, klass, **pair_options)
 
+    def rescue_windows(self, read_offsets, sel_offsets, records, pairs, contigs=None, **rescue_options):
+        """Where to seed a mate again next to its partner (genie_rescue_windows) -> (windows int32[2N, 2], totals):
+        GenieIndex.rescue_windows, which documents the options (orient, isize_max, min_anchor_score) and their defaults."""
+        ix = self.matcher.index(self.lut.lut_size)
+        return ix.rescue_windows(read_offsets, sel_offsets, records, pairs, contigs, **rescue_options)
+
+    def window_mems(self, reads, windows, minimum_length, offsets=None, rows=None, both_strands=False, split_breaks=False):
+        """The MEMs of every strand-read against its own window of the reference, merged into the rows of find_mems*
+        (genie_window_mems) -> (offsets, mems int32[R, 4], status, totals): GenieIndex.window_mems.  reads as find_mems takes
+        them; windows int32[U, 2] = (wb, we), one per strand-read; offsets / rows: find_mems*' first two results, or None."""
+        ix = self.matcher.index(self.lut.lut_size)
+        bases, read_offsets = self._csr_reads(reads, split_breaks)
+        return ix.window_mems(bases, read_offsets, windows, minimum_length, offsets, rows, both_strands, split_breaks)
+
     def map_pairs(self, reads, minimum_length, contigs=None, both_strands=True, split_breaks=False, max_occ=0, align_options=None,
-                  select_options=None, pair_options=None, **chain_options):
+                  select_options=None, pair_options=None, rescue=False, rescue_options=None, **chain_options):
         """Every alignment of every mate, paired: map_records on the interleaved batch, then pair_alignments on its records ->
         (records, sel_offsets, cigar_offsets, cigar, info, pairs, sam): map_records' five results, then pairs int32[P, 8] and
         sam int32[n, 4] parallel to records; sam_lines turns the lot into text.  reads: an interleaved batch (reads 2k and
         2k + 1 are mates) in any form map_records takes, or a tuple (reads1, reads2) of two batches of equally many reads,
-        each in such a form, which text_reads.interleave_reads makes one.  pair_options: a dict of pair_alignments' options."""
+        each in such a form, which text_reads.interleave_reads makes one.  pair_options: a dict of pair_alignments' options.
+        rescue=True (it needs both_strands) seeds the mates of pairs that are not proper again, next to their partner: after
+        the first pairing rescue_windows names the windows; where there is one, window_mems adds each window's MEMs of at
+        least rescue_options["min_len"] bases (12) to the rows of the first pass, and chaining, alignment, selection and pairing
+        run once more over the union, with the same options.  rescue_options: a dict of min_len, min_anchor_score (40) and
+        the orient and isize_max of rescue_windows (default: those of pair_options).  An eighth result then follows the
+        seven: (windows int32[2N, 2], status int32[2N], totals int64[3]) as rescue_windows and window_mems return them, status
+        and totals zero where no unit had a window."""
         import torch
         from .text_reads import interleave_reads
         ix = self.matcher.index(self.lut.lut_size)
@@ -322,9 +343,31 @@ class SMEM:
                                                  **chain_options)
         sel_offsets, sel, records, klass = ix.select_alignments(csr[1], chains[0], chains[1], aln, contigs, both_strands,
                                                                 **(select_options or {}))[:4]
+        if not rescue:
+            offs, cigar, info = ix.chain_cigars(csr, mems[0], mems[1], chains, aln, sel, contigs, both_strands, **opts)
+            pairs, sam, _ = ix.pair_alignments(sel_offsets, records, klass, **(pair_options or {}))
+            return records, sel_offsets, offs, cigar, info, pairs, sam
+        if not both_strands:
+            raise ValueError("rescue needs both_strands: a mate is sought on the strand its partner implies")
+        popts, ropts = dict(pair_options or {}), dict(rescue_options or {})
+        min_len, min_anchor = int(ropts.pop("min_len", 12)), int(ropts.pop("min_anchor_score", 40))
+        where = {key: ropts.pop(key) if key in ropts else popts[key] for key in ("orient", "isize_max") if key in ropts or key in popts}
+        if ropts:
+            raise TypeError(f"unknown rescue option {sorted(ropts)[0]!r}")
+        pairs, sam, _ = ix.pair_alignments(sel_offsets, records, klass, **popts)
+        windows, planned = ix.rescue_windows(csr[1], sel_offsets, records, pairs, contigs, min_anchor_score=min_anchor, **where)
+        status = torch.zeros(windows.shape[0], dtype=torch.int32, device=windows.device)
+        totals = torch.zeros(3, dtype=torch.int64, device=windows.device)
+        if int(planned[0].item()) > 0:                               # the one host read: is there anything to rescue?
+            offsets, rows, status, totals = ix.window_mems(csr[0], csr[1], windows, min_len, mems[0], mems[1], both_strands, split_breaks)
+            chains = self.chain_mems(offsets, rows, contigs, by_score=False, **chain_options)
+            mems = (offsets, rows)
+            aln, _ = self.align_chains(csr, offsets, rows, chains, contigs, both_strands, split_breaks, **opts)
+            sel_offsets, sel, records, klass = ix.select_alignments(csr[1], chains[0], chains[1], aln, contigs, both_strands,
+                                                                    **(select_options or {}))[:4]
+            pairs, sam, _ = ix.pair_alignments(sel_offsets, records, klass, **popts)
         offs, cigar, info = ix.chain_cigars(csr, mems[0], mems[1], chains, aln, sel, contigs, both_strands, **opts)
-        pairs, sam, _ = ix.pair_alignments(sel_offsets, records, klass, **(pair_options or {}))
-        return records, sel_offsets, offs, cigar, info, pairs, sam
+        return records, sel_offsets, offs, cigar, info, pairs, sam, (windows, status, totals)
 
     def locate_contigs(self, contigs, rows):
         """SMEM rows (start, end, lo, hi) of any find_smems* call -> (hit_offsets, hits int32[T, 2] = (contig, 1-based

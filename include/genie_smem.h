@@ -987,6 +987,152 @@ int genie_pair_alignments(const genie_index *ix, int64_t N,
                           int64_t *d_totals,                /* 4, may be NULL */
                           void *d_workspace, int64_t workspace_bytes, void *stream);
 
+/* Mate rescue, step 1: which strand-reads to seed again, and in which window of the reference.  genie_pair_alignments can only
+ * choose among the records that the global seeding produced; a mate without a MEM of min_len bases has none.  Its partner, where
+ * that has a record, fixes the mate's strand and places it within isize_max bases: this call writes that place down as a window
+ * per strand-read, and genie_window_mems (below) seeds the window with a short minimum length.  Everything is integer and
+ * deterministic.
+ * Inputs:
+ *   ix       for the reference length n, the device and the launch sizes.
+ *   contigs  d_contig_offsets, n_contigs as genie_align_chains takes them; NULL with n_contigs == 0: one contig [0, n).
+ *   reads    d_read_offsets[N + 1], used for the read lengths alone; N even (GENIE_E_INVALID otherwise), mate m of pair k is
+ *            read 2 k + m as in genie_pair_alignments.
+ *   records  d_sel_offsets[N + 1], d_records (12 int32 per record), n_records as genie_select_alignments wrote them;
+ *            R = min(d_sel_offsets[N], n_records) as in genie_pair_alignments.  Of d_sel_offsets only entry N is used.
+ *   d_pairs  8 int32 per pair, as genie_pair_alignments wrote it; columns 0 to 2 (rec0, rec1, flags) are read.
+ * Parameters (int32; the call has no defaults): orient in [1, 7] with genie_pair_alignments' bits (bit 0 FR, bit 1 RF, bit 2
+ * same strand); isize_max in [1, GENIE_WINDOW_MAX / 2]; min_anchor_score in [0, 2^30].
+ * Units.  U = 2 N: unit 2 r + s is strand s of read r; both strands are implied, as GENIE_READS_BOTH_STRANDS numbers them.
+ * Rule, per pair k and mate m (both mates may be targets):
+ *   1. Mate m is a TARGET iff the pair's proper bit (flags bit 1) is clear, the other mate has a chosen record a with 0 <= a < R,
+ *      and a's score (column 9) is >= min_anchor_score.  A target without bases (an empty read) gets no window.
+ *   2. Of a: its strand s_a (column 3, anything but 0 taken as 1), its contig c (column 4) clamped to [0, n_contigs), b =
+ *      offset - 1 (column 5), e = b + r_span (column 6), both inside the contig, and the contig's bounds [clo, chi) in the
+ *      concatenation, themselves clamped to 0 <= clo <= chi <= n.
+ *   3. The target's OPPOSITE-strand unit (s = 1 - s_a) gets a window iff orient has FR or RF: the hull of the allowed sides,
+ *        RIGHT [b, b + isize_max)   allowed iff (FR and s_a == 0) or (RF and s_a == 1),
+ *        LEFT  [e - isize_max, e)   allowed iff (FR and s_a == 1) or (RF and s_a == 0).
+ *   4. The target's SAME-strand unit (s = s_a) gets [e - isize_max, b + isize_max) iff orient has bit 2.
+ *   5. Both ends are clamped to [0, chi - clo], the window is cut to GENIE_WINDOW_MAX bases from its start and moved to the
+ *      concatenation by + clo; an empty window is none.
+ * Every other unit has no window.
+ * Property.  Let y be any record of the target on the contig of a whose combination with a is concordant under
+ * genie_pair_alignments' definition with the same orient and isize_max and any isize_min.  Then the reference interval [b_y, e_y)
+ * of y lies inside the window of y's unit: for type FR with a the forward record, b <= b_y and e_y - b = span <= isize_max
+ * (RIGHT); with a the reverse record, e_y <= e and e - b_y = span <= isize_max (LEFT); RF mirrors the two; with equal strands
+ * max(e, e_y) - min(b, b_y) <= isize_max bounds both ends.  isize_max <= GENIE_WINDOW_MAX / 2, so the cut of step 5 removes
+ * nothing while r_span >= 0.
+ * Outputs, in caller buffers:
+ *   d_windows  2 int32 per unit, 8-byte aligned: (wb, we), 0-based and half-open in the concatenation; (0, 0): no window.
+ *              Written for all 2 N units.
+ *   d_totals   3 int64, 8-byte aligned, may be NULL: {units with a window, pairs with at least one, reads that are targets}; it
+ *              stays on the device.
+ * Garbage records or pair rows give undefined windows, but no access outside the declared sizes, and every window written
+ * satisfies 0 <= wb <= we <= n and we - wb <= GENIE_WINDOW_MAX.  No atomic decides a value.
+ * Checked before the device check, so on any handle, in this order.  GENIE_E_INVALID: a null ix or d_sel_offsets; a negative
+ * or odd N, a negative size; for N > 0 a null d_read_offsets, d_pairs or d_windows; a null d_records with n_records > 0; a
+ * parameter outside its range; d_records or d_pairs not 16-byte, d_read_offsets, d_sel_offsets, d_windows or d_totals not 8-byte
+ * aligned; a null table with n_contigs != 0, a table not 8-byte aligned or with n_contigs < 1 (GENIE_E_TOO_LONG for n_contigs
+ * above 2^31 - 2).  Then GENIE_E_TOO_LONG for N or n_records above 2^31 - 1.  Then, for N > 0, a d_workspace that is null, not
+ * 256-byte aligned or smaller than genie_rescue_windows_workspace_bytes(N) gives GENIE_E_CAPACITY.  Then GENIE_E_NO_DEVICE.  The
+ * record offsets are checked on the device as genie_pair_alignments checks them (GENIE_E_INVALID), at the cost of the call's only
+ * synchronisation of `stream`.  N == 0 writes zero totals and nothing else.
+ * The workspace function returns GENIE_E_INVALID for a negative N, is a multiple of 256 and monotone: 256 bytes for the verdict
+ * of the offset check and 4 bytes per read (the target mark), rounded up to 256.
+ * Kernels: one lane per read, then one block for the totals.  Cost: three 16-byte loads per read. */
+#define GENIE_WINDOW_MAX 65536       /* bases of a window: a choice (a window never spans more than two inserts), not a measurement */
+int64_t genie_rescue_windows_workspace_bytes(int64_t N);
+int genie_rescue_windows(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs,
+                         const int64_t *d_read_offsets,    /* N + 1 */
+                         int64_t N,
+                         const int64_t *d_sel_offsets,     /* N + 1 */
+                         const int32_t *d_records,         /* 12 * n_records, 16-byte aligned */
+                         int64_t n_records,
+                         const int32_t *d_pairs,           /* 8 * N / 2, 16-byte aligned */
+                         int32_t orient, int32_t isize_max, int32_t min_anchor_score,
+                         int32_t *d_windows,               /* 2 * 2 N, 8-byte aligned */
+                         int64_t *d_totals,                /* 3, may be NULL */
+                         void *d_workspace, int64_t workspace_bytes, void *stream);
+
+/* Mate rescue, step 2, and a general call: the MEMs of strand-reads against WINDOWS of the reference, added to the MEM rows of
+ * the batch.  Any windows will do, not only genie_rescue_windows'.  The index is not consulted: a window is compared with the
+ * strand-read base for base, so a min_len that would be meaningless against the whole reference (12, say) costs the window's
+ * size and not the number of its occurrences in the genome.  The rows that come out are ordinary MEM rows: genie_chain_mems and
+ * everything behind it run on them unchanged.
+ * Inputs:
+ *   ix       for the packed reference and its length n.
+ *   reads    flags, d_bases, d_read_offsets, N, total_bases, max_len exactly as genie_align_chains takes them:
+ *            GENIE_READS_BOTH_STRANDS gives S = 2 (else 1) with unit u = S i + s read i on strand s, strand 1 the reverse
+ *            complement, built on the fly; GENIE_READS_SPLIT_BREAKS is accepted and changes nothing.  U must equal S N.
+ *   windows  d_windows: 2 int32 per unit, (wb, we), 0-based and half-open.  The call clamps both ends to [0, n]; we <= wb after
+ *            that is an empty window (so is we < wb before it); then we is cut to wb + GENIE_WINDOW_MAX.
+ *   min_len  m >= 1.
+ *   input rows (optional)  d_in_offsets[U + 1], d_in_rows (4 int32 per row), in_total_rows: rows as genie_find_mems* wrote them.
+ *            d_in_offsets == NULL: no unit has input rows.  The offsets are checked on the device as genie_chain_mems checks
+ *            its row offsets (first 0, non-decreasing, last <= in_total_rows, no unit above 2^31 - 1 rows).
+ * Window rows of unit u.  Q is the strand-read, L its length, [wb, we) its window.  A window row is every (p, t, l) with
+ *   l >= m, wb <= t and t + l <= we;
+ *   Q[p .. p+l) == T[t .. t+l) base for base, every query code <= 3 (a code > 3 differs from everything);
+ *   left-maximal INSIDE THE WINDOW   p == 0, or t == wb, or Q[p-1] != T[t-1];
+ *   right-maximal                    p + l == L, or t + l == we, or Q[p+l] != T[t+l]:
+ * the MEMs of Q against T[wb .. we) taken as a reference of its own.  The row is (p, p + l, t + 1, -1): no suffix-array row is
+ * looked up.  A MEM of the whole reference that reaches beyond the window appears clipped to it.
+ * Output of a unit.  Without a window: its input rows, byte for byte and in their order.  With a window: the set union of its
+ * input rows and its window rows on the triple (start, end, pos), sorted ascending by (start, pos, end), all three as signed
+ * integers; column 3 is that of the first input row that has the triple, else -1.  The start order is what genie_chain_mems
+ * needs; the rest makes the output a function of the inputs alone.
+ * Caps, which bound the work and are no policy.  d_status[u] is 0 for a unit without a window and else exactly one of
+ *   1  searched: the unit's output is the union above;
+ *   2  its input rows plus its window rows, counted before the union, exceed GENIE_WINDOW_MAX_ROWS: it keeps its input rows
+ *      as they are;
+ *   4  L > GENIE_MAX_READ_LEN: it keeps its input rows as they are.
+ * GENIE_WINDOW_MAX and GENIE_WINDOW_MAX_ROWS are choices sized to LDS (the rows of a unit are ranked in a 32 KB table of one
+ * wave), not measurements.
+ * Outputs, all in caller buffers:
+ *   d_offsets  U + 1 int64, 8-byte aligned; [U] holds the true total even past out_cap_rows
+ *   d_rows     4 int32 per row, 16-byte aligned, out_cap_rows of them; NULL is the sizing call (offsets, status and totals are
+ *              written all the same).  Rows past the capacity are dropped.
+ *   d_status   U int32, may be NULL
+ *   d_totals   3 int64, 8-byte aligned, may be NULL: {rows in all, window rows added after the union, units over a cap}
+ * Memory-safe on any windows and any input rows: the loops are bounded by L, the window length and the row cap, and rows that
+ * break genie_find_mems' form come out with undefined order but inside the declared sizes.  One integer atomicAdd in LDS hands
+ * out the places of the rows found in a wave's table; it decides no value, since those rows are distinct and the output order
+ * is the rank of the keys.
+ * Checked before the device check, so on any handle, in this order.  GENIE_E_INVALID: a null ix, d_offsets or d_read_offsets, a
+ * null d_bases (total_bases > 0), a negative N, total_bases or max_len, max_len above 2^31 - 1, an unknown flag bit; a negative
+ * U, out_cap_rows, in_total_rows or workspace_bytes, U != S N, min_len < 1; a null d_windows with U > 0, a null d_in_rows with
+ * d_in_offsets and in_total_rows > 0; d_rows or d_in_rows not 16-byte, d_offsets, d_in_offsets, d_read_offsets, d_windows or
+ * d_totals not 8-byte, d_status not 4-byte aligned.  Then GENIE_E_TOO_LONG for U above 2^31 - 1.  Then, for U > 0, a
+ * d_workspace that is null, not 256-byte aligned or smaller than genie_window_mems_workspace_bytes(U) gives GENIE_E_CAPACITY.
+ * Then GENIE_E_NO_DEVICE.  Bad read offsets or input row offsets give GENIE_E_INVALID, found on the device at the cost of the
+ * call's only synchronisation of `stream`.  U == 0 writes d_offsets[0] = 0 and zero totals.
+ * The workspace function returns GENIE_E_INVALID for a negative U, is a multiple of 256 and monotone: 56 bytes per unit (its
+ * clamped window 8, the search mark 4, its row count 4, its new rows 4, its status 4, its row in the list of units to search
+ * twice 16), that list's offsets 8 (U + 1) and 8 per 1024 units (the scan), each piece rounded up to 256 on its own, and 256 for
+ * the verdict of the offset checks; nothing per row.
+ * Kernels: the units with a window are compacted into a list and run one wave each (blocks of one wave: 37 KB of LDS, four
+ * to a CU).  The wave packs the strand-read to 2 bits a base in LDS, with the mask of its codes > 3, and takes the L + B - 1
+ * diagonals d = t - p of a window of B bases 64 at a time; a lane walks its diagonal in 32-base words, the XOR of the query
+ * word with the reference word folded to a bit per base, the runs taken by bit scans.  The rows are ranked by counting the
+ * smaller keys in LDS.  Count, scan, fill: the walk runs twice.  Cost of a unit: about ceil((L + B - 1) / 64) ceil(L / 32) wave
+ * steps a pass, and K^2 / 64 for the rank of its K rows. */
+#define GENIE_WINDOW_MAX_ROWS 2048
+int64_t genie_window_mems_workspace_bytes(int64_t U);
+int genie_window_mems(const genie_index *ix, int32_t flags, const uint8_t *d_bases, const int64_t *d_read_offsets,
+                      int64_t N, int64_t total_bases, int64_t max_len,
+                      int64_t U,
+                      const int32_t *d_windows,        /* 2 * U, 8-byte aligned */
+                      int32_t min_len,
+                      const int64_t *d_in_offsets,     /* U + 1, may be NULL: no input rows */
+                      const int32_t *d_in_rows,        /* 4 * in_total_rows, 16-byte aligned */
+                      int64_t in_total_rows,
+                      int64_t *d_offsets,              /* U + 1 */
+                      int32_t *d_rows,                 /* 4 * out_cap_rows, 16-byte aligned; may be NULL: counting only */
+                      int64_t out_cap_rows,
+                      int32_t *d_status,               /* U, may be NULL */
+                      int64_t *d_totals,               /* 3, may be NULL */
+                      void *d_workspace, int64_t workspace_bytes, void *stream);
+
 /* Matching statistics and SMEMs that are EXACT WITH RESPECT TO THE SEQUENCE SET.  genie_match_stats and the SMEM calls on a
  * reference of several sequences answer for the concatenation; genie_locate_contigs then drops the occurrences that bridge
  * two sequences, and with them seeds.  Contigs ACGT | TTGA and the read CGTT: the concatenation holds CGTT once, across the
