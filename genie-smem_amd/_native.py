@@ -41,6 +41,8 @@ PAIR_LANE_MAX, PAIR_TILE = 64, 256                  # genie_pair_alignments: one
 PAIR_ORIENT = {"fr": 1, "rf": 2, "same": 4, "any": 7}
 WINDOW_MAX, WINDOW_MAX_ROWS = 65536, 2048           # genie_window_mems: bases of a window, rows of a searched unit (sized to LDS)
 WINDOW_SEARCHED, WINDOW_ROW_CAP, WINDOW_TOO_LONG = 1, 2, 4   # its status values
+SAM_NM, SAM_AS, SAM_MD, SAM_MC, SAM_MQ = 1, 2, 4, 8, 16      # genie_sam_text: the tags, written in this order
+SAM_NO_SEQ = 1                                      # its flag
 
 # every symbol include/genie_smem.h declares (tests check the library exports all of them)
 SYMBOLS = [
@@ -69,6 +71,7 @@ SYMBOLS = [
     "genie_pair_alignments", "genie_pair_alignments_workspace_bytes",
     "genie_rescue_windows", "genie_rescue_windows_workspace_bytes",
     "genie_window_mems", "genie_window_mems_workspace_bytes",
+    "genie_sam_text", "genie_sam_text_workspace_bytes",
     "genie_reads_from_text", "genie_reads_from_text_tmp_bytes",
     "genie_reads_from_fasta", "genie_reads_from_fasta_tmp_bytes",
     "genie_reference_segments", "genie_reference_segments_tmp_bytes", "genie_segment_coords",
@@ -94,7 +97,7 @@ class GenieError(RuntimeError):
 
 def build(force=False):
     """Compile libgenie_smem.so for gfx950 with hipcc (csrc/Makefile), in-tree."""
-    srcs = [os.path.join(CSRC, f) for f in ("kernels.hip", "index_build.hip", "short_read_kernel.inc", "match_table_kernel.inc", "match_table_body.inc", "match_table_long_body.inc", "split_reads.inc", "long_reads.inc", "long_units.inc", "lu_seg_body.inc", "exact_match.inc", "contigs.inc", "fwd_step.inc", "contig_stats.inc", "min_occ.inc", "mems.inc", "chains.inc", "align.inc", "cigars.inc", "select.inc", "pairs.inc", "windows.inc", "ingest_tiles.inc", "text_reads.inc", "fasta_reads.inc", "segments.inc", "capi.cpp", "index_host.cpp", "genie_internal.h", "Makefile")]
+    srcs = [os.path.join(CSRC, f) for f in ("kernels.hip", "index_build.hip", "short_read_kernel.inc", "match_table_kernel.inc", "match_table_body.inc", "match_table_long_body.inc", "split_reads.inc", "long_reads.inc", "long_units.inc", "lu_seg_body.inc", "exact_match.inc", "contigs.inc", "fwd_step.inc", "contig_stats.inc", "min_occ.inc", "mems.inc", "chains.inc", "align.inc", "cigars.inc", "select.inc", "pairs.inc", "windows.inc", "sam_text.inc", "ingest_tiles.inc", "text_reads.inc", "fasta_reads.inc", "segments.inc", "capi.cpp", "index_host.cpp", "genie_internal.h", "Makefile")]
     srcs.append(os.path.join(os.path.dirname(_PKG), "include", "genie_smem.h"))
     newest = max(os.path.getmtime(s) for s in srcs)
     if force or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < newest:
@@ -192,6 +195,9 @@ def lib():
         "genie_rescue_windows": (C.c_int, [vp, vp, i64, vp, i64, vp, vp, i64, vp, i32, i32, i32, vp, vp, vp, i64, vp]),
         "genie_window_mems_workspace_bytes": (i64, [i64]),
         "genie_window_mems": (C.c_int, [vp, i32, vp, vp, i64, i64, i64, i64, vp, i32, vp, vp, i64, vp, vp, i64, vp, vp, vp, i64, vp]),
+        "genie_sam_text_workspace_bytes": (i64, [i64, i64]),
+        "genie_sam_text": (C.c_int, [vp, vp, i64, vp, vp, i64, i64, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp, vp, i64, vp, vp, i64, i32, i32,
+                                     vp, vp, i64, vp, vp, i64, vp]),
         "genie_reads_from_text_tmp_bytes": (i64, [i64, i64]),
         "genie_reads_from_text": (C.c_int, [vp, i64, i32, i32, vp, vp, i64, vp, i64, vp, vp, i64, vp]),
         "genie_reads_from_fasta_tmp_bytes": (i64, [i64, i64]),

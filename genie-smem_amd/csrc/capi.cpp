@@ -867,6 +867,52 @@ int genie_window_mems(const genie_index *ix, int32_t flags, const uint8_t *d_bas
     return launch_window_mems(ix, b, wb, {d_offsets, d_rows, out_cap_rows, d_totals}, stream);
 }
 
+int64_t genie_sam_text_workspace_bytes(int64_t N, int64_t n_records)
+{
+    if (N < 0 || n_records < 0) return (int64_t)GENIE_E_INVALID;
+    return sam_text_workspace_bytes(N, n_records);
+}
+
+int genie_sam_text(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs, const uint8_t *d_bases,
+                   const int64_t *d_read_offsets, int64_t N, int64_t total_bases, const uint8_t *d_quals, const int64_t *d_sel_offsets,
+                   const int32_t *d_records, int64_t n_records, const int32_t *d_sam, const int32_t *d_info,
+                   const int64_t *d_cigar_offsets, const uint32_t *d_cigar, int64_t n_ops, const uint8_t *d_names,
+                   const int64_t *d_name_offsets, int64_t name_bytes, const uint8_t *d_contig_names,
+                   const int64_t *d_contig_name_offsets, int64_t contig_name_bytes, int32_t tags, int32_t flags,
+                   int64_t *d_line_offsets, uint8_t *d_text, int64_t cap_text, int64_t *d_totals, void *d_workspace,
+                   int64_t workspace_bytes, void *stream)
+{
+    // argument checks first: they need no device image
+    if (!ix || !d_read_offsets || !d_sel_offsets || !d_name_offsets || !d_contig_name_offsets || !d_line_offsets) return GENIE_E_INVALID;
+    if (N < 0 || total_bases < 0 || n_records < 0 || n_ops < 0 || name_bytes < 0 || contig_name_bytes < 0 || cap_text < 0 ||
+        workspace_bytes < 0)
+        return GENIE_E_INVALID;
+    if (d_sam && (N & 1) != 0) return GENIE_E_INVALID;
+    if ((tags & ~(GENIE_SAM_NM | GENIE_SAM_AS | GENIE_SAM_MD | GENIE_SAM_MC | GENIE_SAM_MQ)) != 0 || (flags & ~GENIE_SAM_NO_SEQ) != 0)
+        return GENIE_E_INVALID;
+    if ((total_bases > 0 && !d_bases) || (name_bytes > 0 && !d_names) || (contig_name_bytes > 0 && !d_contig_names) ||
+        (n_ops > 0 && !d_cigar))
+        return GENIE_E_INVALID;
+    if (n_records > 0 && (!d_records || !d_info || !d_cigar_offsets)) return GENIE_E_INVALID;
+    if (misaligned(d_records, 15) || misaligned(d_sam, 15) || misaligned(d_info, 15) || misaligned(d_read_offsets, 7) ||
+        misaligned(d_sel_offsets, 7) || misaligned(d_cigar_offsets, 7) || misaligned(d_name_offsets, 7) ||
+        misaligned(d_contig_name_offsets, 7) || misaligned(d_line_offsets, 7) || misaligned(d_totals, 7) || misaligned(d_cigar, 3))
+        return GENIE_E_INVALID;
+    // the table is optional: null with n_contigs == 0, or a table as every contig call takes it
+    if (!d_contig_offsets && n_contigs != 0) return GENIE_E_INVALID;
+    if (d_contig_offsets)
+        if (int rc = contig_args(d_contig_offsets, n_contigs)) return rc;
+    // reads and records are named by an int32 in the table of lines
+    if (N > 0x7fffffffll || n_records > 0x7fffffffll) return GENIE_E_TOO_LONG;
+    if (N > 0 && (!d_workspace || misaligned(d_workspace, 255) || workspace_bytes < sam_text_workspace_bytes(N, n_records)))
+        return GENIE_E_CAPACITY;
+    if (int rc = ready(ix)) return rc;
+    const SamBatch b{d_bases, d_read_offsets, N, total_bases, d_quals, d_sel_offsets, d_records, n_records, d_sam, d_info,
+                     d_cigar_offsets, d_cigar, n_ops, d_names, d_name_offsets, name_bytes, d_contig_names, d_contig_name_offsets,
+                     contig_name_bytes, tags, flags};
+    return launch_sam_text(ix, {d_contig_offsets, n_contigs}, b, {d_line_offsets, d_text, cap_text, d_totals}, d_workspace, stream);
+}
+
 int genie_contig_coords(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs, const int32_t *d_pos, int32_t stride,
                         int64_t count, int32_t *d_out, void *stream)
 {

@@ -541,6 +541,35 @@ struct WindowBatch {
 int64_t window_mems_workspace_bytes(int64_t U);
 // the reads, the status and the workspace as the batch of a CSR call; out.offsets has U + 1 entries, out.totals three
 int launch_window_mems(const genie_index *ix, const CsrBatch &b, const WindowBatch &wb, const CsrRows &out, void *stream);
+// sam_text.inc: the SAM records of a mapped batch as text; sam null: single-end mode
+struct SamBatch {
+    const uint8_t *bases;
+    const int64_t *read_offsets;          // N + 1
+    int64_t N, total_bases;
+    const uint8_t *quals;                 // may be null
+    const int64_t *sel_offsets;           // N + 1
+    const int32_t *records;
+    int64_t n_records;
+    const int32_t *sam, *info;
+    const int64_t *cigar_offsets;         // R + 1
+    const uint32_t *cigar;
+    int64_t n_ops;
+    const uint8_t *names;
+    const int64_t *name_offsets;          // N + 1
+    int64_t name_bytes;
+    const uint8_t *contig_names;
+    const int64_t *contig_name_offsets;   // max(n_contigs, 1) + 1
+    int64_t contig_name_bytes;
+    int32_t tags, flags;
+};
+struct SamTextOut {
+    int64_t *line_offsets;
+    uint8_t *text;                        // may be null: sizing only
+    int64_t cap_text;
+    int64_t *totals;                      // may be null
+};
+int64_t sam_text_workspace_bytes(int64_t N, int64_t n_records);
+int launch_sam_text(const genie_index *ix, const ContigTable &ctg, const SamBatch &b, const SamTextOut &out, void *ws, void *stream);
 // min_occ.inc: matching statistics and SMEMs of what occurs at least min_occ times
 int64_t match_stats_min_occ_workspace_bytes(int64_t N, int64_t total_bases, int32_t flags);
 int launch_match_stats_min_occ(const genie_index *ix, int32_t min_occ, const CsrBatch &b, int32_t *d_ms, int32_t *d_lohi,

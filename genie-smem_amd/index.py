@@ -119,6 +119,18 @@ def sam_lines(records, sam, info, cigar_offsets, cigar, read_names, contig_names
     return lines
 
 
+def names_csr(names, device=None):
+    """Names that come from the host as sam_text takes them: a list of str (UTF-8) or bytes -> (bytes uint8[total], offsets
+    int64[len(names) + 1]), two tensors on the host or, with `device`, there.  An empty list gives no bytes and the offset 0."""
+    raw = [x.encode("utf-8") if isinstance(x, str) else bytes(x) for x in names]
+    offsets = np.zeros(len(raw) + 1, np.int64)
+    if raw:
+        offsets[1:] = np.cumsum([len(x) for x in raw])
+    data = torch.from_numpy(np.frombuffer(b"".join(raw), np.uint8).copy())
+    offsets = torch.from_numpy(offsets)
+    return (data, offsets) if device is None else (data.to(device), offsets.to(device))
+
+
 class GenieIndex:
     def __init__(self):
         self._h = C.c_void_p(0)
@@ -994,6 +1006,64 @@ class GenieIndex:
             if found <= out.shape[0]:
                 return out_offsets, out[:found], status[:U], totals
             cap_rows = found                      # capacity guess too small: rerun with the exact size
+
+    def sam_text(self, bases, read_offsets, sel_offsets, records, sam, info, cigar_offsets, cigar, names, name_offsets, contig_names,
+                 contig_name_offsets, quals=None, contigs=None, tags=N.SAM_NM | N.SAM_AS, seq=True):
+        """The SAM records of a mapped batch as text on the device (genie_sam_text) -> (text uint8[bytes], line_offsets
+        int64[n_lines + 1], totals int64[3] = (lines, bytes, unmapped lines)): line l is text[line_offsets[l] :
+        line_offsets[l + 1]], read by read and record by record as sam_lines orders them, a read without records one unmapped
+        line, every line ended by "\\n"; the header is sam_header's.  bases / read_offsets: the batch in read orientation;
+        sel_offsets, records, sam, info, cigar_offsets, cigar: map_pairs' results, or with sam=None map_records' (single-end
+        mode); names / name_offsets and contig_names / contig_name_offsets: names as CSR bytes (names_csr,
+        text_reads.fastq_fields); quals: uint8 parallel to bases, or None (`*`); contigs: the ReferenceSet of the records, or
+        None for one contig; tags: a mask of SAM_NM, SAM_AS, SAM_MD, SAM_MC, SAM_MQ; seq=False writes `*` for SEQ and QUAL.
+        Two native calls: one sizes the text, one fills it."""
+        bases, read_offsets, n_reads, total, _, _, _ = self._csr_call(bases, read_offsets)
+        sel_offsets = self._as_dev(sel_offsets, torch.int64).reshape(-1)
+        records, info = self._as_dev(records, torch.int32), self._as_dev(info, torch.int32)
+        n_rec = records.shape[0]
+        if sel_offsets.numel() != n_reads + 1 or records.dim() != 2 or records.shape[1] != 12 or info.shape != (n_rec, 8):
+            raise ValueError("sel_offsets needs N + 1 entries, records must be [R, 12] and info [R, 8], as map_records returns them")
+        if sam is not None:
+            sam = self._as_dev(sam, torch.int32)
+            if sam.shape != (n_rec, 4) or n_reads % 2:
+                raise ValueError("sam must be [R, 4] for an even number of reads: mates are interleaved")
+        cigar_offsets = self._as_dev(cigar_offsets, torch.int64).reshape(-1)
+        if cigar_offsets.numel() != n_rec + 1:
+            raise ValueError("cigar_offsets needs one entry more than there are records")
+        if isinstance(cigar, torch.Tensor) and cigar.dtype == torch.uint32:
+            cigar = cigar.view(torch.int32)
+        cigar = self._as_dev(cigar, torch.int32).reshape(-1)
+        if quals is not None:
+            quals = self._as_dev(quals, torch.uint8).reshape(-1)
+            if quals.numel() != total:
+                raise ValueError("quals must be parallel to bases")
+            if total == 0:
+                quals = torch.zeros(1, dtype=torch.uint8, device=self.device)      # an address: NULL would mean `*`
+        names, contig_names = self._as_dev(names, torch.uint8).reshape(-1), self._as_dev(contig_names, torch.uint8).reshape(-1)
+        name_offsets = self._as_dev(name_offsets, torch.int64).reshape(-1)
+        contig_name_offsets = self._as_dev(contig_name_offsets, torch.int64).reshape(-1)
+        table = (C.c_void_p(0), 0)
+        if contigs is not None:
+            off, table = self._contig_table(contigs)
+        if name_offsets.numel() != n_reads + 1 or contig_name_offsets.numel() != max(table[1], 1) + 1:
+            raise ValueError("one name per read and one per contig")
+        none = C.c_void_p(0)
+        opt = lambda t: _ptr(t) if t is not None and t.numel() else none      # noqa: E731
+        line_offsets = torch.empty(n_reads + n_rec + 1, dtype=torch.int64, device=self.device)
+        totals = torch.empty(3, dtype=torch.int64, device=self.device)
+        ws, ws_bytes = self._workspace("genie_sam_text_workspace_bytes", n_reads, n_rec)
+        if sam is not None and n_rec == 0:
+            sam = torch.zeros((1, 4), dtype=torch.int32, device=self.device)       # an address: NULL is single-end mode
+        head = (*table, _ptr(bases), _ptr(read_offsets), n_reads, total, _ptr(quals), _ptr(sel_offsets),
+                opt(records), n_rec, _ptr(sam), opt(info), _ptr(cigar_offsets), opt(cigar), cigar.numel(),
+                opt(names), _ptr(name_offsets), names.numel(), opt(contig_names), _ptr(contig_name_offsets), contig_names.numel(),
+                int(tags), 0 if seq else N.SAM_NO_SEQ, _ptr(line_offsets))
+        self._run("genie_sam_text", *head, none, 0, _ptr(totals), _ptr(ws), ws_bytes)
+        n_lines, n_bytes, _ = (int(x) for x in totals.cpu())
+        text = torch.empty(max(n_bytes, 1), dtype=torch.uint8, device=self.device)
+        self._run("genie_sam_text", *head, _ptr(text), n_bytes, _ptr(totals), _ptr(ws), ws_bytes)
+        return text[:n_bytes], line_offsets[:n_lines + 1], totals
 
     def contig_coords(self, contigs, pos, stride=1):
         """1-based concatenation positions -> int32 [count, 2] = (contig, 1-based offset inside it) on the device

@@ -369,6 +369,45 @@ class SMEM:
         offs, cigar, info = ix.chain_cigars(csr, mems[0], mems[1], chains, aln, sel, contigs, both_strands, **opts)
         return records, sel_offsets, offs, cigar, info, pairs, sam, (windows, status, totals)
 
+    def sam_text(self, result, reads, names, contig_names=None, quals=None, contigs=None, tags=N.SAM_NM | N.SAM_AS, seq=True):
+        """The SAM records of a mapped batch as text on the device (genie_sam_text) -> (text uint8[bytes], line_offsets
+        int64[n_lines + 1], totals int64[3] = (lines, bytes, unmapped lines)): GenieIndex.sam_text.  result: the tuple of
+        map_pairs (7 or 8 results) or of map_records (5 results: single-end mode).  reads: the batch as that call took it,
+        interleaved.  names: one per read, a list of str or bytes or the (bytes, offsets) of index.names_csr or
+        text_reads.fastq_fields; contig_names likewise, by default contigs.names, "ref" without contigs.  quals: None (`*`),
+        a list of str or bytes with one entry per read, or uint8 parallel to the bases (fastq_fields).  tags: a mask of
+        _native.SAM_NM (1), SAM_AS (2), SAM_MD (4), SAM_MC (8), SAM_MQ (16); seq=False writes `*` for SEQ and QUAL."""
+        from .index import names_csr
+        ix = self.matcher.index(self.lut.lut_size)
+        if len(result) not in (5, 7, 8):
+            raise ValueError("result must be what map_pairs (7 or 8 results) or map_records (5 results) returned")
+        records, sel_offsets, cigar_offsets, cigar, info = result[:5]
+        sam = result[6] if len(result) > 5 else None
+        bases, read_offsets = self._csr_reads(reads, False)
+        if contig_names is None:
+            contig_names = contigs.names if contigs is not None else ["ref"]
+        csr = lambda x: x if isinstance(x, tuple) else names_csr(x)      # noqa: E731
+        if isinstance(quals, (list, tuple)):
+            quals = names_csr(quals)[0]
+        return ix.sam_text(bases, read_offsets, sel_offsets, records, sam, info, cigar_offsets, cigar, *csr(names), *csr(contig_names),
+                           quals=quals, contigs=contigs, tags=tags, seq=seq)
+
+    def write_sam(self, path, result, reads, names, contig_names=None, contig_lengths=None, **options):
+        """A SAM file: the header lines of index.sam_header, then the text of sam_text(result, reads, names, contig_names,
+        **options) in one copy from the device -> totals.  contig_lengths default to those of options["contigs"], or the
+        reference's length without contigs; contig_names here are a list."""
+        from .index import sam_header
+        contigs = options.get("contigs")
+        if contig_names is None:
+            contig_names = contigs.names if contigs is not None else ["ref"]
+        if contig_lengths is None:
+            contig_lengths = np.diff(contigs.offsets) if contigs is not None else [self.matcher.index(self.lut.lut_size).n]
+        text, _, totals = self.sam_text(result, reads, names, contig_names, **options)
+        with open(path, "wb") as f:
+            f.write(("\n".join(sam_header(contig_names, contig_lengths)) + "\n").encode())
+            f.write(text.cpu().numpy().tobytes())
+        return totals
+
     def locate_contigs(self, contigs, rows):
         """SMEM rows (start, end, lo, hi) of any find_smems* call -> (hit_offsets, hits int32[T, 2] = (contig, 1-based
         offset), dropped): GenieIndex.locate_contigs.  The rows stay SMEMs of the concatenation; occurrences that bridge two

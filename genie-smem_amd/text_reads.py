@@ -151,6 +151,50 @@ def interleave_reads(csr1, csr2):
     return bases, offsets
 
 
+def fastq_fields(data, read_offsets, device=None):
+    """The names and the qualities of the first N records of a FASTQ text -> (names uint8, name_offsets int64[N + 1], quals
+    uint8[total bases]) on `device` (default: where read_offsets lies): what GenieIndex.sam_text takes next to the (bases,
+    read_offsets) that reads_from_text made of the same text.  A record's name is the bytes behind its '@' up to the first
+    space, tab, '\\r' or the line's end; the quality lines are laid back to back under read_offsets.  Lines are those of
+    genie_reads_from_text: a '\\n' ends a line, a '\\r' in front of it is dropped, a non-empty tail is one more line.  Torch
+    calls on the device only, nothing per read on the host.  ValueError when the text holds fewer than N records or a
+    quality line is not as long as its read: one reduction and one host read.  The qualities of two files go through
+    interleave_reads like their bases."""
+    read_offsets = torch.as_tensor(read_offsets).to(torch.int64).reshape(-1)
+    dev = read_offsets.device if device is None else torch.device(device)
+    read_offsets = read_offsets.to(dev)
+    text = _text_tensor(data, dev)
+    n, size = read_offsets.numel() - 1, text.numel()
+    if n < 0:
+        raise ValueError("read_offsets needs N + 1 entries")
+    i64 = lambda *v: torch.tensor(v, dtype=torch.int64, device=dev)      # noqa: E731
+    ends = torch.nonzero(text == 10).reshape(-1)
+    starts = torch.cat([i64(0), ends + 1])
+    closed = ends.numel()                                   # lines that a '\n' ends; the tail is one more where it is not empty
+    cr = torch.zeros(closed, dtype=torch.int64, device=dev)
+    if closed:
+        cr = ((ends > starts[:closed]) & (text[(ends - 1).clamp(min=0)] == 13)).to(torch.int64)
+    ends = torch.cat([ends - cr, i64(size)])
+    if closed + 1 < 4 * n:                                  # the tail counted: an empty one can only be an empty quality line
+        raise ValueError(f"the text holds {(closed + 1) // 4} complete records, read_offsets names {n}")
+    q0, q1 = starts[3:4 * n:4], ends[3:4 * n:4]
+    # a name ends at the first space, tab or '\r' behind the '@', or where its line ends
+    h0 = torch.minimum(starts[0:4 * n:4] + 1, ends[0:4 * n:4])
+    stop = torch.nonzero((text == 32) | (text == 9) | (text == 13)).reshape(-1)
+    first = torch.cat([stop, i64(size)])[torch.searchsorted(stop, h0)]
+    h1 = torch.maximum(torch.minimum(ends[0:4 * n:4], first), h0)
+    lens = read_offsets[1:] - read_offsets[:-1]
+    if n and bool(((q1 - q0) != lens).any()):
+        raise ValueError("a quality line is not as long as its read")
+
+    def gather(begin, length, offsets):
+        shift = torch.repeat_interleave(begin - offsets[:-1], length)      # per byte: how far it moves
+        return text[torch.arange(shift.numel(), device=dev) + shift]
+    name_offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    name_offsets[1:] = torch.cumsum(h1 - h0, 0)
+    return gather(h0, h1 - h0, name_offsets), name_offsets, gather(q0, lens, read_offsets)
+
+
 def default_byte_codes():
     """A C G T -> 0 1 2 3, every other byte 4."""
     table = np.full(256, 4, np.uint8)

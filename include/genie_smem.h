@@ -1133,6 +1133,98 @@ int genie_window_mems(const genie_index *ix, int32_t flags, const uint8_t *d_bas
                       int64_t *d_totals,               /* 3, may be NULL */
                       void *d_workspace, int64_t workspace_bytes, void *stream);
 
+/* The SAM records of a mapped batch as TEXT in device memory: the output end of the pipeline.  One line per record, read by read
+ * and for each read its records in record order; a read without records gets one unmapped line.  Every line ends with '\n'.
+ * Inputs, all on the device:
+ *   ix       for the packed reference (the letters of MD) and its length n.
+ *   table    d_contig_offsets and n_contigs as the *_contigs calls take them; NULL and 0: one contig that starts at position 0.
+ *            Only the start of a record's contig is read, clamped to [0, n]; nc = max(n_contigs, 1) contig names exist.
+ *   reads    d_bases (codes 0..4, read orientation), d_read_offsets[N + 1], total_bases; d_quals, which may be NULL, holds
+ *            total_bases bytes under the same offsets.
+ *   records  d_sel_offsets[N + 1], d_records (12 int32 per record) and n_records as genie_select_alignments wrote them;
+ *            R = min(d_sel_offsets[N], n_records), and the records of read r are the rows [so[r], so[r + 1]) cut to [0, R), as
+ *            in genie_pair_alignments.  d_sam (4 int32 per record: flag, mapq, mate_record, tlen), genie_pair_alignments'; NULL
+ *            is SINGLE-END mode.  d_info (8 int32 per record), d_cigar_offsets[R + 1] and d_cigar (n_ops ops, length << 4 |
+ *            code, codes 1 I, 2 D, 4 S, 7 =, 8 X) as genie_chain_cigars wrote them for these records.
+ *   names    d_names and d_name_offsets[N + 1] (name_bytes bytes), one name per read; d_contig_names and
+ *            d_contig_name_offsets[nc + 1] (contig_name_bytes bytes).
+ *   tags     a mask of GENIE_SAM_NM (1), _AS (2), _MD (4), _MC (8), _MQ (16); the tags are written in that order.
+ *   flags    GENIE_SAM_NO_SEQ: SEQ and QUAL are `*`.
+ * With d_sam, N is even and reads 2 k and 2 k + 1 are mates.
+ * A record line (record j of read r): QNAME the read's name; FLAG and MAPQ d_sam's; RNAME the name of the record's contig
+ * (its index clamped to [0, nc)); POS its offset column; CIGAR the text of its ops, `*` for none; with m = d_sam's mate_record
+ * (none unless 0 <= m < R) RNEXT is `*` and PNEXT 0 for none, else RNEXT is `=` when record m has the same contig column and
+ * its contig's name otherwise, and PNEXT its offset; TLEN d_sam's; SEQ from the codes, 0..3 A C G T and anything else N, and
+ * QUAL the bytes of d_quals (`*` with d_quals == NULL): for a record whose strand column is not 0 SEQ is the complement written
+ * in reverse (N stays N) and QUAL reversed; a read of no bases has an empty SEQ.  Numbers are signed decimals.  Then the tags,
+ * each behind a tab: NM:i: (d_info column 3), AS:i: (the score column), MD:Z: only for a record that has ops, MC:Z: and MQ:i:.
+ * The unmapped line of read r: m is the LAST record in the range of read r ^ 1 whose d_sam flag has neither 0x100 nor 0x800;
+ * FLAG is 0x1 | 0x4 | (0x40 for an even r, 0x80 for an odd one) | (0x8 without m) | (0x20 when m's strand is not 0); with m RNAME
+ * and POS are m's, RNEXT is `=` and PNEXT is POS, else `*`, 0, `*`, 0; MAPQ 0, CIGAR `*`, TLEN 0; SEQ and QUAL in read
+ * orientation; of the tags only MC and MQ.
+ * MC is the CIGAR text of record m, written when m exists and has ops; MQ is d_sam's mapq of record m, written when m exists.
+ * MD is a function of the CIGAR and the reference alone.  t = the contig's start + POS - 1, c = 0 (an int64); an = of length L:
+ * c += L, t += L; an X of length L: for each base write c and the reference letter at t, then c = 0 and t += 1; a D of length
+ * L: write c, `^` and the L reference letters from t on, then c = 0 and t += L; I and S: nothing; at the end write c.  Examples:
+ * 5A0C3, 0A7, 4^AC0T2.  A reference position outside [0, n) is clamped: an undefined letter.
+ * Single-end mode (d_sam == NULL): N need not be even; FLAG = 0x10 (strand) | 0x800 (kind 1) | 0x100 (kind 2), MAPQ the record's
+ * mapq column, RNEXT `*`, PNEXT 0, TLEN 0; the unmapped line has FLAG 4 and `* 0 0 * * 0 0`; MC and MQ are never written.
+ * Outputs, all in caller buffers:
+ *   d_line_offsets  N + n_records + 1 int64 of capacity, 8-byte aligned; with n_lines = R + (reads without records) the entries
+ *                   0 .. n_lines are written, entry [n_lines] the true byte total even when cap_text is smaller
+ *   d_text          cap_text bytes; NULL is the sizing call.  Line l is the bytes [d_line_offsets[l], d_line_offsets[l + 1]);
+ *                   bytes at or past cap_text are dropped and nothing is written outside the buffer
+ *   d_totals        3 int64, 8-byte aligned, may be NULL: {lines, bytes, unmapped lines}; it stays on the device
+ * No atomic decides a value: the text is a function of the inputs alone.  Garbage records, d_sam or d_info rows or ops give
+ * undefined bytes, but no access outside the declared sizes and no unbounded loop: record ranges, record, contig and reference
+ * indices are clamped, every store lies below min(the line's end, cap_text), and the loop over the letters of an X or a D ends
+ * there too.  A line of more than 2^31 - 1 bytes is cut to that length.
+ * Checked before the device check, so on any handle, in this order.  GENIE_E_INVALID: a null ix, d_read_offsets, d_sel_offsets,
+ * d_name_offsets, d_contig_name_offsets or d_line_offsets; a negative size; an odd N with d_sam; an unknown bit in tags or
+ * flags; a null d_bases, d_names, d_contig_names or d_cigar whose size is above 0; a null d_records, d_info or d_cigar_offsets
+ * with n_records > 0; d_records, d_sam or d_info not 16-byte, an offset array, d_line_offsets or d_totals not 8-byte, d_cigar not
+ * 4-byte aligned; a null table with n_contigs != 0, a table with n_contigs < 1 or not 8-byte aligned.  Then GENIE_E_TOO_LONG for
+ * n_contigs, N or n_records above 2^31 - 1.  Then, for N > 0, a d_workspace that is null, not 256-byte aligned or smaller than
+ * genie_sam_text_workspace_bytes(N, n_records) gives GENIE_E_CAPACITY.  Then GENIE_E_NO_DEVICE.  The five offset arrays are
+ * checked on the device as genie_chain_mems checks its row offsets (first 0, non-decreasing, last at most the array's declared
+ * total -- d_sel_offsets has none --, no item above 2^31 - 1; d_cigar_offsets over its first R + 1 entries): GENIE_E_INVALID, at
+ * the cost of the call's only synchronisation of `stream`.  N == 0 writes d_line_offsets[0] = 0 and zero totals.
+ * The workspace function returns GENIE_E_INVALID for negative arguments, is a multiple of 256 and monotone in both: per read 4
+ * (the mark of a read without records) and 8 (the number of such reads before it, N + 1 entries), per line of the N + n_records
+ * there can be 8 (its read and record), 4 (its length) and 8 (its offset, one entry more), 8 per 1024 lines (the scan), each
+ * piece rounded up to 256 on its own, and 256 for the verdict of the offset checks.
+ * Kernels: one wave per line, in a sizing pass and a write pass over the same walk.  The lanes go over the bytes of the name, of
+ * SEQ and QUAL and over the ops, 64 at a time; an op's place in CIGAR, MC and MD is a wave prefix sum over the ops' text lengths,
+ * MD's count in front of an X or a D a segmented sum of the = lengths (a prefix sum less a prefix maximum).  The sizing pass loads
+ * records and ops only.  Cost of a line: about (name + 2 bases) / 64 + 3 ceil(ops / 64) wave steps. */
+#define GENIE_SAM_NM 1
+#define GENIE_SAM_AS 2
+#define GENIE_SAM_MD 4
+#define GENIE_SAM_MC 8
+#define GENIE_SAM_MQ 16
+#define GENIE_SAM_NO_SEQ 1
+int64_t genie_sam_text_workspace_bytes(int64_t N, int64_t n_records);
+int genie_sam_text(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs,
+                   const uint8_t *d_bases, const int64_t *d_read_offsets,  /* N + 1 */
+                   int64_t N, int64_t total_bases,
+                   const uint8_t *d_quals,              /* total_bases, may be NULL */
+                   const int64_t *d_sel_offsets,        /* N + 1 */
+                   const int32_t *d_records,            /* 12 * n_records, 16-byte aligned */
+                   int64_t n_records,
+                   const int32_t *d_sam,                /* 4 * n_records, 16-byte aligned; NULL: single-end mode */
+                   const int32_t *d_info,               /* 8 * n_records, 16-byte aligned */
+                   const int64_t *d_cigar_offsets,      /* R + 1 */
+                   const uint32_t *d_cigar, int64_t n_ops,
+                   const uint8_t *d_names, const int64_t *d_name_offsets /* N + 1 */, int64_t name_bytes,
+                   const uint8_t *d_contig_names, const int64_t *d_contig_name_offsets /* max(n_contigs, 1) + 1 */,
+                   int64_t contig_name_bytes,
+                   int32_t tags, int32_t flags,
+                   int64_t *d_line_offsets,             /* N + n_records + 1 */
+                   uint8_t *d_text,                     /* cap_text; may be NULL: sizing only */
+                   int64_t cap_text,
+                   int64_t *d_totals,                   /* 3, may be NULL */
+                   void *d_workspace, int64_t workspace_bytes, void *stream);
+
 /* Matching statistics and SMEMs that are EXACT WITH RESPECT TO THE SEQUENCE SET.  genie_match_stats and the SMEM calls on a
  * reference of several sequences answer for the concatenation; genie_locate_contigs then drops the occurrences that bridge
  * two sequences, and with them seeds.  Contigs ACGT | TTGA and the read CGTT: the concatenation holds CGTT once, across the
