@@ -39,6 +39,8 @@ SEG_FORMS = {"positions": SEG_POSITIONS, "hits": SEG_HITS}
 SELECT_LANE_MAX, SELECT_TILE = 8, 512               # genie_select_alignments: one lane per read up to the first, LDS state up to the second
 PAIR_LANE_MAX, PAIR_TILE = 64, 256                  # genie_pair_alignments: one lane per pair up to the first (combinations), LDS records per mate
 PAIR_ORIENT = {"fr": 1, "rf": 2, "same": 4, "any": 7}
+ISIZE_LDS_BINS = 4096                               # genie_insert_size_stats: spans below it are counted in LDS
+ISIZE_OUTLIER_IQR, ISIZE_WINDOW_IQR, ISIZE_WINDOW_STD = 2, 3, 4   # its multipliers (BWA-MEM's)
 WINDOW_MAX, WINDOW_MAX_ROWS = 65536, 2048           # genie_window_mems: bases of a window, rows of a searched unit (sized to LDS)
 WINDOW_SEARCHED, WINDOW_ROW_CAP, WINDOW_TOO_LONG = 1, 2, 4   # its status values
 SAM_NM, SAM_AS, SAM_MD, SAM_MC, SAM_MQ = 1, 2, 4, 8, 16      # genie_sam_text: the tags, written in this order
@@ -69,6 +71,7 @@ SYMBOLS = [
     "genie_chain_cigars", "genie_chain_cigars_workspace_bytes",
     "genie_select_alignments", "genie_select_alignments_workspace_bytes",
     "genie_pair_alignments", "genie_pair_alignments_workspace_bytes",
+    "genie_insert_size_stats", "genie_insert_size_stats_workspace_bytes",
     "genie_rescue_windows", "genie_rescue_windows_workspace_bytes",
     "genie_window_mems", "genie_window_mems_workspace_bytes",
     "genie_sam_text", "genie_sam_text_workspace_bytes",
@@ -97,7 +100,7 @@ class GenieError(RuntimeError):
 
 def build(force=False):
     """Compile libgenie_smem.so for gfx950 with hipcc (csrc/Makefile), in-tree."""
-    srcs = [os.path.join(CSRC, f) for f in ("kernels.hip", "index_build.hip", "short_read_kernel.inc", "match_table_kernel.inc", "match_table_body.inc", "match_table_long_body.inc", "split_reads.inc", "long_reads.inc", "long_units.inc", "lu_seg_body.inc", "exact_match.inc", "contigs.inc", "fwd_step.inc", "contig_stats.inc", "min_occ.inc", "mems.inc", "chains.inc", "align.inc", "cigars.inc", "select.inc", "pairs.inc", "windows.inc", "sam_text.inc", "ingest_tiles.inc", "text_reads.inc", "fasta_reads.inc", "segments.inc", "capi.cpp", "index_host.cpp", "genie_internal.h", "Makefile")]
+    srcs = [os.path.join(CSRC, f) for f in ("kernels.hip", "index_build.hip", "short_read_kernel.inc", "match_table_kernel.inc", "match_table_body.inc", "match_table_long_body.inc", "split_reads.inc", "long_reads.inc", "long_units.inc", "lu_seg_body.inc", "exact_match.inc", "contigs.inc", "fwd_step.inc", "contig_stats.inc", "min_occ.inc", "mems.inc", "chains.inc", "align.inc", "cigars.inc", "select.inc", "pairs.inc", "insert_size.inc", "windows.inc", "sam_text.inc", "ingest_tiles.inc", "text_reads.inc", "fasta_reads.inc", "segments.inc", "capi.cpp", "index_host.cpp", "genie_internal.h", "Makefile")]
     srcs.append(os.path.join(os.path.dirname(_PKG), "include", "genie_smem.h"))
     newest = max(os.path.getmtime(s) for s in srcs)
     if force or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < newest:
@@ -191,6 +194,8 @@ def lib():
                                               i64, vp, vp, vp, i64, vp]),
         "genie_pair_alignments_workspace_bytes": (i64, [i64, i64]),
         "genie_pair_alignments": (C.c_int, [vp, i64, vp, vp, i64, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, i64, vp]),
+        "genie_insert_size_stats_workspace_bytes": (i64, [i64, i32]),
+        "genie_insert_size_stats": (C.c_int, [vp, i64, vp, vp, i64, i32, i32, i32, vp, vp, vp, vp, i64, vp]),
         "genie_rescue_windows_workspace_bytes": (i64, [i64]),
         "genie_rescue_windows": (C.c_int, [vp, vp, i64, vp, i64, vp, vp, i64, vp, i32, i32, i32, vp, vp, vp, i64, vp]),
         "genie_window_mems_workspace_bytes": (i64, [i64]),

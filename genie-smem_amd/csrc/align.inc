@@ -387,6 +387,7 @@ __global__ void __launch_bounds__(kScanBlock) align_totals_kernel(const long lon
 #include "cigars.inc"
 #include "select.inc"
 #include "pairs.inc"
+#include "insert_size.inc"
 
 int64_t align_chains_workspace_bytes(int64_t U, int64_t cap_chains)
 {

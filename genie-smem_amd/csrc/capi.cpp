@@ -801,6 +801,34 @@ int genie_pair_alignments(const genie_index *ix, int64_t N, const int64_t *d_sel
     return launch_pair_alignments(ix, b, {d_pairs, d_sam, d_totals}, d_workspace, stream);
 }
 
+int64_t genie_insert_size_stats_workspace_bytes(int64_t N, int32_t max_span)
+{
+    if (N < 0 || max_span < 1 || max_span > GENIE_WINDOW_MAX / 2) return (int64_t)GENIE_E_INVALID;
+    return insert_size_stats_workspace_bytes(N, max_span);
+}
+
+int genie_insert_size_stats(const genie_index *ix, int64_t N, const int64_t *d_sel_offsets, const int32_t *d_records, int64_t n_records,
+                            int32_t min_mapq, int32_t max_span, int32_t min_samples, int64_t *d_stats, int32_t *d_samples,
+                            int64_t *d_totals, void *d_workspace, int64_t workspace_bytes, void *stream)
+{
+    // argument checks first: they need no device image
+    if (!ix || !d_sel_offsets || !d_stats) return GENIE_E_INVALID;
+    if (N < 0 || (N & 1) != 0 || n_records < 0 || workspace_bytes < 0) return GENIE_E_INVALID;
+    if (n_records > 0 && !d_records) return GENIE_E_INVALID;
+    if (min_mapq < 0 || min_mapq > 60 || max_span < 1 || max_span > GENIE_WINDOW_MAX / 2 || min_samples < 1 || min_samples > (1 << 30))
+        return GENIE_E_INVALID;
+    if (misaligned(d_records, 15) || misaligned(d_sel_offsets, 7) || misaligned(d_stats, 7) || misaligned(d_samples, 7) ||
+        misaligned(d_totals, 7))
+        return GENIE_E_INVALID;
+    // reads and records are named by an int32, and a bin's count stays below 2^30
+    if (N > 0x7fffffffll || n_records > 0x7fffffffll) return GENIE_E_TOO_LONG;
+    if (N > 0 && (!d_workspace || misaligned(d_workspace, 255) || workspace_bytes < insert_size_stats_workspace_bytes(N, max_span)))
+        return GENIE_E_CAPACITY;
+    if (int rc = ready(ix)) return rc;
+    const IsizeBatch b{N, d_sel_offsets, d_records, n_records, min_mapq, max_span, min_samples};
+    return launch_insert_size_stats(ix, b, {d_stats, d_samples, d_totals}, d_workspace, stream);
+}
+
 int64_t genie_rescue_windows_workspace_bytes(int64_t N)
 {
     if (N < 0) return (int64_t)GENIE_E_INVALID;

@@ -517,6 +517,21 @@ struct PairOut {
 };
 int64_t pair_alignments_workspace_bytes(int64_t N, int64_t n_records);
 int launch_pair_alignments(const genie_index *ix, const PairBatch &b, const PairOut &out, void *ws, void *stream);
+// insert_size.inc: the insert-size distribution of the pairs whose heads map confidently, per combination type
+struct IsizeBatch {
+    int64_t N;                            // reads, even
+    const int64_t *sel_offsets;           // N + 1
+    const int32_t *records;
+    int64_t n_records;
+    int32_t min_mapq, max_span, min_samples;
+};
+struct IsizeOut {
+    int64_t *stats;                       // 3 x 12
+    int32_t *samples;                     // may be null
+    int64_t *totals;                      // may be null
+};
+int64_t insert_size_stats_workspace_bytes(int64_t N, int32_t max_span);
+int launch_insert_size_stats(const genie_index *ix, const IsizeBatch &b, const IsizeOut &out, void *ws, void *stream);
 // windows.inc: where to seed a mate again next to its partner, and the MEMs of strand-reads against windows of the reference
 struct RescueBatch {
     int64_t N;                            // reads, even

@@ -6,6 +6,7 @@ device memory, the stream and -- multi-GPU -- the one-time broadcast of the inde
 """
 import ctypes as C
 import re
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -117,6 +118,31 @@ def sam_lines(records, sam, info, cigar_offsets, cigar, read_names, contig_names
                 rname, pos, rnext = contig_names[rec[mate][4]], rec[mate][5], "="
             lines.append("\t".join(str(c) for c in [name, flag, rname, pos, 0, "*", rnext, pos, 0] + seq_qual(read, 0)))
     return lines
+
+
+InsertSize = namedtuple("InsertSize", "orient isize_min isize_max isize_mean estimated stats")
+_PAIR_DEFAULTS = {"orient": "fr", "isize_min": 0, "isize_max": 1000, "isize_mean": 300}      # GenieIndex.pair_alignments'
+
+
+def insert_size_options(stats, fallback=None):
+    """The pairing options that insert_size_stats' statistics stand for -> InsertSize(orient, isize_min, isize_max, isize_mean,
+    estimated, stats).  A host function: stats is int64[3, 12] as a CPU tensor or an array, one row per type (FR, RF, same) =
+    (n, ok, q25, q50, q75, lo_b, hi_b, n_in, mean, std, isize_min, isize_max).  The ok type with the most samples gives its
+    bit as orient (pair_alignments' mask), its window and its mean, and estimated is True; a tie goes to the lower type.  With
+    no ok type the four values are the fallback's -- a dict of pair_alignments' options, those it lacks being that call's
+    defaults -- and estimated is False.  ONE orientation: a window per orientation would need another pairing call.  stats
+    comes back as a tuple of three tuples."""
+    rows = np.asarray(stats.cpu() if hasattr(stats, "cpu") else stats, dtype=np.int64).reshape(3, 12)
+    kept = tuple(tuple(int(v) for v in row) for row in rows)
+    best = None
+    for t in range(3):
+        if kept[t][1] and (best is None or kept[t][0] > kept[best][0]):
+            best = t
+    if best is not None:
+        return InsertSize(1 << best, kept[best][10], kept[best][11], kept[best][8], True, kept)
+    opts = dict(_PAIR_DEFAULTS, **{k: v for k, v in (fallback or {}).items() if k in _PAIR_DEFAULTS})
+    orient = N.PAIR_ORIENT[opts["orient"]] if isinstance(opts["orient"], str) else int(opts["orient"])
+    return InsertSize(orient, int(opts["isize_min"]), int(opts["isize_max"]), int(opts["isize_mean"]), False, kept)
 
 
 def names_csr(names, device=None):
@@ -935,6 +961,32 @@ class GenieIndex:
         self._run("genie_pair_alignments", n_reads, _ptr(sel_offsets), _ptr(records) if n_rec else none, n_rec,
                   _ptr(klass) if kept else none, kept, *prm, _ptr(pairs), _ptr(sam) if n_rec else none, _ptr(totals), _ptr(ws), ws_bytes)
         return pairs[:n_reads // 2], sam[:n_rec], totals
+
+    def insert_size_stats(self, sel_offsets, records, min_mapq=20, max_span=10000, min_samples=25, samples=False):
+        """The insert-size distribution of a paired batch, estimated from the batch (genie_insert_size_stats) -> (stats
+        int64[3, 12], one row per combination type FR, RF, same = (n, ok, q25, q50, q75, lo_b, hi_b, n_in, mean, std,
+        isize_min, isize_max); samples int32[P, 2] = (type, span) per pair, (-1, 0) for a pair that gives none, or None; totals
+        int64[4] = (pairs with both mates mapped, pairs sampled, refused for mapq alone, refused for contig, type or span)) on
+        the device.  sel_offsets, records: select_alignments' first and third results.  A pair is a sample when both heads
+        have a mapq of at least min_mapq, share a contig and span 1 to max_span bases; a type with at least min_samples
+        samples and a twentieth of the largest type's is ok.  insert_size_options turns stats into pair_alignments' options.
+        The defaults are this wrapper's; the C call has none."""
+        self._need_device()
+        sel_offsets = self._as_dev(sel_offsets, torch.int64).reshape(-1)
+        records = self._as_dev(records, torch.int32)
+        if sel_offsets.numel() < 1 or (sel_offsets.numel() - 1) % 2:
+            raise ValueError("sel_offsets needs N + 1 entries for an even number of reads: mates are interleaved")
+        if records.dim() != 2 or records.shape[1] != 12:
+            raise ValueError("records must be [R, 12], as select_alignments returns them")
+        n_reads, n_rec = sel_offsets.numel() - 1, records.shape[0]
+        none = C.c_void_p(0)
+        stats = torch.empty((3, 12), dtype=torch.int64, device=self.device)
+        per_pair = torch.empty((max(n_reads // 2, 1), 2), dtype=torch.int32, device=self.device) if samples else None
+        totals = torch.empty(4, dtype=torch.int64, device=self.device)
+        ws, ws_bytes = self._workspace("genie_insert_size_stats_workspace_bytes", n_reads, int(max_span))
+        self._run("genie_insert_size_stats", n_reads, _ptr(sel_offsets), _ptr(records) if n_rec else none, n_rec, int(min_mapq),
+                  int(max_span), int(min_samples), _ptr(stats), _ptr(per_pair) if samples else none, _ptr(totals), _ptr(ws), ws_bytes)
+        return stats, per_pair[:n_reads // 2] if samples else None, totals
 
     def rescue_windows(self, read_offsets, sel_offsets, records, pairs, contigs=None, orient="fr", isize_max=1000, min_anchor_score=40):
         """Where to seed a mate again next to its partner (genie_rescue_windows) -> (windows int32[2N, 2] = (wb, we), 0-based

@@ -302,6 +302,14 @@ class SMEM:
         ix = self.matcher.index(self.lut.lut_size)
         return ix.pair_alignments(sel_offsets, records, klass, **pair_options)
 
+    def insert_size_stats(self, sel_offsets, records, **options):
+        """The insert-size distribution of a paired batch, estimated from the batch (genie_insert_size_stats) -> (stats
+        int64[3, 12], samples int32[P, 2] or None, totals int64[4]): GenieIndex.insert_size_stats, which documents the options
+        (min_mapq, max_span, min_samples, samples) and their defaults; index.insert_size_options turns stats into
+        pair_alignments' options."""
+        ix = self.matcher.index(self.lut.lut_size)
+        return ix.insert_size_stats(sel_offsets, records, **options)
+
     def rescue_windows(self, read_offsets, sel_offsets, records, pairs, contigs=None, **rescue_options):
         """Where to seed a mate again next to its partner (genie_rescue_windows) -> (windows int32[2N, 2], totals):
         GenieIndex.rescue_windows, which documents the options (orient, isize_max, min_anchor_score) and their defaults."""
@@ -317,7 +325,7 @@ class SMEM:
         return ix.window_mems(bases, read_offsets, windows, minimum_length, offsets, rows, both_strands, split_breaks)
 
     def map_pairs(self, reads, minimum_length, contigs=None, both_strands=True, split_breaks=False, max_occ=0, align_options=None,
-                  select_options=None, pair_options=None, rescue=False, rescue_options=None, **chain_options):
+                  select_options=None, pair_options=None, rescue=False, rescue_options=None, insert_size=None, **chain_options):
         """Every alignment of every mate, paired: map_records on the interleaved batch, then pair_alignments on its records ->
         (records, sel_offsets, cigar_offsets, cigar, info, pairs, sam): map_records' five results, then pairs int32[P, 8] and
         sam int32[n, 4] parallel to records; sam_lines turns the lot into text.  reads: an interleaved batch (reads 2k and
@@ -329,8 +337,16 @@ class SMEM:
         run once more over the union, with the same options.  rescue_options: a dict of min_len, min_anchor_score (40) and
         the orient and isize_max of rescue_windows (default: those of pair_options).  An eighth result then follows the
         seven: (windows int32[2N, 2], status int32[2N], totals int64[3]) as rescue_windows and window_mems return them, status
-        and totals zero where no unit had a window."""
+        and totals zero where no unit had a window.
+        insert_size: None, and orient, isize_min, isize_max and isize_mean are pair_options' (or the defaults).  "estimate", or
+        a dict of insert_size_stats' options (min_mapq, max_span, min_samples): the statistics of the records of the first
+        selection are read to the host (36 numbers: the one added host read) and index.insert_size_options turns them into
+        those four options of every pairing, before and after rescue, and into rescue's orient and isize_max unless
+        rescue_options names them; the values given in pair_options are the fallback where no type has samples enough.  An
+        index.InsertSize of an earlier call is applied as it is, without estimating: estimate on the first chunk of a file,
+        reuse on the others.  In both cases the InsertSize used follows as the last result."""
         import torch
+        from .index import InsertSize, insert_size_options
         from .text_reads import interleave_reads
         ix = self.matcher.index(self.lut.lut_size)
         if isinstance(reads, tuple) and len(reads) == 2 and all(isinstance(r, (list, tuple)) for r in reads):
@@ -343,13 +359,23 @@ class SMEM:
                                                  **chain_options)
         sel_offsets, sel, records, klass = ix.select_alignments(csr[1], chains[0], chains[1], aln, contigs, both_strands,
                                                                 **(select_options or {}))[:4]
+        popts, ropts, used = dict(pair_options or {}), dict(rescue_options or {}), ()
+        if insert_size is not None:
+            if isinstance(insert_size, InsertSize):
+                est = insert_size
+            elif insert_size == "estimate" or isinstance(insert_size, dict):
+                stats = ix.insert_size_stats(sel_offsets, records, **(insert_size if isinstance(insert_size, dict) else {}))[0]
+                est = insert_size_options(stats.cpu(), popts)        # the added host read
+            else:
+                raise ValueError('insert_size must be None, "estimate", a dict of insert_size_stats\' options or an InsertSize')
+            popts.update(orient=est.orient, isize_min=est.isize_min, isize_max=est.isize_max, isize_mean=est.isize_mean)
+            used = (est,)
         if not rescue:
             offs, cigar, info = ix.chain_cigars(csr, mems[0], mems[1], chains, aln, sel, contigs, both_strands, **opts)
-            pairs, sam, _ = ix.pair_alignments(sel_offsets, records, klass, **(pair_options or {}))
-            return records, sel_offsets, offs, cigar, info, pairs, sam
+            pairs, sam, _ = ix.pair_alignments(sel_offsets, records, klass, **popts)
+            return (records, sel_offsets, offs, cigar, info, pairs, sam) + used
         if not both_strands:
             raise ValueError("rescue needs both_strands: a mate is sought on the strand its partner implies")
-        popts, ropts = dict(pair_options or {}), dict(rescue_options or {})
         min_len, min_anchor = int(ropts.pop("min_len", 12)), int(ropts.pop("min_anchor_score", 40))
         where = {key: ropts.pop(key) if key in ropts else popts[key] for key in ("orient", "isize_max") if key in ropts or key in popts}
         if ropts:
@@ -367,20 +393,20 @@ class SMEM:
                                                                     **(select_options or {}))[:4]
             pairs, sam, _ = ix.pair_alignments(sel_offsets, records, klass, **popts)
         offs, cigar, info = ix.chain_cigars(csr, mems[0], mems[1], chains, aln, sel, contigs, both_strands, **opts)
-        return records, sel_offsets, offs, cigar, info, pairs, sam, (windows, status, totals)
+        return (records, sel_offsets, offs, cigar, info, pairs, sam, (windows, status, totals)) + used
 
     def sam_text(self, result, reads, names, contig_names=None, quals=None, contigs=None, tags=N.SAM_NM | N.SAM_AS, seq=True):
         """The SAM records of a mapped batch as text on the device (genie_sam_text) -> (text uint8[bytes], line_offsets
         int64[n_lines + 1], totals int64[3] = (lines, bytes, unmapped lines)): GenieIndex.sam_text.  result: the tuple of
-        map_pairs (7 or 8 results) or of map_records (5 results: single-end mode).  reads: the batch as that call took it,
+        map_pairs (7 to 9 results; only the first five and the seventh are used) or of map_records (5 results: single-end mode).  reads: the batch as that call took it,
         interleaved.  names: one per read, a list of str or bytes or the (bytes, offsets) of index.names_csr or
         text_reads.fastq_fields; contig_names likewise, by default contigs.names, "ref" without contigs.  quals: None (`*`),
         a list of str or bytes with one entry per read, or uint8 parallel to the bases (fastq_fields).  tags: a mask of
         _native.SAM_NM (1), SAM_AS (2), SAM_MD (4), SAM_MC (8), SAM_MQ (16); seq=False writes `*` for SEQ and QUAL."""
         from .index import names_csr
         ix = self.matcher.index(self.lut.lut_size)
-        if len(result) not in (5, 7, 8):
-            raise ValueError("result must be what map_pairs (7 or 8 results) or map_records (5 results) returned")
+        if len(result) not in (5, 7, 8, 9):
+            raise ValueError("result must be what map_pairs (7 to 9 results) or map_records (5 results) returned")
         records, sel_offsets, cigar_offsets, cigar, info = result[:5]
         sam = result[6] if len(result) > 5 else None
         bases, read_offsets = self._csr_reads(reads, False)

@@ -1054,6 +1054,77 @@ int genie_rescue_windows(const genie_index *ix, const int64_t *d_contig_offsets,
                          int64_t *d_totals,                /* 3, may be NULL */
                          void *d_workspace, int64_t workspace_bytes, void *stream);
 
+/* The insert-size distribution of a paired batch, estimated from the batch itself: what genie_pair_alignments and
+ * genie_rescue_windows ask their caller for (orient, isize_min, isize_max, isize_mean) and nobody knows before mapping.  The
+ * pairs whose two heads map confidently to one contig are the sample, as in BWA-MEM's mem_pestat; per combination type their
+ * spans give quartiles, a mean and a deviation without the outliers, and a window.  Everything is integer and deterministic.
+ * Inputs, those of genie_pair_alignments:
+ *   ix       used for the device and the launch sizes.
+ *   N        the number of reads, even (GENIE_E_INVALID otherwise); P = N / 2; mate m of pair k is read 2 k + m.
+ *   records  d_sel_offsets[N + 1], d_records (12 int32 per record) and n_records: genie_select_alignments' outputs.
+ *            R = min(d_sel_offsets[N], n_records).  The records of read r are the rows [so[r], so[r + 1]) clamped to [0, R] and
+ *            ordered; its HEAD is the first of them.  Of a head the columns strand, contig, offset, r_span and mapq are read.
+ * Parameters (int32; the call has no defaults): min_mapq in [0, 60]; max_span in [1, GENIE_WINDOW_MAX / 2], so that an estimated
+ * isize_max is always one that genie_rescue_windows accepts; min_samples in [1, 2^30].
+ * Sample.  Pair k gives a sample (t, s) iff both mates have a head; both heads' mapq column, clamped to [0, 60], is >= min_mapq;
+ * the heads share a contig; t, the combination type of the two heads exactly as genie_pair_alignments defines it (b = offset - 1,
+ * e = b + r_span, a strand other than 0 taken as 1), is FR (0), RF (1) or same (2), type 3 gives no sample; and
+ * 1 <= s <= max_span, where s = max(e) - min(b) is that definition's span.
+ * Per type t, over its n_t samples in ascending order v[0 .. n_t), with integer division:
+ *   q25 = v[min(n_t - 1, (n_t + 1) / 4)], q50 = v[n_t / 2], q75 = v[min(n_t - 1, (3 n_t + 1) / 4)]
+ *         (BWA's (int)(p n + .499) ranks); IQR = q75 - q25;
+ *   lo_b = max(1, q25 - GENIE_ISIZE_OUTLIER_IQR IQR), hi_b = q75 + GENIE_ISIZE_OUTLIER_IQR IQR: the outlier bounds;
+ *   over the n_in samples with lo_b <= s <= hi_b, their sum S:
+ *     mean = floor((2 S + n_in) / (2 n_in));  SS = sum of (s - mean)^2;
+ *     std  = the smallest d >= 0 with d d n_in >= SS: a ceiling, in whole bases.  max_span <= 2^15 and n_in < 2^30: nothing
+ *            leaves int64;
+ *   isize_min = max(0, min(q25 - GENIE_ISIZE_WINDOW_IQR IQR, mean - GENIE_ISIZE_WINDOW_STD std)),
+ *   isize_max = min(max_span, max(q75 + GENIE_ISIZE_WINDOW_IQR IQR, mean + GENIE_ISIZE_WINDOW_STD std)).
+ * A type is OK iff n_t >= min_samples and 20 n_t >= the largest n of the three types (BWA's 5 % rule).  A type that is not OK
+ * still reports n and, when n > 0, its quartiles; its other columns are 0.
+ * Outputs, in caller buffers:
+ *   d_stats    3 x 12 int64, 8-byte aligned, one row per type:
+ *              (n, ok, q25, q50, q75, lo_b, hi_b, n_in, mean, std, isize_min, isize_max)
+ *   d_samples  2 int32 per pair, 8-byte aligned, may be NULL: (t, s) of a pair with a sample, (-1, 0) of any other; for
+ *              histograms and tests.
+ *   d_totals   4 int64, 8-byte aligned, may be NULL: {pairs with both mates mapped, pairs sampled, pairs refused for mapq alone
+ *              (contig, type and span would do), pairs refused for contig, type or span (whatever their mapq)}: the first is the
+ *              sum of the other three; it stays on the device.
+ * No atomic decides a value: the spans are counted into a histogram of max_span + 1 bins per type and the totals are summed with
+ * atomic adds, but every such sum is an integer add, so the counts, and with them every output, do not depend on the order in
+ * which the adds arrive.  Garbage records (negative r_span, wild offsets, contigs, strands, mapq) give undefined statistics, but
+ * no access outside the declared sizes and no unbounded loop: the record ranges are clamped to [0, R] and ordered, a span outside
+ * [1, max_span] is never counted, and every loop runs over at most max_span + 1 bins.
+ * Checked before the device check, so on any handle, in this order.  GENIE_E_INVALID: a null ix, d_sel_offsets or d_stats; an
+ * odd or negative N, a negative size; a null d_records with n_records > 0; a parameter outside its range; d_records not 16-byte,
+ * d_sel_offsets, d_stats, d_samples or d_totals not 8-byte aligned.  Then GENIE_E_TOO_LONG for N or n_records above 2^31 - 1.
+ * Then, for N > 0, a d_workspace that is null, not 256-byte aligned or smaller than
+ * genie_insert_size_stats_workspace_bytes(N, max_span) gives GENIE_E_CAPACITY.  Then GENIE_E_NO_DEVICE.  The record offsets are
+ * checked on the device as genie_pair_alignments checks them (GENIE_E_INVALID), at the cost of the call's only synchronisation
+ * of `stream`.  N == 0 writes zero stats and zero totals and nothing else.
+ * The workspace function returns GENIE_E_INVALID for a negative N or a max_span outside its range, is a multiple of 256 and
+ * monotone in both: 256 bytes for the verdict of the offset check, 256 for the four totals, and 12 bytes per bin (a 4-byte
+ * counter for each of the three types) for max_span + 1 bins, rounded up to 256; nothing per pair.
+ * Kernels: one lane per pair reads three offsets and the three 16-byte rows of each head, writes d_samples and counts the span:
+ * spans below GENIE_ISIZE_LDS_BINS in a histogram of the block in LDS, whose non-zero bins the block adds to the global one when
+ * it is done, spans from GENIE_ISIZE_LDS_BINS on in the global one at once; the totals are summed over the block and added once.
+ * Then one block, 256 lanes per type, finds the three ranks by a scan over the bins, passes over [lo_b, hi_b] for n_in and S
+ * and again for SS, bisects std over [0, max_span] and writes the 36 numbers.  Nothing is sorted. */
+#define GENIE_ISIZE_OUTLIER_IQR 2    /* the three multipliers are BWA-MEM's: choices, not measurements */
+#define GENIE_ISIZE_WINDOW_IQR 3
+#define GENIE_ISIZE_WINDOW_STD 4
+#define GENIE_ISIZE_LDS_BINS 4096    /* spans counted in LDS: a choice sized to three 48 KB blocks on a compute unit */
+int64_t genie_insert_size_stats_workspace_bytes(int64_t N, int32_t max_span);
+int genie_insert_size_stats(const genie_index *ix, int64_t N,
+                            const int64_t *d_sel_offsets,   /* N + 1 */
+                            const int32_t *d_records,       /* 12 * n_records, 16-byte aligned */
+                            int64_t n_records,
+                            int32_t min_mapq, int32_t max_span, int32_t min_samples,
+                            int64_t *d_stats,               /* 3 * 12 */
+                            int32_t *d_samples,             /* 2 * N / 2, 8-byte aligned, may be NULL */
+                            int64_t *d_totals,              /* 4, may be NULL */
+                            void *d_workspace, int64_t workspace_bytes, void *stream);
+
 /* Mate rescue, step 2, and a general call: the MEMs of strand-reads against WINDOWS of the reference, added to the MEM rows of
  * the batch.  Any windows will do, not only genie_rescue_windows'.  The index is not consulted: a window is compared with the
  * strand-read base for base, so a min_len that would be meaningless against the whole reference (12, say) costs the window's
