@@ -399,7 +399,8 @@ class SMEM:
         """The SAM records of a mapped batch as text on the device (genie_sam_text) -> (text uint8[bytes], line_offsets
         int64[n_lines + 1], totals int64[3] = (lines, bytes, unmapped lines)): GenieIndex.sam_text.  result: the tuple of
         map_pairs (7 to 9 results; only the first five and the seventh are used) or of map_records (5 results: single-end mode).  reads: the batch as that call took it,
-        interleaved.  names: one per read, a list of str or bytes or the (bytes, offsets) of index.names_csr or
+        interleaved; strings are encoded with ExactMatch.encode_lenient whatever split_breaks that call had, so a symbol
+        outside the alphabet is written N.  names: one per read, a list of str or bytes or the (bytes, offsets) of index.names_csr or
         text_reads.fastq_fields; contig_names likewise, by default contigs.names, "ref" without contigs.  quals: None (`*`),
         a list of str or bytes with one entry per read, or uint8 parallel to the bases (fastq_fields).  tags: a mask of
         _native.SAM_NM (1), SAM_AS (2), SAM_MD (4), SAM_MC (8), SAM_MQ (16); seq=False writes `*` for SEQ and QUAL."""
@@ -409,7 +410,7 @@ class SMEM:
             raise ValueError("result must be what map_pairs (7 to 9 results) or map_records (5 results) returned")
         records, sel_offsets, cigar_offsets, cigar, info = result[:5]
         sam = result[6] if len(result) > 5 else None
-        bases, read_offsets = self._csr_reads(reads, False)
+        bases, read_offsets = self._csr_reads(reads, True)       # strings as the split_breaks calls took them: N, code 4, is written N
         if contig_names is None:
             contig_names = contigs.names if contigs is not None else ["ref"]
         csr = lambda x: x if isinstance(x, tuple) else names_csr(x)      # noqa: E731
