@@ -7,7 +7,8 @@ CPU fallback.
 """
 from . import _native
 from .exact_match import ExactMatch
-from .index import GenieIndex, InsertSize, cigar_strings, insert_size_options, names_csr, paf_lines, sam_header, sam_lines
+from .index import (GenieIndex, InsertSize, bam_header, bgzf_compress, cigar_strings, insert_size_options, names_csr, paf_lines, sam_header,
+                    sam_lines)
 from .lut import LUT
 from .rmi import RMI
 from .rmi_lut import RMI_LUT
@@ -15,5 +16,5 @@ from .smem import SMEM, create_query_from_ref, create_random_query
 from .contigs import ReferenceSet, SegmentedReferenceSet, reference_segments
 from . import packing, parallel, text_reads
 
-__all__ = ["ExactMatch", "LUT", "RMI", "RMI_LUT", "SMEM", "GenieIndex", "InsertSize", "insert_size_options", "cigar_strings", "paf_lines", "sam_header", "sam_lines", "names_csr", "ReferenceSet", "SegmentedReferenceSet", "reference_segments",
+__all__ = ["ExactMatch", "LUT", "RMI", "RMI_LUT", "SMEM", "GenieIndex", "InsertSize", "insert_size_options", "cigar_strings", "paf_lines", "sam_header", "sam_lines", "bam_header", "bgzf_compress", "names_csr", "ReferenceSet", "SegmentedReferenceSet", "reference_segments",
            "parallel", "packing", "text_reads", "_native", "create_query_from_ref", "create_random_query"]

@@ -75,6 +75,7 @@ SYMBOLS = [
     "genie_rescue_windows", "genie_rescue_windows_workspace_bytes",
     "genie_window_mems", "genie_window_mems_workspace_bytes",
     "genie_sam_text", "genie_sam_text_workspace_bytes",
+    "genie_bam_records", "genie_bam_records_workspace_bytes",
     "genie_reads_from_text", "genie_reads_from_text_tmp_bytes",
     "genie_reads_from_fasta", "genie_reads_from_fasta_tmp_bytes",
     "genie_reference_segments", "genie_reference_segments_tmp_bytes", "genie_segment_coords",
@@ -100,7 +101,7 @@ class GenieError(RuntimeError):
 
 def build(force=False):
     """Compile libgenie_smem.so for gfx950 with hipcc (csrc/Makefile), in-tree."""
-    srcs = [os.path.join(CSRC, f) for f in ("kernels.hip", "index_build.hip", "short_read_kernel.inc", "match_table_kernel.inc", "match_table_body.inc", "match_table_long_body.inc", "split_reads.inc", "long_reads.inc", "long_units.inc", "lu_seg_body.inc", "exact_match.inc", "contigs.inc", "fwd_step.inc", "contig_stats.inc", "min_occ.inc", "mems.inc", "chains.inc", "align.inc", "cigars.inc", "select.inc", "pairs.inc", "insert_size.inc", "windows.inc", "sam_text.inc", "ingest_tiles.inc", "text_reads.inc", "fasta_reads.inc", "segments.inc", "capi.cpp", "index_host.cpp", "genie_internal.h", "Makefile")]
+    srcs = [os.path.join(CSRC, f) for f in ("kernels.hip", "index_build.hip", "short_read_kernel.inc", "match_table_kernel.inc", "match_table_body.inc", "match_table_long_body.inc", "split_reads.inc", "long_reads.inc", "long_units.inc", "lu_seg_body.inc", "exact_match.inc", "contigs.inc", "fwd_step.inc", "contig_stats.inc", "min_occ.inc", "mems.inc", "chains.inc", "align.inc", "cigars.inc", "select.inc", "pairs.inc", "insert_size.inc", "windows.inc", "sam_text.inc", "bam_records.inc", "ingest_tiles.inc", "text_reads.inc", "fasta_reads.inc", "segments.inc", "capi.cpp", "index_host.cpp", "genie_internal.h", "Makefile")]
     srcs.append(os.path.join(os.path.dirname(_PKG), "include", "genie_smem.h"))
     newest = max(os.path.getmtime(s) for s in srcs)
     if force or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < newest:
@@ -203,6 +204,9 @@ def lib():
         "genie_sam_text_workspace_bytes": (i64, [i64, i64]),
         "genie_sam_text": (C.c_int, [vp, vp, i64, vp, vp, i64, i64, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp, vp, i64, vp, vp, i64, i32, i32,
                                      vp, vp, i64, vp, vp, i64, vp]),
+        "genie_bam_records_workspace_bytes": (i64, [i64, i64]),
+        "genie_bam_records": (C.c_int, [vp, vp, i64, vp, vp, i64, i64, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp, vp, i64, vp, vp, i64, i32, i32,
+                                        vp, vp, i64, vp, vp, i64, vp]),
         "genie_reads_from_text_tmp_bytes": (i64, [i64, i64]),
         "genie_reads_from_text": (C.c_int, [vp, i64, i32, i32, vp, vp, i64, vp, i64, vp, vp, i64, vp]),
         "genie_reads_from_fasta_tmp_bytes": (i64, [i64, i64]),

@@ -901,6 +901,39 @@ int64_t genie_sam_text_workspace_bytes(int64_t N, int64_t n_records)
     return sam_text_workspace_bytes(N, n_records);
 }
 
+// the checks that genie_sam_text and genie_bam_records share, in the header's order; `out` holds the call's line or record
+// offsets and its text or data, workspace_needed its workspace function, called only with sizes that passed the checks
+// before it.  GENIE_OK: the device check has passed too.
+static int sam_args(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs, const SamBatch &b, const SamTextOut &out,
+                    const void *d_workspace, int64_t workspace_bytes, int64_t (*workspace_needed)(int64_t, int64_t))
+{
+    // argument checks first: they need no device image
+    if (!ix || !b.read_offsets || !b.sel_offsets || !b.name_offsets || !b.contig_name_offsets || !out.line_offsets) return GENIE_E_INVALID;
+    if (b.N < 0 || b.total_bases < 0 || b.n_records < 0 || b.n_ops < 0 || b.name_bytes < 0 || b.contig_name_bytes < 0 || out.cap_text < 0 ||
+        workspace_bytes < 0)
+        return GENIE_E_INVALID;
+    if (b.sam && (b.N & 1) != 0) return GENIE_E_INVALID;
+    if ((b.tags & ~(GENIE_SAM_NM | GENIE_SAM_AS | GENIE_SAM_MD | GENIE_SAM_MC | GENIE_SAM_MQ)) != 0 || (b.flags & ~GENIE_SAM_NO_SEQ) != 0)
+        return GENIE_E_INVALID;
+    if ((b.total_bases > 0 && !b.bases) || (b.name_bytes > 0 && !b.names) || (b.contig_name_bytes > 0 && !b.contig_names) ||
+        (b.n_ops > 0 && !b.cigar))
+        return GENIE_E_INVALID;
+    if (b.n_records > 0 && (!b.records || !b.info || !b.cigar_offsets)) return GENIE_E_INVALID;
+    if (misaligned(b.records, 15) || misaligned(b.sam, 15) || misaligned(b.info, 15) || misaligned(b.read_offsets, 7) ||
+        misaligned(b.sel_offsets, 7) || misaligned(b.cigar_offsets, 7) || misaligned(b.name_offsets, 7) ||
+        misaligned(b.contig_name_offsets, 7) || misaligned(out.line_offsets, 7) || misaligned(out.totals, 7) || misaligned(b.cigar, 3))
+        return GENIE_E_INVALID;
+    // the table is optional: null with n_contigs == 0, or a table as every contig call takes it
+    if (!d_contig_offsets && n_contigs != 0) return GENIE_E_INVALID;
+    if (d_contig_offsets)
+        if (int rc = contig_args(d_contig_offsets, n_contigs)) return rc;
+    // reads and records are named by an int32 in the table of lines
+    if (b.N > 0x7fffffffll || b.n_records > 0x7fffffffll) return GENIE_E_TOO_LONG;
+    if (b.N > 0 && (!d_workspace || misaligned(d_workspace, 255) || workspace_bytes < workspace_needed(b.N, b.n_records)))
+        return GENIE_E_CAPACITY;
+    return ready(ix);
+}
+
 int genie_sam_text(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs, const uint8_t *d_bases,
                    const int64_t *d_read_offsets, int64_t N, int64_t total_bases, const uint8_t *d_quals, const int64_t *d_sel_offsets,
                    const int32_t *d_records, int64_t n_records, const int32_t *d_sam, const int32_t *d_info,
@@ -910,35 +943,35 @@ int genie_sam_text(const genie_index *ix, const int64_t *d_contig_offsets, int64
                    int64_t *d_line_offsets, uint8_t *d_text, int64_t cap_text, int64_t *d_totals, void *d_workspace,
                    int64_t workspace_bytes, void *stream)
 {
-    // argument checks first: they need no device image
-    if (!ix || !d_read_offsets || !d_sel_offsets || !d_name_offsets || !d_contig_name_offsets || !d_line_offsets) return GENIE_E_INVALID;
-    if (N < 0 || total_bases < 0 || n_records < 0 || n_ops < 0 || name_bytes < 0 || contig_name_bytes < 0 || cap_text < 0 ||
-        workspace_bytes < 0)
-        return GENIE_E_INVALID;
-    if (d_sam && (N & 1) != 0) return GENIE_E_INVALID;
-    if ((tags & ~(GENIE_SAM_NM | GENIE_SAM_AS | GENIE_SAM_MD | GENIE_SAM_MC | GENIE_SAM_MQ)) != 0 || (flags & ~GENIE_SAM_NO_SEQ) != 0)
-        return GENIE_E_INVALID;
-    if ((total_bases > 0 && !d_bases) || (name_bytes > 0 && !d_names) || (contig_name_bytes > 0 && !d_contig_names) ||
-        (n_ops > 0 && !d_cigar))
-        return GENIE_E_INVALID;
-    if (n_records > 0 && (!d_records || !d_info || !d_cigar_offsets)) return GENIE_E_INVALID;
-    if (misaligned(d_records, 15) || misaligned(d_sam, 15) || misaligned(d_info, 15) || misaligned(d_read_offsets, 7) ||
-        misaligned(d_sel_offsets, 7) || misaligned(d_cigar_offsets, 7) || misaligned(d_name_offsets, 7) ||
-        misaligned(d_contig_name_offsets, 7) || misaligned(d_line_offsets, 7) || misaligned(d_totals, 7) || misaligned(d_cigar, 3))
-        return GENIE_E_INVALID;
-    // the table is optional: null with n_contigs == 0, or a table as every contig call takes it
-    if (!d_contig_offsets && n_contigs != 0) return GENIE_E_INVALID;
-    if (d_contig_offsets)
-        if (int rc = contig_args(d_contig_offsets, n_contigs)) return rc;
-    // reads and records are named by an int32 in the table of lines
-    if (N > 0x7fffffffll || n_records > 0x7fffffffll) return GENIE_E_TOO_LONG;
-    if (N > 0 && (!d_workspace || misaligned(d_workspace, 255) || workspace_bytes < sam_text_workspace_bytes(N, n_records)))
-        return GENIE_E_CAPACITY;
-    if (int rc = ready(ix)) return rc;
     const SamBatch b{d_bases, d_read_offsets, N, total_bases, d_quals, d_sel_offsets, d_records, n_records, d_sam, d_info,
                      d_cigar_offsets, d_cigar, n_ops, d_names, d_name_offsets, name_bytes, d_contig_names, d_contig_name_offsets,
                      contig_name_bytes, tags, flags};
-    return launch_sam_text(ix, {d_contig_offsets, n_contigs}, b, {d_line_offsets, d_text, cap_text, d_totals}, d_workspace, stream);
+    const SamTextOut out{d_line_offsets, d_text, cap_text, d_totals};
+    if (int rc = sam_args(ix, d_contig_offsets, n_contigs, b, out, d_workspace, workspace_bytes, sam_text_workspace_bytes)) return rc;
+    return launch_sam_text(ix, {d_contig_offsets, n_contigs}, b, out, d_workspace, stream);
+}
+
+int64_t genie_bam_records_workspace_bytes(int64_t N, int64_t n_records)
+{
+    if (N < 0 || n_records < 0) return (int64_t)GENIE_E_INVALID;
+    return bam_records_workspace_bytes(N, n_records);
+}
+
+int genie_bam_records(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs, const uint8_t *d_bases,
+                      const int64_t *d_read_offsets, int64_t N, int64_t total_bases, const uint8_t *d_quals, const int64_t *d_sel_offsets,
+                      const int32_t *d_records, int64_t n_records, const int32_t *d_sam, const int32_t *d_info,
+                      const int64_t *d_cigar_offsets, const uint32_t *d_cigar, int64_t n_ops, const uint8_t *d_names,
+                      const int64_t *d_name_offsets, int64_t name_bytes, const uint8_t *d_contig_names,
+                      const int64_t *d_contig_name_offsets, int64_t contig_name_bytes, int32_t tags, int32_t flags,
+                      int64_t *d_record_offsets, uint8_t *d_data, int64_t cap_data, int64_t *d_totals, void *d_workspace,
+                      int64_t workspace_bytes, void *stream)
+{
+    const SamBatch b{d_bases, d_read_offsets, N, total_bases, d_quals, d_sel_offsets, d_records, n_records, d_sam, d_info,
+                     d_cigar_offsets, d_cigar, n_ops, d_names, d_name_offsets, name_bytes, d_contig_names, d_contig_name_offsets,
+                     contig_name_bytes, tags, flags};
+    const SamTextOut out{d_record_offsets, d_data, cap_data, d_totals};
+    if (int rc = sam_args(ix, d_contig_offsets, n_contigs, b, out, d_workspace, workspace_bytes, bam_records_workspace_bytes)) return rc;
+    return launch_bam_records(ix, {d_contig_offsets, n_contigs}, b, out, d_workspace, stream);
 }
 
 int genie_contig_coords(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs, const int32_t *d_pos, int32_t stride,

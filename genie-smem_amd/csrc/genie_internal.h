@@ -585,6 +585,9 @@ struct SamTextOut {
 };
 int64_t sam_text_workspace_bytes(int64_t N, int64_t n_records);
 int launch_sam_text(const genie_index *ix, const ContigTable &ctg, const SamBatch &b, const SamTextOut &out, void *ws, void *stream);
+// bam_records.inc: the same batch as uncompressed BAM records; out.line_offsets are the record offsets, out.text the data
+int64_t bam_records_workspace_bytes(int64_t N, int64_t n_records);
+int launch_bam_records(const genie_index *ix, const ContigTable &ctg, const SamBatch &b, const SamTextOut &out, void *ws, void *stream);
 // min_occ.inc: matching statistics and SMEMs of what occurs at least min_occ times
 int64_t match_stats_min_occ_workspace_bytes(int64_t N, int64_t total_bases, int32_t flags);
 int launch_match_stats_min_occ(const genie_index *ix, int32_t min_occ, const CsrBatch &b, int32_t *d_ms, int32_t *d_lohi,

@@ -1433,6 +1433,7 @@ int launch_locate(const genie_index *ix, const int32_t *d_lohi, int32_t stride, 
 #include "align.inc"
 #include "windows.inc"
 #include "sam_text.inc"
+#include "bam_records.inc"
 #include "ingest_tiles.inc"
 #include "text_reads.inc"
 #include "fasta_reads.inc"

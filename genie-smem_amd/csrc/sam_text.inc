@@ -391,14 +391,17 @@ __device__ __forceinline__ long long sam_chosen(const SamInput &in, long long R,
     return -1;
 }
 
-// The line of read r: its record j, or with j < 0 its unmapped line.  -> the position behind its line end
-template <bool kWrite>
-__device__ __forceinline__ long long sam_line(const SamRef &ix, const SamInput &in, long long R, long long r, long long j,
-                                              const SamOut<kWrite> &o, long long pos)
+// What a line says of its record j of read r, or with j < 0 of the read without records: the columns that the text and the BAM
+// record (bam_records.inc) share, derived in this one place
+struct SamFields {
+    long long mate;                       // the mate's chosen record, or -1
+    int flag, mapq, contig, rpos, tlen, strand;
+};
+
+__device__ __forceinline__ SamFields sam_fields(const SamInput &in, long long R, long long r, long long j, int lane)
 {
     const bool paired = sam_all(in.sam != nullptr), mapped = sam_all(j >= 0);
-    const int tags = rfl(in.tags);
-    long long mate = -1;                                             // the mate's chosen record
+    long long mate = -1;
     int flag, mapq = 0, contig = 0, rpos = 0, tlen = 0, strand = 0;
     if (mapped) {
         const int4 r0 = in.rec[3 * j], r1 = in.rec[3 * j + 1];
@@ -417,7 +420,7 @@ __device__ __forceinline__ long long sam_line(const SamRef &ix, const SamInput &
         }
     } else if (paired) {
         flag = 0x1 | 0x4 | ((r & 1) ? 0x80 : 0x40);
-        mate = sam_chosen(in, R, r ^ 1, o.lane);
+        mate = sam_chosen(in, R, r ^ 1, lane);
         if (sam_all(mate < 0)) {
             flag |= 0x8;
         } else {
@@ -429,6 +432,19 @@ __device__ __forceinline__ long long sam_line(const SamRef &ix, const SamInput &
     } else {
         flag = 0x4;
     }
+    return SamFields{mate, flag, mapq, contig, rpos, tlen, strand};
+}
+
+// The line of read r: its record j, or with j < 0 its unmapped line.  -> the position behind its line end
+template <bool kWrite>
+__device__ __forceinline__ long long sam_line(const SamRef &ix, const SamInput &in, long long R, long long r, long long j,
+                                              const SamOut<kWrite> &o, long long pos)
+{
+    const bool paired = sam_all(in.sam != nullptr), mapped = sam_all(j >= 0);
+    const int tags = rfl(in.tags);
+    const SamFields f = sam_fields(in, R, r, j, o.lane);
+    const long long mate = f.mate;
+    const int flag = f.flag, mapq = f.mapq, contig = f.contig, rpos = f.rpos, tlen = f.tlen, strand = f.strand;
     const bool mated = sam_all(mate >= 0), placed = mapped || mated;                        // RNAME and POS are some record's
     pos = sam_bytes(o, pos, in.names, in.no[r], in.no[r + 1]);
     pos = sam_char(o, pos, '\t');
@@ -559,6 +575,42 @@ __global__ void __launch_bounds__(256) sam_finish_kernel(SamInput in, const long
     }
 }
 
+// the batch as the kernels take it
+inline SamInput sam_input(const ContigTable &ctg, const SamBatch &b)
+{
+    const long long nc = ctg.n_contigs > 0 ? ctg.n_contigs : 1;
+    return SamInput{b.bases, reinterpret_cast<const long long *>(b.read_offsets), b.quals, (long long)b.N,
+                    reinterpret_cast<const long long *>(b.sel_offsets), reinterpret_cast<const int4 *>(b.records), (long long)b.n_records,
+                    reinterpret_cast<const int4 *>(b.sam), reinterpret_cast<const int4 *>(b.info),
+                    reinterpret_cast<const long long *>(b.cigar_offsets), b.cigar, b.names,
+                    reinterpret_cast<const long long *>(b.name_offsets), b.contig_names,
+                    reinterpret_cast<const long long *>(b.contig_name_offsets),
+                    ctg.n_contigs > 0 ? reinterpret_cast<const long long *>(ctg.offsets) : nullptr, (int)nc, b.tags, b.flags};
+}
+
+// ST0 .. ST3 for N > 0: the offset checks with the call's one synchronisation, then a.eoff and a.table
+inline int sam_tables(const SamInput &in, const SamBatch &b, const SamArea &a, void *stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t N = b.N, n_rec = b.n_records, bound = N + n_rec;
+    const long long nc = in.nctg;
+    HIP_TRY(hipMemsetAsync(a.flag, 0, 8, s));
+    LAUNCH_BLOCKS(chain_check_kernel, (N + 1 + 255) / 256, 256, 0, s, in.ro, (long long)N, (long long)b.total_bases, a.flag);
+    LAUNCH_BLOCKS(chain_check_kernel, (N + 1 + 255) / 256, 256, 0, s, in.so, (long long)N, 0x7fffffffffffffffll, a.flag);
+    LAUNCH_BLOCKS(chain_check_kernel, (N + 1 + 255) / 256, 256, 0, s, in.no, (long long)N, (long long)b.name_bytes, a.flag);
+    LAUNCH_BLOCKS(chain_check_kernel, (nc + 1 + 255) / 256, 256, 0, s, in.cno, nc, (long long)b.contig_name_bytes, a.flag);
+    if (n_rec > 0) LAUNCH_BLOCKS(sam_cigar_check_kernel, (n_rec + 1 + 255) / 256, 256, 0, s, in, (long long)b.n_ops, a.flag);
+    int bad = 0;
+    HIP_TRY(hipMemcpyAsync(&bad, a.flag, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (bad) return GENIE_E_INVALID;
+    LAUNCH_BLOCKS(sam_empty_kernel, (N + 255) / 256, 256, 0, s, in, a.empty);
+    if (int rc = launch_compact(a.empty, nullptr, N, 1, reinterpret_cast<int64_t *>(a.eoff), nullptr, 0, a.scan_tmp, stream)) return rc;
+    const long long *eoff = a.eoff;
+    LAUNCH_BLOCKS(sam_table_kernel, (bound + 255) / 256, 256, 0, s, in, eoff, a.table);
+    return GENIE_OK;
+}
+
 }  // namespace
 
 int64_t sam_text_workspace_bytes(int64_t N, int64_t n_records)
@@ -578,28 +630,9 @@ int launch_sam_text(const genie_index *ix, const ContigTable &ctg, const SamBatc
     }
     SamArea a;
     sam_layout(static_cast<uint8_t *>(ws), N, n_rec, &a);
-    const long long nc = ctg.n_contigs > 0 ? ctg.n_contigs : 1;
-    const SamInput in{b.bases, reinterpret_cast<const long long *>(b.read_offsets), b.quals, (long long)N,
-                      reinterpret_cast<const long long *>(b.sel_offsets), reinterpret_cast<const int4 *>(b.records), (long long)n_rec,
-                      reinterpret_cast<const int4 *>(b.sam), reinterpret_cast<const int4 *>(b.info),
-                      reinterpret_cast<const long long *>(b.cigar_offsets), b.cigar, b.names,
-                      reinterpret_cast<const long long *>(b.name_offsets), b.contig_names,
-                      reinterpret_cast<const long long *>(b.contig_name_offsets),
-                      ctg.n_contigs > 0 ? reinterpret_cast<const long long *>(ctg.offsets) : nullptr, (int)nc, b.tags, b.flags};
-    HIP_TRY(hipMemsetAsync(a.flag, 0, 8, s));
-    LAUNCH_BLOCKS(chain_check_kernel, (N + 1 + 255) / 256, 256, 0, s, in.ro, (long long)N, (long long)b.total_bases, a.flag);
-    LAUNCH_BLOCKS(chain_check_kernel, (N + 1 + 255) / 256, 256, 0, s, in.so, (long long)N, 0x7fffffffffffffffll, a.flag);
-    LAUNCH_BLOCKS(chain_check_kernel, (N + 1 + 255) / 256, 256, 0, s, in.no, (long long)N, (long long)b.name_bytes, a.flag);
-    LAUNCH_BLOCKS(chain_check_kernel, (nc + 1 + 255) / 256, 256, 0, s, in.cno, nc, (long long)b.contig_name_bytes, a.flag);
-    if (n_rec > 0) LAUNCH_BLOCKS(sam_cigar_check_kernel, (n_rec + 1 + 255) / 256, 256, 0, s, in, (long long)b.n_ops, a.flag);
-    int bad = 0;
-    HIP_TRY(hipMemcpyAsync(&bad, a.flag, 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (bad) return GENIE_E_INVALID;
-    LAUNCH_BLOCKS(sam_empty_kernel, (N + 255) / 256, 256, 0, s, in, a.empty);
-    if (int rc = launch_compact(a.empty, nullptr, N, 1, reinterpret_cast<int64_t *>(a.eoff), nullptr, 0, a.scan_tmp, stream)) return rc;
+    const SamInput in = sam_input(ctg, b);
+    if (int rc = sam_tables(in, b, a, stream)) return rc;
     const long long *eoff = a.eoff;
-    LAUNCH_BLOCKS(sam_table_kernel, (bound + 255) / 256, 256, 0, s, in, eoff, a.table);
     const int2 *table = a.table;
     const long long want = (bound + kSamWaves - 1) / kSamWaves, most = (long long)(ix->num_cus > 0 ? ix->num_cus : 256) * 8;
     const dim3 grid((unsigned)std::min(want, most)), block(kSamWaves * kWave);

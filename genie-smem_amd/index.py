@@ -5,7 +5,10 @@ Everything that computes goes through the C ABI (include/genie_smem.h); torch on
 device memory, the stream and -- multi-GPU -- the one-time broadcast of the index image.
 """
 import ctypes as C
+import os
 import re
+import struct
+import zlib
 from collections import namedtuple
 
 import numpy as np
@@ -65,6 +68,88 @@ def sam_header(contig_names, contig_lengths):
     lines = ["@HD\tVN:1.6\tSO:unsorted\tGO:query"]
     lines += [f"@SQ\tSN:{name}\tLN:{int(length)}" for name, length in zip(contig_names, contig_lengths)]
     return lines + ["@PG\tID:genie-smem_amd\tPN:genie-smem_amd"]
+
+
+def bam_header(contig_names, contig_lengths):
+    """The header of a BAM file (SAMv1 section 4.2) as uncompressed bytes: the magic BAM\\1, l_text, the lines of sam_header
+    joined with "\\n" plus a final "\\n", n_ref, and per contig l_name, the name with a NUL and l_ref.  The records of
+    GenieIndex.bam_records follow it, and bgzf_compress turns the two into the file.  Names are str (UTF-8) or bytes."""
+    names = [x.encode("utf-8") if isinstance(x, str) else bytes(x) for x in contig_names]
+    lengths = [int(v) for v in contig_lengths]
+    if len(names) != len(lengths):
+        raise ValueError("one length per contig name")
+    text = ("\n".join(sam_header([x.decode("latin-1") for x in names], lengths)) + "\n").encode("latin-1")
+    out = [b"BAM\1", struct.pack("<i", len(text)), text, struct.pack("<i", len(names))]
+    for name, length in zip(names, lengths):
+        out += [struct.pack("<i", len(name) + 1), name, b"\0", struct.pack("<i", length)]
+    return b"".join(out)
+
+
+BGZF_PAYLOAD = 0xff00                                # input bytes per block: what they deflate to fits 64 KiB at any level
+BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
+
+
+def _bgzf_block(payload, level):
+    z = zlib.compressobj(level, zlib.DEFLATED, -15)
+    body = z.compress(payload) + z.flush()
+    size = 18 + len(body) + 8                        # the member's header with the BC subfield, the body, CRC32 and ISIZE
+    if size > 0x10000:
+        raise ValueError("a BGZF block above 64 KiB")
+    return b"".join([b"\x1f\x8b\x08\x04\0\0\0\0\0\xff\x06\0BC\x02\0", struct.pack("<H", size - 1), body,
+                     struct.pack("<II", zlib.crc32(payload) & 0xffffffff, len(payload))])
+
+
+def bgzf_blocks(buffers, level=1, threads=None):
+    """The BGZF blocks of the concatenation of `buffers` (bytes or anything with the buffer interface), in order, the EOF block
+    last: a generator, so that a writer holds a few blocks at a time and the buffers are never joined.  See bgzf_compress."""
+    views = [memoryview(x).cast("B") for x in buffers]
+    views = [v for v in views if len(v)]
+    if threads is None:
+        env = os.environ.get("OMP_NUM_THREADS", "")
+        threads = int(env) if env.isdigit() and int(env) > 0 else min(4, os.cpu_count() or 1)
+
+    def pieces():
+        carry = b""                                  # the tail of a buffer that did not fill a payload: copied, below 0xff00 bytes
+        for v in views:
+            at = 0
+            if carry:
+                at = min(BGZF_PAYLOAD - len(carry), len(v))
+                carry += bytes(v[:at])
+                if len(carry) < BGZF_PAYLOAD:
+                    continue
+                yield carry
+                carry = b""
+            whole = at + (len(v) - at) // BGZF_PAYLOAD * BGZF_PAYLOAD
+            for k in range(at, whole, BGZF_PAYLOAD):
+                yield v[k:k + BGZF_PAYLOAD]
+            carry = bytes(v[whole:])
+        if carry:
+            yield carry
+
+    threads = max(1, int(threads)) if sum(len(v) for v in views) > BGZF_PAYLOAD else 1      # no pool for one block
+    if threads == 1:
+        for x in pieces():
+            yield _bgzf_block(x, level)
+    else:
+        from collections import deque
+        from concurrent.futures import ThreadPoolExecutor
+        with ThreadPoolExecutor(threads) as pool:
+            pending = deque()                        # at most four blocks per thread in flight, taken in order
+            for x in pieces():
+                pending.append(pool.submit(_bgzf_block, x, level))
+                if len(pending) >= 4 * threads:
+                    yield pending.popleft().result()
+            while pending:
+                yield pending.popleft().result()
+    yield BGZF_EOF
+
+
+def bgzf_compress(data, level=1, threads=None):
+    """data (bytes or any buffer) as a BGZF stream (SAMv1 section 4.1): cut into payloads of at most 0xff00 bytes, each one
+    gzip member with the BC extra subfield (BSIZE = the member's length - 1), raw deflate at `level`, CRC32 and ISIZE; then
+    the 28-byte EOF block.  The blocks are independent and zlib releases the GIL, so a pool of `threads` compresses them: by
+    default OMP_NUM_THREADS when that is set, else min(4, the CPUs there are).  The result does not depend on it."""
+    return b"".join(bgzf_blocks([data], level, threads))
 
 
 _COMPLEMENT = str.maketrans("ACGTNacgtn", "TGCANtgcan")
@@ -1070,6 +1155,22 @@ class GenieIndex:
         text_reads.fastq_fields); quals: uint8 parallel to bases, or None (`*`); contigs: the ReferenceSet of the records, or
         None for one contig; tags: a mask of SAM_NM, SAM_AS, SAM_MD, SAM_MC, SAM_MQ; seq=False writes `*` for SEQ and QUAL.
         Two native calls: one sizes the text, one fills it."""
+        return self._sam_bytes("genie_sam_text", bases, read_offsets, sel_offsets, records, sam, info, cigar_offsets, cigar, names,
+                               name_offsets, contig_names, contig_name_offsets, quals, contigs, tags, seq)
+
+    def bam_records(self, bases, read_offsets, sel_offsets, records, sam, info, cigar_offsets, cigar, names, name_offsets, contig_names,
+                    contig_name_offsets, quals=None, contigs=None, tags=N.SAM_NM | N.SAM_AS, seq=True):
+        """The same batch as uncompressed BAM alignment records on the device (genie_bam_records) -> (data uint8[bytes],
+        record_offsets int64[n + 1], totals int64[3] = (records, bytes, unmapped records)): record l is data[record_offsets[l] :
+        record_offsets[l + 1]], one per line of sam_text and in its order, block_size first.  The arguments and their forms are
+        sam_text's; of contig_names only the count matters (BAM names a contig by its index).  bam_header(...) + data, through
+        bgzf_compress, is a BAM file.  Two native calls: one sizes the data, one fills it."""
+        return self._sam_bytes("genie_bam_records", bases, read_offsets, sel_offsets, records, sam, info, cigar_offsets, cigar, names,
+                               name_offsets, contig_names, contig_name_offsets, quals, contigs, tags, seq)
+
+    def _sam_bytes(self, entry, bases, read_offsets, sel_offsets, records, sam, info, cigar_offsets, cigar, names, name_offsets,
+                   contig_names, contig_name_offsets, quals, contigs, tags, seq):
+        """sam_text and bam_records: two calls with the same arguments, and bytes, offsets and totals of one shape."""
         bases, read_offsets, n_reads, total, _, _, _ = self._csr_call(bases, read_offsets)
         sel_offsets = self._as_dev(sel_offsets, torch.int64).reshape(-1)
         records, info = self._as_dev(records, torch.int32), self._as_dev(info, torch.int32)
@@ -1104,17 +1205,17 @@ class GenieIndex:
         opt = lambda t: _ptr(t) if t is not None and t.numel() else none      # noqa: E731
         line_offsets = torch.empty(n_reads + n_rec + 1, dtype=torch.int64, device=self.device)
         totals = torch.empty(3, dtype=torch.int64, device=self.device)
-        ws, ws_bytes = self._workspace("genie_sam_text_workspace_bytes", n_reads, n_rec)
+        ws, ws_bytes = self._workspace(entry + "_workspace_bytes", n_reads, n_rec)
         if sam is not None and n_rec == 0:
             sam = torch.zeros((1, 4), dtype=torch.int32, device=self.device)       # an address: NULL is single-end mode
         head = (*table, _ptr(bases), _ptr(read_offsets), n_reads, total, _ptr(quals), _ptr(sel_offsets),
                 opt(records), n_rec, _ptr(sam), opt(info), _ptr(cigar_offsets), opt(cigar), cigar.numel(),
                 opt(names), _ptr(name_offsets), names.numel(), opt(contig_names), _ptr(contig_name_offsets), contig_names.numel(),
                 int(tags), 0 if seq else N.SAM_NO_SEQ, _ptr(line_offsets))
-        self._run("genie_sam_text", *head, none, 0, _ptr(totals), _ptr(ws), ws_bytes)
+        self._run(entry, *head, none, 0, _ptr(totals), _ptr(ws), ws_bytes)
         n_lines, n_bytes, _ = (int(x) for x in totals.cpu())
         text = torch.empty(max(n_bytes, 1), dtype=torch.uint8, device=self.device)
-        self._run("genie_sam_text", *head, _ptr(text), n_bytes, _ptr(totals), _ptr(ws), ws_bytes)
+        self._run(entry, *head, _ptr(text), n_bytes, _ptr(totals), _ptr(ws), ws_bytes)
         return text[:n_bytes], line_offsets[:n_lines + 1], totals
 
     def contig_coords(self, contigs, pos, stride=1):

@@ -404,6 +404,16 @@ class SMEM:
         text_reads.fastq_fields; contig_names likewise, by default contigs.names, "ref" without contigs.  quals: None (`*`),
         a list of str or bytes with one entry per read, or uint8 parallel to the bases (fastq_fields).  tags: a mask of
         _native.SAM_NM (1), SAM_AS (2), SAM_MD (4), SAM_MC (8), SAM_MQ (16); seq=False writes `*` for SEQ and QUAL."""
+        return self._sam_bytes("sam_text", result, reads, names, contig_names, quals, contigs, tags, seq)
+
+    def bam_records(self, result, reads, names, contig_names=None, quals=None, contigs=None, tags=N.SAM_NM | N.SAM_AS, seq=True):
+        """The same batch as uncompressed BAM alignment records on the device (genie_bam_records) -> (data uint8[bytes],
+        record_offsets int64[n + 1], totals int64[3] = (records, bytes, unmapped records)): GenieIndex.bam_records.  The
+        arguments and their forms are sam_text's; one record per line of sam_text, in its order."""
+        return self._sam_bytes("bam_records", result, reads, names, contig_names, quals, contigs, tags, seq)
+
+    def _sam_bytes(self, method, result, reads, names, contig_names, quals, contigs, tags, seq):
+        """sam_text and bam_records: the input forms they share, then GenieIndex's method of that name."""
         from .index import names_csr
         ix = self.matcher.index(self.lut.lut_size)
         if len(result) not in (5, 7, 8, 9):
@@ -416,8 +426,8 @@ class SMEM:
         csr = lambda x: x if isinstance(x, tuple) else names_csr(x)      # noqa: E731
         if isinstance(quals, (list, tuple)):
             quals = names_csr(quals)[0]
-        return ix.sam_text(bases, read_offsets, sel_offsets, records, sam, info, cigar_offsets, cigar, *csr(names), *csr(contig_names),
-                           quals=quals, contigs=contigs, tags=tags, seq=seq)
+        return getattr(ix, method)(bases, read_offsets, sel_offsets, records, sam, info, cigar_offsets, cigar, *csr(names), *csr(contig_names),
+                                   quals=quals, contigs=contigs, tags=tags, seq=seq)
 
     def write_sam(self, path, result, reads, names, contig_names=None, contig_lengths=None, **options):
         """A SAM file: the header lines of index.sam_header, then the text of sam_text(result, reads, names, contig_names,
@@ -433,6 +443,23 @@ class SMEM:
         with open(path, "wb") as f:
             f.write(("\n".join(sam_header(contig_names, contig_lengths)) + "\n").encode())
             f.write(text.cpu().numpy().tobytes())
+        return totals
+
+    def write_bam(self, path, result, reads, names, contig_names=None, contig_lengths=None, level=1, **options):
+        """A BAM file: index.bam_header, then the records of bam_records(result, reads, names, contig_names, **options) in one
+        copy from the device, the two compressed as by index.bgzf_compress at `level` and written block by block -> totals.
+        Names and lengths default as in write_sam.  The records are in the order of the reads (unsorted, grouped by query), as
+        the header says."""
+        from .index import bam_header, bgzf_blocks
+        contigs = options.get("contigs")
+        if contig_names is None:
+            contig_names = contigs.names if contigs is not None else ["ref"]
+        if contig_lengths is None:
+            contig_lengths = np.diff(contigs.offsets) if contigs is not None else [self.matcher.index(self.lut.lut_size).n]
+        data, _, totals = self.bam_records(result, reads, names, contig_names, **options)
+        with open(path, "wb") as f:
+            for block in bgzf_blocks([bam_header(contig_names, contig_lengths), data.cpu().numpy()], level):
+                f.write(block)
         return totals
 
     def locate_contigs(self, contigs, rows):

@@ -1296,6 +1296,87 @@ int genie_sam_text(const genie_index *ix, const int64_t *d_contig_offsets, int64
                    int64_t *d_totals,                   /* 3, may be NULL */
                    void *d_workspace, int64_t workspace_bytes, void *stream);
 
+/* The same batch as uncompressed BAM ALIGNMENT RECORDS in device memory (SAMv1 section 4.2): what a BAM file holds between its
+ * header and its end, before BGZF compression.  The inputs, through `tags, flags`, are genie_sam_text's in its order and with
+ * its meaning, single-end mode (d_sam == NULL) included.  One record per line of genie_sam_text, in the same order: read by read
+ * and for each read record by record, a read without records one unmapped record.  The record of line l has the FLAG, MAPQ,
+ * contig, POS, mate record m, PNEXT, TLEN and strand that genie_sam_text derives for that line (above): the unmapped line's flag
+ * bits, its place at the LAST record of its mate that is neither secondary nor supplementary, and the single-end rules are
+ * those and are not restated here.
+ * The bytes of a record, little-endian, no padding; records lie back to back, so a record starts at any byte alignment:
+ *   block_size  int32   the record's length minus 4
+ *   refID       int32   RNAME's contig index clamped to [0, nc), -1 where the line has `*`
+ *   pos         int32   POS - 1
+ *   l_read_name uint8   the stored name's length + 1
+ *   mapq        uint8   MAPQ clamped to [0, 255]
+ *   bin         uint16  SAMv1's reg2bin(beg, end) on int64 with arithmetic shifts, cut to 16 bits: beg = pos, end = beg + the
+ *                       sum of the lengths of the ops with the codes 0, 2, 3, 7, 8, or beg + 1 when that sum is 0; pos -1
+ *                       gives 4680
+ *   n_cigar_op  uint16
+ *   flag        uint16  FLAG's low 16 bits
+ *   l_seq       int32   the read's length, 0 under GENIE_SAM_NO_SEQ
+ *   next_refID  int32   -1 for RNEXT `*`, else record m's contig index clamped (for `=` that is refID)
+ *   next_pos    int32   PNEXT - 1
+ *   tlen        int32
+ *   read_name   the name's first min(length, 254) bytes and a NUL; an empty name is stored as `*`
+ *   cigar       the record's ops as they are, uint32 each; none for a record without ops
+ *   seq         (l_seq + 1) / 2 bytes, base 2 i in the high nibble of byte i; codes 0..3 are 1, 2, 4, 8, anything else 15; the
+ *               unused low nibble of an odd length is 0.  A record whose strand column is not 0 has the complement in reverse
+ *               order (N stays N), as SEQ in genie_sam_text
+ *   qual        l_seq bytes max(q - 33, 0), reversed on that strand; every byte 0xFF with d_quals == NULL
+ *   tags        NM, AS, MD, MC, MQ in that order under the text's conditions: NM and AS on record lines only, MD on a record
+ *               with ops, MC when m exists and has ops, MQ when m exists; an unmapped record has MC and MQ only.  NM, AS, MQ
+ *               are of type `i` (two letters, `i`, int32: 7 bytes); MD and MC of type `Z`: two letters, `Z`, the characters
+ *               genie_sam_text writes behind MD:Z: and MC:Z:, and a NUL
+ * More than 65535 ops (SAMv1 4.2.2): n_cigar_op is 2, the cigar field holds l_seq << 4 | 4 and then min(reference span,
+ * 2^28 - 1) << 4 | 3, and the real ops follow all other tags as `CG`, `B`, `I`, an int32 count and the ops; bin is still that of
+ * the real ops.
+ * Outputs, all in caller buffers:
+ *   d_record_offsets  N + n_records + 1 int64 of capacity, 8-byte aligned; with n = R + (reads without records) the entries
+ *                     0 .. n are written, entry [n] the true byte total even when cap_data is smaller
+ *   d_data            cap_data bytes; NULL is the sizing call.  Record l is the bytes [d_record_offsets[l],
+ *                     d_record_offsets[l + 1]); bytes at or past cap_data are dropped and nothing is written outside the buffer
+ *   d_totals          3 int64, 8-byte aligned, may be NULL: {records, bytes, unmapped records}; it stays on the device
+ * No atomic decides a value: the bytes are a function of the inputs alone.  Garbage records, d_sam or d_info rows or ops give
+ * undefined bytes, but no access outside the declared sizes and no unbounded loop, under genie_sam_text's clamps: every store
+ * lies below min(the record's end, cap_data), and the loop over the letters of an X or a D in MD ends there too.  A record of
+ * more than 2^31 - 1 bytes is cut to that length, and block_size says the length it was cut to.
+ * The argument checks, their order and their results are genie_sam_text's word for word, with d_record_offsets, d_data and
+ * cap_data in the places of d_line_offsets, d_text and cap_text and genie_bam_records_workspace_bytes as the bound of the
+ * workspace; then GENIE_E_NO_DEVICE; then the same device check of the five offset arrays, GENIE_E_INVALID, at the cost of the
+ * call's only synchronisation of `stream`.  N == 0 writes d_record_offsets[0] = 0 and zero totals.
+ * The workspace function returns GENIE_E_INVALID for negative arguments, is a multiple of 256 and monotone in both.  Its pieces
+ * are those of genie_sam_text_workspace_bytes: per read 4 (the mark of a read without records) and 8 (the number of such reads
+ * before it, N + 1 entries), per record of the N + n_records there can be 8 (its read and record), 4 (its length) and 8 (its
+ * offset, one entry more), 8 per 1024 records (the scan), each piece rounded up to 256 on its own, and 256 for the verdict of
+ * the offset checks.
+ * Kernels: one wave per record, in a sizing pass and a write pass over the same walk.  Where a field lies is closed-form but for
+ * MD and MC, so the sizing pass loads ops only when one of the two is asked for.  Nothing is stored wider than a byte, the lanes
+ * of a step on consecutive addresses: one lane per byte of the name, of QUAL and of the ops, one lane per byte (two bases) of
+ * SEQ; the loop that copies the ops also sums their reference span for bin, so the 36-byte head goes last.  Cost of a record:
+ * about (name + 1.5 bases) / 64 + 5 ceil(ops / 64) wave steps, plus genie_sam_text's 2 ceil(ops / 64) each for MD and MC. */
+int64_t genie_bam_records_workspace_bytes(int64_t N, int64_t n_records);
+int genie_bam_records(const genie_index *ix, const int64_t *d_contig_offsets, int64_t n_contigs,
+                      const uint8_t *d_bases, const int64_t *d_read_offsets,  /* N + 1 */
+                      int64_t N, int64_t total_bases,
+                      const uint8_t *d_quals,              /* total_bases, may be NULL */
+                      const int64_t *d_sel_offsets,        /* N + 1 */
+                      const int32_t *d_records,            /* 12 * n_records, 16-byte aligned */
+                      int64_t n_records,
+                      const int32_t *d_sam,                /* 4 * n_records, 16-byte aligned; NULL: single-end mode */
+                      const int32_t *d_info,               /* 8 * n_records, 16-byte aligned */
+                      const int64_t *d_cigar_offsets,      /* R + 1 */
+                      const uint32_t *d_cigar, int64_t n_ops,
+                      const uint8_t *d_names, const int64_t *d_name_offsets /* N + 1 */, int64_t name_bytes,
+                      const uint8_t *d_contig_names, const int64_t *d_contig_name_offsets /* max(n_contigs, 1) + 1 */,
+                      int64_t contig_name_bytes,
+                      int32_t tags, int32_t flags,
+                      int64_t *d_record_offsets,           /* N + n_records + 1 */
+                      uint8_t *d_data,                     /* cap_data; may be NULL: sizing only */
+                      int64_t cap_data,
+                      int64_t *d_totals,                   /* 3, may be NULL: {records, bytes, unmapped records} */
+                      void *d_workspace, int64_t workspace_bytes, void *stream);
+
 /* Matching statistics and SMEMs that are EXACT WITH RESPECT TO THE SEQUENCE SET.  genie_match_stats and the SMEM calls on a
  * reference of several sequences answer for the concatenation; genie_locate_contigs then drops the occurrences that bridge
  * two sequences, and with them seeds.  Contigs ACGT | TTGA and the read CGTT: the concatenation holds CGTT once, across the
